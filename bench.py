@@ -5,24 +5,32 @@ One "step" = one launch of atom_gemm_w4a4_f16 (through the C ABI) on the headlin
 (configs[2]: M=N=K=4096, group 128, 128 INT8 outlier columns), operands resident in HBM, synthetic uniform random
 int4/int8 codes and U(0.005,0.05) fp16 scales (never zeros: zero data clocks ~19 % higher).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--M 4096 --N 4096 --K 4096] [--format f6|packed|wide] [--no-cpu-baseline]
-                    [--no-configs] [--no-block] [--no-decode] [--workload gemm|block]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--M 4096 --N 4096 --K 4096] [--format f6|packed|wide]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-configs] [--no-block] [--no-decode]]
+                    [--workload gemm|block]
                     [--ramp 1500]   (untimed set-up launches ahead of the W warm-up steps: power-state ramp after idle;
                                      reported as "ramp" in the JSON line)
+
+A plain run sets up, ramps and warms up, times the K steps and prints the line; nothing else.  --dump-outputs DIR then writes
+what the last timed step computed -- the fp16 output D of the GEMM -- as DIR/out.npy in float32: all of it where that fits in
+32 MiB, else a fixed sample of its rows (np.random.default_rng(0), sorted; 2048 of the 4096 rows at the default size).  The
+operands are seeded, so two runs with the same arguments compute on the same inputs.
 
 --gpus N > 1 without a torch.distributed environment (no WORLD_SIZE): bench.py starts the N ranks itself
 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>); under
 torch.distributed.run WORLD_SIZE must equal --gpus.  "n_gpus" in the JSON line is the number of ranks that ran.
 
 The headline runs the operand format the drop-in modules use for prefill batches (F6: both operands BF6-coded, block-scaled
-MFMA); at N=1 the reference's packed-nibble format and the wide-activation format are timed beside it (same codes, same
-scales, outputs compared bit for bit) and reported under "other_operand_formats", as is the packed format on the re-coding
-route three ways: "packed_ws" (C ABI + caller-owned workspace, nothing cached), "packed_ws_same_weight" (the caller asserts
-ATOM_WS_WEIGHT_CACHED: one weight repeated) and "packed_ops" (atom_amd.ops with two weights in alternation: its per-weight
+MFMA).  --full adds the side measurements, each timed on its own after the headline's steps: at N=1 the reference's
+packed-nibble format and the wide-activation format are timed beside it (same codes, same scales, outputs compared bit for
+bit) and reported under "other_operand_formats", as is the packed format on the re-coding route three ways: "packed_ws"
+(C ABI + caller-owned workspace, nothing cached), "packed_ws_same_weight" (the caller asserts ATOM_WS_WEIGHT_CACHED:
+one weight repeated) and "packed_ops" (atom_amd.ops with two weights in alternation: its per-weight
 cache; = "abi_value").  Also at N=1: "cold" (the headline with 512 MB flushed between launches) and "configs" -- the other
 BASELINE configs (config 2 M=1, the corners of config 5, the 4096-wide batch sweep), HIP-graph replay per launch, hot and with
 the weights streamed from HBM (--no-configs skips it), and "block" -- BASELINE config 4 (one Llama-7B decoder block at batch 32 x
-seq 2048, KV INT4) through --workload block in its own process, with its GEMM / quantiser / attention split (--no-block skips it).
+seq 2048, KV INT4) through --workload block in its own process, with its GEMM / quantiser / attention split (--no-block skips it),
+"decode_layer" (--no-decode skips it) and "cpu_baseline" (--no-cpu-baseline skips it).
 
 N > 1: one process per GPU (torch.distributed.run), every rank runs an independent replica (the path is a
 single-device per-layer GEMM: "replicas only", no collective on the data path); value = all ranks' ops / max time.
@@ -250,6 +258,20 @@ def kernel_source_sha():
     return h.hexdigest()
 
 
+DUMP_BYTES = 32 << 20
+
+
+def dump_outputs(d, out):
+    """DIR/out.npy: the output as float32, whole where it fits in DUMP_BYTES, else a fixed, seeded sample of its rows."""
+    os.makedirs(d, exist_ok=True)
+    a = out.float().cpu().numpy() if isinstance(out, torch.Tensor) else np.asarray(out, np.float32)
+    a = a.reshape(a.shape[0], -1)
+    n = max(1, DUMP_BYTES // (4 * a.shape[1]))
+    if a.shape[0] > n:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))]
+    np.save(os.path.join(d, "out.npy"), np.ascontiguousarray(a, np.float32))
+
+
 def spawn_ranks(n, argv):
     """--gpus N without a torch.distributed environment: start the N ranks the way the driver would."""
     import socket
@@ -375,6 +397,12 @@ def main():
                                                            "reported in the JSON line")
     ap.add_argument("--format", choices=["f6", "packed", "wide"], default="f6",
                     help="operand format of the headline measurement (the other two are reported beside it at N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements: cold launches, the other operand formats, the "
+                         "other BASELINE configs, the Llama-7B block, the decode layer and the CPU baseline (N=1 only; the --no-* "
+                         "options below skip single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/out.npy (float32; a fixed sample of rows above 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the side sweep over the other BASELINE configs (N=1 only)")
     ap.add_argument("--with-block", action="store_true", help="(the default since round 5; kept so that older command lines parse)")
@@ -411,6 +439,8 @@ def main():
         def step():
             acc.add_(eye @ eye)
         wall, kern_ms = timed_steps(step, args.steps, args.warmup, lambda: None, dist, dev)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, acc)
         if rank == 0:
             agg = aggregate(world, args.steps, wall, kern_ms, M, N, K)
             print(json.dumps({"metric": "stub", "value": agg["value"], "unit": "TOPS", "n_gpus": world, "steps": args.steps,
@@ -425,6 +455,8 @@ def main():
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if args.workload == "block":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the GEMM workload's output (--workload gemm)")
         return block_workload(args, rank, world, dev)
     dist = None
     if world > 1:
@@ -505,12 +537,14 @@ def main():
     if args.ramp:                                # ... and one dry pass through the timing apparatus itself (event creation, first
         timed_steps(step, 2, 0, sync, dist, dev)  # synchronize / barrier of the process): 2 more untimed launches, counted in "ramp"
     wall, kern_ms = timed_steps(step, args.steps, args.warmup, sync, dist, dev)
+    if rank == 0 and args.dump_outputs:                          # D holds the last timed step's output until a side run below
+        dump_outputs(args.dump_outputs, D)
 
-    # N=1 only: the headline kernel with every operand byte coming from HBM ("additionally reported with a 512 MB flush
-    # buffer"), then the other operand formats beside the headline, and a bit-for-bit comparison of the outputs
+    # --full, N=1 only: the headline kernel with every operand byte coming from HBM ("additionally reported with a 512 MB
+    # flush buffer"), then the other operand formats beside the headline, and a bit-for-bit comparison of the outputs
     others = {}
     cold = None
-    if world == 1:
+    if world == 1 and args.full:
         c_mean, c_med, c_n = cold_launches(step, dev)
         cold = {"kernel_us": round(c_mean, 2), "median_us": round(c_med, 2), "launches": c_n,
                 "value": round(2.0 * M * N * K / (c_mean * 1e-6) / 1e12, 2), "unit": "TOPS",
@@ -585,11 +619,11 @@ def main():
                 out["abi_value_note"] = ("TOPS of the same GEMM called with the reference's packed operand format through atom_amd.ops, two "
                                          "weights in alternation (packed_ops); packed_ws = nothing cached, "
                                          "packed_ws_same_weight = the round-3 figure (one weight repeated)")
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             del a6, b6, wide
             torch.cuda.empty_cache()
             out["configs"] = configs_sweep(dev)
-        if world == 1 and not args.no_block:                     # BASELINE configs[3] at its stated size in the same line (its own
+        if world == 1 and args.full and not args.no_block:       # BASELINE configs[3] at its stated size in the same line (its own
             import subprocess                                    # process: fresh allocator state; ~1 minute)
             torch.cuda.empty_cache()
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "block", "--steps", "3", "--warmup", "1",
@@ -614,7 +648,7 @@ def main():
                                         "*_attn_sdpa = the same block with the opt-in args.attn_sdpa (torch's fused attention)"}
             except Exception as e:                               # pragma: no cover
                 out["block"] = {"error": f"{type(e).__name__}: {e}; stderr tail: {r.stderr[-300:]}"}
-        if world == 1 and not args.no_decode:                    # the decode step of a Llama-7B layer (reference punica/models/llama.py:259-292):
+        if world == 1 and args.full and not args.no_decode:      # the decode step of a Llama-7B layer (reference punica/models/llama.py:259-292):
             import subprocess                                    # its own process too (tools/cold_bench.py: HIP-graph replay, hot / cold)
             torch.cuda.empty_cache()
             r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cold_bench.py"), "layer", "1,16"], capture_output=True, text=True)
@@ -637,7 +671,7 @@ def main():
                                                "55.3 / 59.7 us"}
             except Exception as e:                               # pragma: no cover
                 out["decode_layer"] = {"error": f"{type(e).__name__}: {e}; stderr tail: {r.stderr[-300:]}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(M, N, K)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -69,3 +69,32 @@ def test_bench_gpus_flag_must_match_world_size():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub-step"], capture_output=True,
                          text=True, timeout=120, env=env, cwd=ROOT)
     assert out.returncode != 0 and "WORLD_SIZE" in (out.stderr + out.stdout)
+
+
+def test_bench_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR writes what the timed path computed in its last step as float32 (the stub step: acc += I each step)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--stub-step",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["steps"] == 5 and r["ms_per_step"] > 0
+    import numpy as np
+    a = np.load(tmp_path / "dump" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (64, 64)
+    assert np.array_equal(a, 7 * np.eye(64, dtype=np.float32))
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """Above the size limit the dump is a fixed, seeded sample of rows, the same from run to run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    x = torch.arange(4096 * 4096, dtype=torch.float32).reshape(4096, 4096).half()
+    bench.dump_outputs(str(tmp_path / "a"), x)
+    bench.dump_outputs(str(tmp_path / "b"), x)
+    a, b = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "b" / "out.npy")
+    assert a.dtype == np.float32 and a.nbytes <= bench.DUMP_BYTES and a.shape == (2048, 4096)
+    assert np.array_equal(a, b)

@@ -225,8 +225,6 @@ def test_append_and_decode_vs_reference_cpu_implementation(seqlens, heads, block
     cpu_reference::append_paged_kv_cache byte for byte; atom_batch_decode_i4 is within 2e-3 of cpu_reference::single_quantize_mha
     (FP32, std::exp / std::cos) on the gathered keys and values of every sequence."""
     from tests import ref_golden as R
-    if not R.available():
-        pytest.skip("oracle/_ref/libatom_ref.so not built (needs /root/reference)")
     from atom_amd import ops
     pool, cs, kv, g = _setup(seqlens, heads=heads, block=block, seed=7)
     T = sum(seqlens)

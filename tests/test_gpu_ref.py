@@ -10,8 +10,7 @@ from oracle import atom_oracle as O
 from tests import ref_golden as R
 from tests.helpers import bits16, rand_act, t2n
 
-pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(not R.available(), reason="oracle/_ref/libatom_ref.so not built (needs /root/reference)")]
+pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 256), (37, 4096), (16, 11008), (8, 5120), (130, 4096)]
 

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." || exit 1
 O=gpurun_out/r05; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -12 > $O/pytest_gpu_full.txt
 cat $O/pytest_gpu_full.txt
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 600 $O/bench_default.err
 python3 - <<PY
 import json

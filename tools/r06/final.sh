@@ -11,4 +11,4 @@ ATOM_LIB=$PWD/build/tools/libatom_hip.so timeout 300 python tools/r06/gemvq_trac
 build/tools/trace_f6q 4096 4096 4096 > $O/trace_f6q.txt 2>&1; head -3 $O/trace_f6q.txt | cut -c1-200
 bash tools/profile_bench.sh > $O/profile_bench.log 2>&1; tail -3 $O/profile_bench.log
 ls gpurun_out/prof_summary
-python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 1500 $O/bench_line.json
+python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 1500 $O/bench_line.json

@@ -6,4 +6,4 @@ O=gpurun_out/r06; mkdir -p $O
 build/tools/trace_f6q 4096 4096 4096 > $O/trace_f6q.txt 2>&1; tail -12 $O/trace_f6q.txt | cut -c1-400
 bash tools/profile_bench.sh > $O/profile_bench.log 2>&1; tail -5 $O/profile_bench.log
 ls gpurun_out/prof_summary
-python bench.py > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json
+python bench.py --full > $O/bench_line.json 2> $O/bench.err; tail -c 600 $O/bench_line.json

@@ -76,7 +76,7 @@ def main(raw, out):
         if "FETCH_SIZE" in summ and "WRITE_SIZE" in summ:
             fetch_kib, write_kib = summ["FETCH_SIZE"]["mean"], summ["WRITE_SIZE"]["mean"]
             json.dump({
-                "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python bench.py --no-cpu-baseline",
+                "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python bench.py --full --no-cpu-baseline",
                 "kernel": KERNELS[fmt] + "  M=N=K=4096", "operand_format": fmt,
                 "FETCH_SIZE_KiB_per_launch": fetch_kib, "WRITE_SIZE_KiB_per_launch": write_kib,
                 "correction": "FETCH_SIZE and WRITE_SIZE divided by what the same counters report per KiB of a known stream of the same "
