@@ -1,0 +1,367 @@
+// Prefill / chunked-prefill attention over the INT4 paged KV cache on gfx950: causal multi-query attention with RoPE fused.
+//
+//   atom_batch_prefill_i4   o[row, h] = softmax_{j <= p}( <RoPE(q[row, h], p), RoPE(deq K[b, h, j], j)> / sqrt(128) ) . deq V[b, h, j]
+//
+// Sequence b holds len_b tokens in the cache (layout of kv_i4.hip); its queries are rows qo_indptr[b] .. qo_indptr[b+1] and sit at its
+// LAST q_b positions: query i at p = len_b - q_b + i.  So a prompt from an empty cache, a chunk on a cached prefix and a multi-token
+// verification step are one operation; with q_b = 1 it is what atom_batch_decode_i4 computes.  (The reference never bound an INT4
+// prefill: its prefill attends to random K/V, punica/models/llama.py:164-167.)
+//
+// Geometry: one workgroup of 4 waves per (query block of 64 rows, sequence, head, KV split); wave w owns rows 16 w .. 16 w + 15 of the
+// block.  The query blocks farthest from the diagonal (most key tiles) are dispatched first.  Per 64-key tile the 256 threads read the
+// tile's INT4 K / V (thread = (key, quarter): K as the two 8-byte halves of its 16 RoPE pairs, V as 16 bytes -- the decode kernel's
+// load), de-quantise to FP32 (nibble * scale - zero), rotate K at each key's own position, round to f16 and stage both in LDS; keys
+// past the sequence end (uninitialised memory, possibly NaN / Inf) are staged as zeros and never loaded.  K is de-quantised again in
+// every query block of its (sequence, head): VALU work in place of a second pass through HBM for an f16 copy of the whole cache.
+//
+// Products, per wave, on v_mfma_f32_16x16x32_f16 with FP32 accumulation:
+//   S^T[key][q] = K . Q^T   A = K rows from LDS (ds_read_b128, 16-byte chunks XOR-swizzled by key), B = the rotated q in registers.
+//                           The accumulator puts a query row on the lane (lane & 15) and 4 keys in the registers: the softmax state
+//                           (running maximum, denominator) of a row lives in the 4 lanes that share lane & 15.
+//   O^T[d][q]  = V^T . P^T  B = P straight from the S accumulator (keys 16kt + 4g + r in the order the registers hold them, k-step s
+//                           takes tiles 2s, 2s+1), A = the V rows of the SAME key order, read column-wise from the row-major V image
+//                           with ds_read_b64_tr_b16 (T10; chunks XOR-swizzled by (key & 7) << 1 so a half-wave's two 4-row blocks
+//                           hit distinct banks).  O^T has the row on the lane too: rescaling by the row's factor is lane-local.
+// Softmax: online, FP32, base 2 (scores scaled by log2(e) / sqrt(128)); the maximum is reduced over the 4 lanes of a row per tile, the
+// denominator once at the end.  Causal mask: tiles past a wave's last row are skipped, the select (-inf score) runs only on tiles that
+// cross a wave's first row; masking is a select before the exponent, and masked / zeroed entries enter the MFMAs as exact zeros.
+//
+// Numerics: q, rotated K, P and V are rounded to f16 as MFMA operands -- the only departure from the FP32 decode op (no bf16: its
+// 8x larger rounding would need another bound).  RoPE angles in revolutions through v_sin / v_cos, as the decode kernel.
+//
+// Short chunks on long prefixes (few query blocks, many key tiles): the KV range of a block is split over `splits` workgroups that
+// write the decode op's partial states float [rows][heads][splits][130] to the workspace, merged by decode_merge_kernel (kv_attn.h)
+// with the query rows as its "batch".
+#include <math.h>
+
+#include <algorithm>
+#include "common.h"
+#include "kv_attn.h"
+
+namespace atom {
+
+constexpr int kPfRows = 64;    // query rows per workgroup (4 waves x 16)
+constexpr int kPfKeys = 64;    // keys per tile
+constexpr int kPfThreads = 256;
+
+typedef _Float16 pf_h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 pf_h4 __attribute__((ext_vector_type(4)));
+typedef short pf_s4 __attribute__((ext_vector_type(4)));
+typedef float pf_f2 __attribute__((ext_vector_type(2)));
+
+struct PrefillParams {
+  const uint8_t *data;
+  const half_t *param;
+  const int32_t *kv_indptr, *kv_indices, *last_page_offset, *qo_indptr;
+  const half_t *q;   // [T, N, 128]
+  half_t *o;         // [T, N, 128] (splits == 1)
+  float *ws;         // splits > 1: [T, N, splits, 130]
+  int batch, L, layer, N, P;
+  int nqb;           // query blocks per sequence: ceil(max_q_len / 64)
+  int splits;
+  float qk_scale, log2_theta, rope_inv_scale;
+};
+
+// sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
+__device__ __forceinline__ void pf_sincos_rev(float rev, float &s, float &c) {
+  const float fr = rev - floorf(rev);
+  s = __builtin_amdgcn_sinf(fr);
+  c = __builtin_amdgcn_cosf(fr);
+}
+
+struct PfTileRegs {   // one thread's share of a 64-key tile, as loaded: K dims [16u, 16u+16) and [64+16u, 64+16u+16), V dims [32u, 32u+32)
+  v2u k1, k2;
+  v4u v;
+  unsigned kq, vq;    // (scale, zero) half2 of the key
+};
+
+// LDS images [64 keys][128 dims] f16, 256-byte rows; chunk = 8 dims (16 bytes)
+__device__ __forceinline__ int k_off(int key, int ch) { return key * 256 + 16 * (ch ^ (key & 15)); }
+__device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * (ch ^ ((key & 7) << 1)); }
+
+__global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
+  __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
+  __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
+  __shared__ float rope_fr[64];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = p.N, P = p.P;
+  // heavy-first order: the last query blocks (the most key tiles) get the lowest workgroup ids
+  const int per_qb = p.batch * N * p.splits;
+  const int idx = blockIdx.x;
+  const int qb = p.nqb - 1 - idx / per_qb;
+  const int rem = idx - (idx / per_qb) * per_qb;
+  const int bh = rem / p.splits, sp = rem - bh * p.splits;
+  const int b = bh / N, h = bh - b * N;
+
+  const int qbeg = p.qo_indptr[b], q_b = p.qo_indptr[b + 1] - qbeg;
+  const int q0 = qb * kPfRows;
+  if (q0 >= q_b) return;                                  // (uniform over the workgroup: before any barrier)
+  const int pg0 = p.kv_indptr[b];
+  const int len = (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
+  const int prefix = len - q_b;                           // position of query 0
+  const int kend = prefix + min(q0 + kPfRows, q_b);       // keys this block sees: 0 .. kend-1
+  const int ntiles = kend > 0 ? (kend + kPfKeys - 1) / kPfKeys : 0;
+  const int chunk = (ntiles + p.splits - 1) / p.splits;
+  const int t0 = sp * chunk, t1 = min(ntiles, t0 + chunk);
+
+  if (tid < 64)   // decode.cuh:535-539 / batch_decode_kernel: freq = rope_inv_scale * theta^(-2 i / 128), here in revolutions
+    rope_fr[tid] = p.rope_inv_scale * 0.15915494309189535f * __builtin_amdgcn_exp2f(-p.log2_theta * (float)(2 * tid) * (1.0f / kHeadDim));
+  __syncthreads();
+
+  // ---- my query row: lane (li, g) = (row 16 w + li of the block, k-group); B operand of S^T: q[row][32 ks + 8 g .. + 7], ks = 0..3.
+  // ks = 0 / 2 and 1 / 3 hold the two halves of the RoPE pairs (i, i + 64) with i = 8 g + j and 32 + 8 g + j.
+  const int li = lane & 15, g = lane >> 4;
+  const int qi = q0 + 16 * w + li;                        // query index within the sequence
+  const bool row_ok = qi < q_b;
+  const int pos = prefix + qi;
+  const bool wave_live = q0 + 16 * w < q_b;               // (wave-uniform) any row of this wave exists
+  const int pmin_w = prefix + q0 + 16 * w, pmax_w = pmin_w + 15;
+  pf_h8 qf[4];
+  {
+    v4u raw[4];
+    const half_t *qp = p.q + ((int64_t)(qbeg + (row_ok ? qi : 0)) * N + h) * kHeadDim + 8 * g;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) raw[ks] = row_ok ? *reinterpret_cast<const v4u *>(qp + 32 * ks) : v4u{0u, 0u, 0u, 0u};
+    const pf_h8 *x = reinterpret_cast<const pf_h8 *>(raw);
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float s, c;
+        pf_sincos_rev((float)pos * rope_fr[32 * hf + 8 * g + j], s, c);
+        const float x1 = (float)x[hf][j], x2 = (float)x[hf + 2][j];
+        qf[hf][j] = (half_t)(x1 * c - x2 * s);
+        qf[hf + 2][j] = (half_t)(x2 * c + x1 * s);
+      }
+  }
+
+  // ---- staging: thread (key kk, quarter u)
+  const int kk = tid >> 2, u = tid & 3;
+  const int64_t blk = (int64_t)N * P;                     // tokens x heads of one (page, layer, K|V) block
+  const uint8_t *kbase = p.data + ((int64_t)p.layer * 2 * N + h) * P * 64;
+  const half_t *qpbase = p.param + ((int64_t)p.layer * 2 * N + h) * P * 2;
+  const int64_t page_bytes = (int64_t)p.L * 2 * blk * 64, page_halves = (int64_t)p.L * 2 * blk * 2;
+  auto load = [&](int tile) -> PfTileRegs {
+    PfTileRegs r;
+    const int j = tile * kPfKeys + kk;
+    if (j < len) {
+      const int pg = j / P, e = j - pg * P;
+      const int64_t page = p.kv_indices[pg0 + pg];
+      const uint8_t *kp = kbase + page * page_bytes + e * 64;
+      const half_t *pp = qpbase + page * page_halves + e * 2;
+      r.k1 = *reinterpret_cast<const v2u *>(kp + 8 * u);
+      r.k2 = *reinterpret_cast<const v2u *>(kp + 32 + 8 * u);
+      r.v = *reinterpret_cast<const v4u *>(kp + blk * 64 + 16 * u);
+      r.kq = *reinterpret_cast<const unsigned *>(pp);
+      r.vq = *reinterpret_cast<const unsigned *>(pp + blk * 2);
+    } else {
+      r.k1 = v2u{0u, 0u};
+      r.k2 = v2u{0u, 0u};
+      r.v = v4u{0u, 0u, 0u, 0u};
+      r.kq = r.vq = 0u;
+    }
+    return r;
+  };
+  auto stage = [&](int tile, const PfTileRegs &r) {
+    const int j = tile * kPfKeys + kk;
+    const bool ok = j < len;                              // past the end: zeros (the loaded registers are zeros too, see load)
+    const float ks = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq & 0xFFFF)) : 0.f;
+    const float kz = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq >> 16)) : 0.f;
+    const float vs = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.vq & 0xFFFF)) : 0.f;
+    const float vz = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.vq >> 16)) : 0.f;
+    // K: pair m = dims (16u + m, 64 + 16u + m); word hw of k1 / k2 holds m = 8 hw .. 8 hw + 7, nibble e at bits 4e
+    pf_h8 klo[2], khi[2];
+#pragma unroll
+    for (int hw = 0; hw < 2; ++hw)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int m = 8 * hw + e;
+        const float x1 = __builtin_fmaf((float)((r.k1[hw] >> (4 * e)) & 0xF), ks, -kz);
+        const float x2 = __builtin_fmaf((float)((r.k2[hw] >> (4 * e)) & 0xF), ks, -kz);
+        float s, c;
+        pf_sincos_rev((float)j * rope_fr[16 * u + m], s, c);
+        klo[hw][e] = (half_t)(x1 * c - x2 * s);
+        khi[hw][e] = (half_t)(x2 * c + x1 * s);
+      }
+    char *kl = reinterpret_cast<char *>(Ks);
+    *reinterpret_cast<pf_h8 *>(kl + k_off(kk, 2 * u)) = klo[0];
+    *reinterpret_cast<pf_h8 *>(kl + k_off(kk, 2 * u + 1)) = klo[1];
+    *reinterpret_cast<pf_h8 *>(kl + k_off(kk, 8 + 2 * u)) = khi[0];
+    *reinterpret_cast<pf_h8 *>(kl + k_off(kk, 8 + 2 * u + 1)) = khi[1];
+    // V: word vw holds dims 32u + 8 vw .. + 7
+    char *vl = reinterpret_cast<char *>(Vs);
+#pragma unroll
+    for (int vw = 0; vw < 4; ++vw) {
+      pf_h8 vv;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vv[e] = (half_t)__builtin_fmaf((float)((r.v[vw] >> (4 * e)) & 0xF), vs, -vz);
+      *reinterpret_cast<pf_h8 *>(vl + v_off(kk, 4 * u + vw)) = vv;
+    }
+  };
+
+  v4f O[8];
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) O[dt] = v4f{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;                   // row state (m reduced over the row's 4 lanes; l: this lane's keys only)
+
+  PfTileRegs regs;
+  if (t0 < t1) regs = load(t0);
+  for (int tile = t0; tile < t1; ++tile) {
+    __syncthreads();                                      // the previous tile's LDS reads are done
+    stage(tile, regs);
+    __syncthreads();
+    if (tile + 1 < t1) regs = load(tile + 1);             // in flight during this tile's products
+    const int kt0 = tile * kPfKeys;
+    if (!wave_live || kt0 > pmax_w) continue;             // (wave-uniform) no row of this wave sees a key of this tile
+    // ---- S^T = K . Q^T
+    v4f S[4];
+    const char *kl = reinterpret_cast<const char *>(Ks);
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) {
+      S[kt] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const pf_h8 a = *reinterpret_cast<const pf_h8 *>(kl + k_off(16 * kt + li, 4 * ks + g));
+        S[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qf[ks], S[kt], 0, 0, 0);
+      }
+    }
+    // ---- online softmax; lane holds row li's scores of keys kt0 + 16 kt + 4 g + r
+    const bool masked = kt0 + kPfKeys - 1 > pmin_w;       // (wave-uniform) some key of the tile is past some row's position
+    float mt = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s = S[kt][r] * p.qk_scale;
+        if (masked && kt0 + 16 * kt + 4 * g + r > pos) s = -INFINITY;
+        S[kt][r] = s;
+        mt = fmaxf(mt, s);
+      }
+    mt = fmaxf(mt, __shfl_xor(mt, 16));
+    mt = fmaxf(mt, __shfl_xor(mt, 32));
+    const float m_new = fmaxf(m_run, mt);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new; // (a row with every key masked so far: exp2(-inf - 0) = 0, no NaN)
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+    m_run = m_new;
+    float ls = 0.f;
+    pf_h8 pf[2];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pr = __builtin_amdgcn_exp2f(S[kt][r] - m_use);
+        ls += pr;
+        pf[kt >> 1][4 * (kt & 1) + r] = (half_t)pr;
+      }
+    l_run = __builtin_fmaf(l_run, alpha, ls);
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) O[dt] *= alpha;
+    // ---- O^T += V^T . P^T; k-step s: element j of lane group g is key 32 s + 16 (j >> 2) + 4 g + (j & 3)
+    const char *vl = reinterpret_cast<const char *>(Vs);
+    const int tq = li >> 2, tp = li & 3;                  // transposed read: lane 4 tq + tp addresses row tq, dims 4 tp .. 4 tp + 3
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        pf_h4 half2x[2];
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          const int row = 32 * s + 16 * hh + 4 * g + tq;
+          const int off = v_off(row, 2 * dt + (tp >> 1)) + 8 * (tp & 1);
+          const pf_s4 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) pf_s4 *)(const_cast<char *>(vl) + off));
+          half2x[hh] = __builtin_bit_cast(pf_h4, t);
+        }
+        const pf_h8 a = {half2x[0][0], half2x[0][1], half2x[0][2], half2x[0][3], half2x[1][0], half2x[1][1], half2x[1][2], half2x[1][3]};
+        O[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, pf[s], O[dt], 0, 0, 0);
+      }
+  }
+
+  // ---- the row's denominator over its 4 lanes; lane holds O[row][16 dt + 4 g + r]
+  float l_all = l_run + __shfl_xor(l_run, 16);
+  l_all += __shfl_xor(l_all, 32);
+  if (!row_ok) return;
+  const int64_t orow = (int64_t)(qbeg + qi) * N + h;
+  if (p.splits == 1) {
+    const float rl = l_all > 0.f ? 1.0f / l_all : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+      const pf_h4 hv = {(half_t)(O[dt][0] * rl), (half_t)(O[dt][1] * rl), (half_t)(O[dt][2] * rl), (half_t)(O[dt][3] * rl)};
+      *reinterpret_cast<pf_h4 *>(p.o + orow * kHeadDim + 16 * dt + 4 * g) = hv;
+    }
+  } else {
+    float *wp = p.ws + (orow * p.splits + sp) * (kHeadDim + 2);
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+      *reinterpret_cast<pf_f2 *>(wp + 16 * dt + 4 * g) = pf_f2{O[dt][0], O[dt][1]};
+      *reinterpret_cast<pf_f2 *>(wp + 16 * dt + 4 * g + 2) = pf_f2{O[dt][2], O[dt][3]};
+    }
+    if (g == 0) {
+      wp[kHeadDim] = m_run;
+      wp[kHeadDim + 1] = l_all;
+    }
+  }
+}
+
+// KV splits: only where the query blocks leave the chip short of work (short chunks on long prefixes).  Aim at ~2 workgroups per CU
+// (256 CUs) with at least 4 key tiles per split.
+static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages) {
+  if (max_pages <= 0) return 1;
+  const int64_t blocks = (int64_t)batch * N * ((max_q_len + kPfRows - 1) / kPfRows);
+  const int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  if (blocks >= 512 || tiles < 8) return 1;
+  int64_t s = (512 + blocks - 1) / blocks;
+  s = std::min<int64_t>(s, tiles / 4);
+  s = std::min<int64_t>(s, 32);
+  return (int)std::max<int64_t>(s, 1);
+}
+
+}  // namespace atom
+
+using namespace atom;
+
+extern "C" {
+
+size_t atom_batch_prefill_i4_workspace_bytes(int64_t total_q, int batch, int num_heads, int page_size, int max_q_len,
+                                             int max_pages_per_seq) {
+  if (total_q < 1 || batch < 1 || num_heads < 1 || page_size < 16 || max_q_len < 1) return 0;
+  const int s = prefill_splits(batch, num_heads, (int)std::min<int64_t>(max_q_len, total_q), page_size, max_pages_per_seq);
+  return s > 1 ? (size_t)total_q * num_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+}
+
+int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                          const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                          int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
+                          float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads,
+                          page_size, head_dim);
+  if (st != ATOM_OK) return st;
+  if (!o || !q || !qo_indptr || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
+  if (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1) return ATOM_ERR_SHAPE;
+  if (!aligned16(o) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
+  const int mq = (int)std::min<int64_t>(max_q_len, total_q);
+  const int nqb = (mq + kPfRows - 1) / kPfRows;
+  int splits = prefill_splits(batch, num_heads, mq, page_size, max_pages_per_seq);
+  const size_t need = (size_t)total_q * num_heads * splits * (kHeadDim + 2) * sizeof(float);
+  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
+  const int64_t grid = (int64_t)nqb * batch * num_heads * splits;
+  if (grid > 0x7fffffff || (int64_t)total_q * num_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
+  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, qo_indptr,
+                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_heads, page_size, nqb, splits,
+                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(batch_prefill_kernel, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  if (splits > 1) {
+    const unsigned rows = (unsigned)(total_q * num_heads);
+    if (splits <= 8)
+      hipLaunchKernelGGL(decode_merge_kernel<8>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
+    else if (splits <= 16)
+      hipLaunchKernelGGL(decode_merge_kernel<16>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
+    else
+      hipLaunchKernelGGL(decode_merge_kernel<32>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
+  }
+  return check_launch();
+}
+
+}  // extern "C"

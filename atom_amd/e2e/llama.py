@@ -42,7 +42,11 @@ class DecodeFusion:
                  (Rounds 3-5 ran it in every 16-feature workgroup of the decode-batch kernel: only reorder -> o_proj paid, default 2.)
       q_mask2    the same choice for a step of TWO tokens: their projections with K <= 4096 run the decode-batch kernel (two tokens double
                  the dot-product kernel's arithmetic per weight chunk), where only reorder -> o_proj pays: default 2 (66-67 us per layer
-                 cold; 15 measures 69-71)"""
+                 cold; 15 measures 69-71)
+      prefill_attn  prefill requests from an EMPTY cache attend through the HIP prefill op (ops.batch_prefill_i4, one launch for all of
+                 them) instead of the torch route (FP32 de-quantisation + SDPA per request).  Requests with a cached prefix (chunked
+                 prefill, a continued prompt) always take the HIP op: the torch route cannot see the prefix.  Default off: prompts from
+                 an empty cache keep the torch route's numbers until the op's are reviewed against them."""
     decode: bool = True
     kv_append: bool = True
     kv_in_decode: bool = True
@@ -50,6 +54,7 @@ class DecodeFusion:
     q_decode: bool = True
     q_mask: int = 15
     q_mask2: int = 2
+    prefill_attn: bool = False
 
 
 FUSION = DecodeFusion()
@@ -247,7 +252,8 @@ class LlamaAttention(nn.Module):
     decode requests through the RoPE-fused batch-decode kernel, output reordered + quantised + projected.
     Prefill requests: the reference attends to RANDOM keys and values there (llama.py:164-167, "HACK": a latency
     harness); this class attends to the de-quantised projections it has just written to the cache (causal, RoPE at
-    positions 0..len-1) -- the values a later decode step reads back."""
+    positions 0..len-1) -- the values a later decode step reads back.  A prefill request whose cache already holds tokens (chunked
+    prefill: its length exceeds the request's) attends to them too, through ops.batch_prefill_i4 (DecodeFusion.prefill_attn)."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -279,6 +285,13 @@ class LlamaAttention(nn.Module):
     def forward(self, hidden_states, blen: BatchLenInfo, prefill_kv: BatchedKvCacheInt4 | None,
                 decode_kv: BatchedKvCacheInt4 | None) -> torch.Tensor:
         nh, hd = self.num_heads, self.head_dim
+        prefixes = []
+        if len(blen.prefills) > 0:
+            # cached tokens in front of each prefill request's chunk (host-side lengths: no synchronisation)
+            assert prefill_kv is not None
+            prefixes = [s - n for s, n in zip(prefill_kv.seqlens, blen.prefills)]
+            if len(prefixes) != len(blen.prefills) or min(prefixes) < 0:
+                raise ValueError(f"prefill requests of {list(blen.prefills)} tokens do not fit caches of {list(prefill_kv.seqlens)} tokens")
         rows = hidden_states[0].size(0)
         pure_decode = (len(blen.prefills) == 0 and blen.decode == rows and self.fusion.kv_append
                        and ops.decode_gemm_fits(rows, self.hidden_size, self.hidden_size))
@@ -307,16 +320,23 @@ class LlamaAttention(nn.Module):
             ks = k_sz[:blen.doff].view(-1, nh, 2)
             vs = v_sz[:blen.doff].view(-1, nh, 2)
             ops.init_kv_i4(prefill_kv, k, v, ks, vs, blen.indptr, self.layer_idx)
-            kf, vf = dequant_kv_u4(k, ks), dequant_kv_u4(v, vs)
-            beg = 0
-            for q_len in blen.prefills:
-                sl = slice(beg, beg + q_len)
-                pos = torch.arange(q_len, device=q_proj.device)
-                q = rope_llama(q_proj[sl].view(q_len, nh, hd).float(), pos, self.rope_theta).transpose(0, 1)
-                kk = rope_llama(kf[sl], pos, self.rope_theta).transpose(0, 1)
-                o = torch.nn.functional.scaled_dot_product_attention(q, kk, vf[sl].transpose(0, 1), is_causal=True)
-                outs.append(o.transpose(0, 1).reshape(q_len, self.hidden_size).to(q_proj.dtype))
-                beg += q_len
+            if self.fusion.prefill_attn or max(prefixes) > 0:
+                # every prefill request in ONE launch, over its cached prefix and its new tokens (csrc/prefill_i4.hip)
+                q = q_proj[:blen.doff].view(-1, nh, hd)
+                o = ops.batch_prefill_i4(q, blen.indptr, prefill_kv, self.layer_idx, rope_theta=self.rope_theta,
+                                         max_q_len=max(blen.prefills))
+                outs.append(o.view(blen.doff, self.hidden_size))
+            else:
+                kf, vf = dequant_kv_u4(k, ks), dequant_kv_u4(v, vs)
+                beg = 0
+                for q_len in blen.prefills:
+                    sl = slice(beg, beg + q_len)
+                    pos = torch.arange(q_len, device=q_proj.device)
+                    q = rope_llama(q_proj[sl].view(q_len, nh, hd).float(), pos, self.rope_theta).transpose(0, 1)
+                    kk = rope_llama(kf[sl], pos, self.rope_theta).transpose(0, 1)
+                    o = torch.nn.functional.scaled_dot_product_attention(q, kk, vf[sl].transpose(0, 1), is_causal=True)
+                    outs.append(o.transpose(0, 1).reshape(q_len, self.hidden_size).to(q_proj.dtype))
+                    beg += q_len
         if blen.decode > 0:
             assert decode_kv is not None
             q = q_proj[blen.doff:].view(blen.decode, nh, hd)

@@ -662,6 +662,37 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     return o if merge else part
 
 
+
+def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
+                     max_q_len: int = None):
+    """Prefill / chunked-prefill attention over the INT4 paged cache, causal, RoPE fused (atom_batch_prefill_i4).  q fp16
+    [T, heads, 128] (not yet rotated); qo_indptr int32 [batch + 1] on the device: sequence b's queries are rows
+    qo_indptr[b] .. qo_indptr[b+1] and its LAST positions in the cache (already written there, init_kv_i4).  ``max_q_len``: host-side
+    bound of every sequence's query count (default T; it sizes the grid).  No host synchronisation: capturable in a graph.  With one
+    query per sequence the output is batch_decode_i4's (fp16 matrix-core operands: within rounding of it)."""
+    _require_cuda_half(q, "q")
+    for t in (qo_indptr, kv.data, kv.param):
+        if not t.is_cuda:
+            raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
+    num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
+    total = q.size(0)
+    assert q.shape == (total, num_heads, head_dim) and q.is_contiguous()
+    assert qo_indptr.dtype == torch.int32 and qo_indptr.is_contiguous()
+    batch = kv.last_page_offset.numel()
+    assert qo_indptr.numel() == batch + 1
+    max_q = total if max_q_len is None else int(max_q_len)
+    lib = L.lib()
+    max_pages = int(getattr(kv, "max_pages", 0))
+    ws_bytes = lib.atom_batch_prefill_i4_workspace_bytes(total, batch, num_heads, page_size, max_q, max_pages)
+    ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+    o = torch.empty_like(q)
+    st = lib.atom_batch_prefill_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, kv.data.data_ptr(),
+                                   kv.param.data_ptr(), kv.indptr.data_ptr(), kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(),
+                                   batch, num_layers, int(layer_idx), num_heads, page_size, head_dim, float(rope_theta),
+                                   float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+    L.check(st, "atom_batch_prefill_i4")
+    return o
+
 def kv_fake_quant(x: torch.Tensor, n_bits: int = 4, clip: float = 1.0) -> torch.Tensor:
     """Asymmetric per-head-vector fake quantisation of a [batch, heads, seq, 128] fp16 tensor (any strides over the first
     three dims) -- quantize_attn_k_wrapper / quantize_attn_v_wrapper of the reference (model/quant.py:233-257)."""

@@ -1,7 +1,7 @@
 """INT4 paged KV-cache bookkeeping with the API of the reference's ``punica/utils/kvcache.py`` (KvPoolInt4 :6-55,
 KvCacheInt4 :58-98, BatchedKvCacheInt4 :101-128): same class / property / method names and the same tensor layouts, so
 code written against the reference's objects runs on these.  Host-side only; the device work is in atom_amd.ops
-(init_kv_i4 / append_kv_i4 / batch_decode_i4 -> csrc/kv_i4.hip).
+(init_kv_i4 / append_kv_i4 / batch_decode_i4 -> csrc/kv_i4.hip, batch_prefill_i4 -> csrc/prefill_i4.hip).
 
 Pool layout (reference kvcache.py:17-26, page.cuh:78-110):
     buf    uint8 [capacity, num_layers, 2, num_heads, block_len, head_dim // 2]   packed u4, K at [.., 0, ..], V at [.., 1, ..]
@@ -57,6 +57,13 @@ class KvCacheInt4:
             self._indicies.append(self._pool.alloc_block())
         self._seqlen += 1
 
+    def acquire(self, n: int):
+        """Make room for ``n`` more tokens (a chunk of a prefill: n x acquire_one)."""
+        if n < 0:
+            raise ValueError("n must be non-negative")
+        for _ in range(n):
+            self.acquire_one()
+
     def release(self):
         for idx in self._indicies:
             self._pool.free_block(idx)
@@ -80,6 +87,7 @@ class BatchedKvCacheInt4:
         self.last_page_offset = torch.tensor([(c.seqlen - 1) % pool.block_len + 1 for c in kv], dtype=torch.int32,
                                              device=device)
         self.max_pages = max(counts)            # host-side hint for the decode kernel's KV split (not in the reference)
+        self.seqlens = [c.seqlen for c in kv]   # host-side lengths: the prefill attention's cached prefixes (not in the reference)
 
     @property
     def page_size(self):

@@ -439,6 +439,27 @@ int atom_batch_decode_append_i4(void *o, const void *q, const void *k_f32, const
                                 int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
                                 float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Prefill / chunked-prefill attention over the same cache: causal multi-query attention, RoPE fused.  Sequence b's queries are rows
+ * qo_indptr[b] .. qo_indptr[b+1] of q (fp16 [total_q, heads, 128], not yet rotated; qo_indptr int32 [batch+1] on the device) and
+ * sit at the LAST q_b positions of its len_b cached tokens (the tokens atom_kv_append_i4 has just written there): query i at
+ * p = len_b - q_b + i, attending to keys 0 .. p.
+ *   o[row,h,:] (fp16) = softmax_{j <= p}( <RoPE(q[row,h], p), RoPE(dequant K[b,h,j], j)> / sqrt(128) ) . dequant V[b,h,j]
+ * With one query per sequence this is atom_batch_decode_i4.  q, the rotated keys, the softmax weights and the de-quantised values
+ * are rounded to fp16 as matrix-core operands (FP32 accumulation, FP32 softmax): the only departure from the FP32 arithmetic of
+ * the decode op.  Cache slots past a sequence's end are never read.
+ * max_q_len: host-side bound of every q_b (it sizes the grid; a sequence with more queries is an error the op cannot see);
+ * max_pages_per_seq (0 = unknown) lets few query blocks on long prefixes split their KV range: FP32 partial states go to
+ * `workspace` (atom_batch_prefill_i4_workspace_bytes; NULL / too small = no split) and a second launch merges them.
+ * Errors: ATOM_ERR_INVALID_ARG for a null pointer (o, q, qo_indptr or a cache table), rope_theta <= 0 or rope_scale <= 0;
+ * ATOM_ERR_SHAPE for head_dim != 128, page_size not a multiple of 16, a layer out of range, batch / num_heads < 1, total_q < 1
+ * or max_q_len < 1; ATOM_ERR_ALIGN for q / o / kv_data not 16-byte aligned or kv_param / qo_indptr not 4-byte aligned. */
+size_t atom_batch_prefill_i4_workspace_bytes(int64_t total_q, int batch, int num_heads, int page_size, int max_q_len,
+                                             int max_pages_per_seq);
+int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                          const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                          int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
+                          float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
+
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised
  * asymmetrically to n_bits in FP16 opmath -- scale = ((max - min) * clip).clamp(1e-5) / (2^n - 1), base =
