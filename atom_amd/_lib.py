@@ -83,6 +83,11 @@ SIGNATURES = {
     "atom_batch_decode_append_i4": (_int, [_vp] * 9 + [_int] * 6 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_batch_prefill_i4_workspace_bytes": (ctypes.c_size_t, [_i64, _int, _int, _int, _int, _int]),
     "atom_batch_prefill_i4": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 6 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_decode_gqa_i4_workspace_bytes": (ctypes.c_size_t, [_int] * 5),
+    "atom_batch_decode_gqa_i4_splits": (_int, [_int] * 5),
+    "atom_batch_decode_gqa_i4": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_prefill_gqa_i4_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 6),
+    "atom_batch_prefill_gqa_i4": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -53,13 +53,14 @@ struct PrefillParams {
   const uint8_t *data;
   const half_t *param;
   const int32_t *kv_indptr, *kv_indices, *last_page_offset, *qo_indptr;
-  const half_t *q;   // [T, N, 128]
-  half_t *o;         // [T, N, 128] (splits == 1)
-  float *ws;         // splits > 1: [T, N, splits, 130]
-  int batch, L, layer, N, P;
-  int nqb;           // query blocks per sequence: ceil(max_q_len / 64)
+  const half_t *q;   // [T, Nq, 128]
+  half_t *o;         // [T, Nq, 128] (splits == 1)
+  float *ws;         // splits > 1: [T, Nq, splits, 130]
+  int batch, L, layer, N, P;   // N: heads of the cache (K/V heads)
+  int nqb;           // query blocks per (sequence, K/V head): ceil(max_q_len * G / 64)
   int splits;
   float qk_scale, log2_theta, rope_inv_scale;
+  int G, Nq;         // GQA kernel only: query heads per K/V head, query heads (N * G); qo_indptr NULL = one query per sequence
 };
 
 // sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
@@ -79,6 +80,9 @@ struct PfTileRegs {   // one thread's share of a 64-key tile, as loaded: K dims 
 __device__ __forceinline__ int k_off(int key, int ch) { return key * 256 + 16 * (ch ^ (key & 15)); }
 __device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * (ch ^ ((key & 7) << 1)); }
 
+// GQA: a block's rows are (query, head of the group) pairs, query-major -- row r of (sequence b, K/V head h) is query r / G of query head
+// h G + r % G -- so every staged tile serves the whole group.  The MHA instantiation is the kernel with G = 1 (the same code).
+template <bool kGqa>
 __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
   __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
   __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
@@ -87,6 +91,7 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int N = p.N, P = p.P;
+  const int G = kGqa ? p.G : 1, Nq = kGqa ? p.Nq : N;
   // heavy-first order: the last query blocks (the most key tiles) get the lowest workgroup ids
   const int per_qb = p.batch * N * p.splits;
   const int idx = blockIdx.x;
@@ -95,13 +100,15 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int bh = rem / p.splits, sp = rem - bh * p.splits;
   const int b = bh / N, h = bh - b * N;
 
-  const int qbeg = p.qo_indptr[b], q_b = p.qo_indptr[b + 1] - qbeg;
+  const bool one_q = kGqa && !p.qo_indptr;               // (the GQA decode entry point)
+  const int qbeg = one_q ? b : p.qo_indptr[b], q_b = one_q ? 1 : p.qo_indptr[b + 1] - qbeg;
+  const int nrows = q_b * G;
   const int q0 = qb * kPfRows;
-  if (q0 >= q_b) return;                                  // (uniform over the workgroup: before any barrier)
+  if (q0 >= nrows) return;                                // (uniform over the workgroup: before any barrier)
   const int pg0 = p.kv_indptr[b];
   const int len = (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
   const int prefix = len - q_b;                           // position of query 0
-  const int kend = prefix + min(q0 + kPfRows, q_b);       // keys this block sees: 0 .. kend-1
+  const int kend = prefix + (min(q0 + kPfRows, nrows) + G - 1) / G;   // keys this block sees: 0 .. kend-1
   const int ntiles = kend > 0 ? (kend + kPfKeys - 1) / kPfKeys : 0;
   const int chunk = (ntiles + p.splits - 1) / p.splits;
   const int t0 = sp * chunk, t1 = min(ntiles, t0 + chunk);
@@ -113,15 +120,16 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   // ---- my query row: lane (li, g) = (row 16 w + li of the block, k-group); B operand of S^T: q[row][32 ks + 8 g .. + 7], ks = 0..3.
   // ks = 0 / 2 and 1 / 3 hold the two halves of the RoPE pairs (i, i + 64) with i = 8 g + j and 32 + 8 g + j.
   const int li = lane & 15, g = lane >> 4;
-  const int qi = q0 + 16 * w + li;                        // query index within the sequence
-  const bool row_ok = qi < q_b;
+  const int ri = q0 + 16 * w + li;                        // row of the block's (sequence, K/V head)
+  const bool row_ok = ri < nrows;
+  const int qi = ri / G, hq = h * G + (ri - qi * G);      // query index within the sequence, query head
   const int pos = prefix + qi;
-  const bool wave_live = q0 + 16 * w < q_b;               // (wave-uniform) any row of this wave exists
-  const int pmin_w = prefix + q0 + 16 * w, pmax_w = pmin_w + 15;
+  const bool wave_live = q0 + 16 * w < nrows;             // (wave-uniform) any row of this wave exists
+  const int pmin_w = prefix + (q0 + 16 * w) / G, pmax_w = prefix + (q0 + 16 * w + 15) / G;
   pf_h8 qf[4];
   {
     v4u raw[4];
-    const half_t *qp = p.q + ((int64_t)(qbeg + (row_ok ? qi : 0)) * N + h) * kHeadDim + 8 * g;
+    const half_t *qp = p.q + ((int64_t)(qbeg + (row_ok ? qi : 0)) * Nq + hq) * kHeadDim + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) raw[ks] = row_ok ? *reinterpret_cast<const v4u *>(qp + 32 * ks) : v4u{0u, 0u, 0u, 0u};
     const pf_h8 *x = reinterpret_cast<const pf_h8 *>(raw);
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   float l_all = l_run + __shfl_xor(l_run, 16);
   l_all += __shfl_xor(l_all, 32);
   if (!row_ok) return;
-  const int64_t orow = (int64_t)(qbeg + qi) * N + h;
+  const int64_t orow = (int64_t)(qbeg + qi) * Nq + hq;
   if (p.splits == 1) {
     const float rl = l_all > 0.f ? 1.0f / l_all : 0.f;
 #pragma unroll
@@ -315,6 +323,44 @@ static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages)
   s = std::min<int64_t>(s, tiles / 4);
   s = std::min<int64_t>(s, 32);
   return (int)std::max<int64_t>(s, 1);
+}
+
+// ---- grouped-query attention (GQA): query head hq reads K/V head hq / G; the batch_prefill_kernel<true> geometry (see there)
+
+static int gqa_group(int num_qo_heads, int num_kv_heads) {   // G, or 0 for a rejected pair of head counts
+  if (num_kv_heads < 1 || num_qo_heads < 1 || num_qo_heads % num_kv_heads != 0) return 0;
+  return num_qo_heads / num_kv_heads;
+}
+
+// Decode: a unit is (sequence, K/V head) -- one workgroup streams the unit's KV range (or one split of it) once for the whole group.
+// Splits: the decode op's cost model (kv_i4.hip decode_splits_total) with units in place of (sequence, head) pairs, 64-key tiles, at
+// least 2 tiles per split and 512 resident workgroups (2 per CU: 140 VGPRs + 32 AGPRs, 2 waves per SIMD).
+static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages) {
+  if (max_pages <= 0) return 1;
+  const int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys, units = (int64_t)batch * num_kv_heads;
+  const int64_t smax = std::max<int64_t>(std::min<int64_t>(tiles / 2, 32), 1);
+  int best = 1;
+  double best_cost = 1e30;
+  for (int64_t s = 1; s <= smax; ++s) {
+    const int64_t rounds = (units * s + 511) / 512;
+    const double cost = (double)rounds * ((double)tiles / (double)s + 2.0) + 0.15 * (double)s;
+    if (cost < best_cost - 1e-9) { best_cost = cost; best = (int)s; }
+  }
+  return best;
+}
+
+// Prefill: the rows of a (sequence, K/V head) are max_q_len * G
+static int gqa_prefill_rows(int64_t total_q, int max_q_len, int G) {
+  return (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
+}
+
+static void launch_merge(const float *ws, half_t *o, int64_t rows, int splits, hipStream_t s) {
+  if (splits <= 8)
+    hipLaunchKernelGGL(decode_merge_kernel<8>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
+  else if (splits <= 16)
+    hipLaunchKernelGGL(decode_merge_kernel<16>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
+  else
+    hipLaunchKernelGGL(decode_merge_kernel<32>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
 }
 
 }  // namespace atom
@@ -351,7 +397,7 @@ int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int6
                   (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_heads, page_size, nqb, splits,
                   kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(batch_prefill_kernel, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  hipLaunchKernelGGL(batch_prefill_kernel<false>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
   if (splits > 1) {
     const unsigned rows = (unsigned)(total_q * num_heads);
     if (splits <= 8)
@@ -361,6 +407,98 @@ int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int6
     else
       hipLaunchKernelGGL(decode_merge_kernel<32>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
   }
+  return check_launch();
+}
+
+size_t atom_batch_prefill_gqa_i4_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                 int max_q_len, int max_pages_per_seq) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return 0;
+  if (G == 1) return atom_batch_prefill_i4_workspace_bytes(total_q, batch, num_qo_heads, page_size, max_q_len, max_pages_per_seq);
+  if (total_q < 1 || batch < 1 || page_size < 16 || max_q_len < 1) return 0;
+  const int s = prefill_splits(batch, num_kv_heads, gqa_prefill_rows(total_q, max_q_len, G), page_size, max_pages_per_seq);
+  return s > 1 ? (size_t)total_q * num_qo_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+}
+
+int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                              const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                              int batch, int num_layers, int layer_idx, int num_qo_heads, int num_kv_heads, int page_size, int head_dim,
+                              float rope_theta, float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes,
+                              void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  if (G == 1)
+    return atom_batch_prefill_i4(o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                                 num_layers, layer_idx, num_qo_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq,
+                                 workspace, workspace_bytes, stream);
+  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
+                          page_size, head_dim);
+  if (st != ATOM_OK) return st;
+  if (!o || !q || !qo_indptr || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
+  if (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1) return ATOM_ERR_SHAPE;
+  if (!aligned16(o) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
+  const int rows = gqa_prefill_rows(total_q, max_q_len, G);
+  const int nqb = (int)(((int64_t)rows + kPfRows - 1) / kPfRows);
+  int splits = prefill_splits(batch, num_kv_heads, rows, page_size, max_pages_per_seq);
+  const size_t need = (size_t)total_q * num_qo_heads * splits * (kHeadDim + 2) * sizeof(float);
+  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
+  const int64_t grid = (int64_t)nqb * batch * num_kv_heads * splits;
+  if (grid > 0x7fffffff || (int64_t)total_q * num_qo_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
+  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, qo_indptr,
+                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_kv_heads, page_size, nqb, splits,
+                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, G, num_qo_heads};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  if (splits > 1) launch_merge((const float *)workspace, (half_t *)o, total_q * num_qo_heads, splits, s);
+  return check_launch();
+}
+
+size_t atom_batch_decode_gqa_i4_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return 0;
+  if (G == 1) return atom_batch_decode_i4_workspace_bytes(batch, num_qo_heads, page_size, max_pages_per_seq);
+  if (batch < 1 || page_size < 16) return 0;
+  const int s = gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
+  return s > 1 ? (size_t)batch * num_qo_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+}
+
+int atom_batch_decode_gqa_i4_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return 0;
+  if (G == 1) return atom_batch_decode_i4_splits(batch, num_qo_heads, page_size, max_pages_per_seq);
+  if (batch < 1 || page_size < 16) return 0;
+  return gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
+}
+
+int atom_batch_decode_gqa_i4(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                             const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                             int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                             int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  if (G == 1)
+    return atom_batch_decode_i4(o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
+                                num_qo_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace, workspace_bytes,
+                                stream);
+  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
+                          page_size, head_dim);
+  if (st != ATOM_OK) return st;
+  if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
+  if ((o && !aligned16(o)) || !aligned16(q)) return ATOM_ERR_ALIGN;
+  int splits = gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
+  const size_t need = (size_t)batch * num_qo_heads * splits * (kHeadDim + 2) * sizeof(float);
+  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
+  // o == NULL: the partial states stay in the workspace un-merged, as atom_batch_decode_i4 leaves them
+  if (!o && splits < 2) return ATOM_ERR_INVALID_ARG;
+  const int nqb = (G + kPfRows - 1) / kPfRows;
+  const int64_t grid = (int64_t)nqb * batch * num_kv_heads * splits;
+  if (grid > 0x7fffffff || (int64_t)batch * num_qo_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
+  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, nullptr,
+                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_kv_heads, page_size, nqb, splits,
+                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, G, num_qo_heads};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  if (splits > 1 && o) launch_merge((const float *)workspace, (half_t *)o, (int64_t)batch * num_qo_heads, splits, s);
   return check_launch();
 }
 

@@ -45,7 +45,8 @@ class DecodeFusion:
                  cold; 15 measures 69-71)
       prefill_attn  prefill requests from an EMPTY cache attend through the HIP prefill op (ops.batch_prefill_i4, one launch for all of
                  them) instead of the torch route (FP32 de-quantisation + SDPA per request).  Requests with a cached prefix (chunked
-                 prefill, a continued prompt) always take the HIP op: the torch route cannot see the prefix.  Default off: prompts from
+                 prefill, a continued prompt) always take the HIP op: the torch route cannot see the prefix (grouped-query models: the GQA op, and
+                 the torch route repeats each K/V head over its group).  Default off: prompts from
                  an empty cache keep the torch route's numbers until the op's are reviewed against them."""
     decode: bool = True
     kv_append: bool = True
@@ -240,8 +241,9 @@ def rope_llama(x: torch.Tensor, pos: torch.Tensor, theta: float = 1e4) -> torch.
 def _append_and_decode(fusion, q, k32, v32, decode_kv, layer_idx, rope_theta, merge=True):
     """reference llama.py:168-196 for a pure decode step: this token's k / v into the INT4 paged cache, then attention over it -- one
     launch (DecodeFusion.kv_in_decode) or two; the same cache bytes and the same output either way.  ``merge=False``: the KV-split
-    partial states instead of the output (ops.batch_decode_i4)."""
-    if fusion.kv_in_decode:
+    partial states instead of the output (ops.batch_decode_i4).  Grouped-query attention (q with more heads than the cache) always
+    takes two launches: the GQA decode op has no append built in."""
+    if fusion.kv_in_decode and q.size(1) == ops._kv_dims(decode_kv)[1]:
         return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, append_kv=(k32, v32), merge=merge)
     ops.quant_append_kv_i4(decode_kv, k32, v32, layer_idx)
     return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, merge=merge)
@@ -253,7 +255,9 @@ class LlamaAttention(nn.Module):
     Prefill requests: the reference attends to RANDOM keys and values there (llama.py:164-167, "HACK": a latency
     harness); this class attends to the de-quantised projections it has just written to the cache (causal, RoPE at
     positions 0..len-1) -- the values a later decode step reads back.  A prefill request whose cache already holds tokens (chunked
-    prefill: its length exceeds the request's) attends to them too, through ops.batch_prefill_i4 (DecodeFusion.prefill_attn)."""
+    prefill: its length exceeds the request's) attends to them too, through ops.batch_prefill_i4 (DecodeFusion.prefill_attn).
+    Grouped-query attention: ``config.num_key_value_heads`` (default num_attention_heads) K/V heads, query head h reads K/V head
+    h // G; k_proj / v_proj are num_key_value_heads * 128 wide, the paged caches hold num_key_value_heads heads."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -268,9 +272,14 @@ class LlamaAttention(nn.Module):
             raise ValueError(f"hidden_size {self.hidden_size} is not divisible by num_heads {self.num_heads}")
         if self.head_dim != 128:
             raise ValueError("the INT4 KV kernels are built for head_dim 128 (as the reference's, punica_ops.cc:112)")
+        nkv = getattr(config, "num_key_value_heads", None)
+        self.num_kv_heads = self.num_heads if nkv is None else int(nkv)
+        if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads:
+            raise ValueError(f"num_key_value_heads {self.num_kv_heads} does not divide num_attention_heads {self.num_heads}")
+        self.kv_dim = self.num_kv_heads * self.head_dim
         self.q_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="fp16", bias=False, fusion=fusion)
-        self.k_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="int4", bias=False, fusion=fusion)
-        self.v_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="int4", bias=False, fusion=fusion)
+        self.k_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype="int4", bias=False, fusion=fusion)
+        self.v_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype="int4", bias=False, fusion=fusion)
         self.o_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="fp16", bias=False, fusion=fusion)
         self.reorder_index = nn.Parameter(torch.randperm(self.hidden_size).to(torch.int16), requires_grad=False)
         self.rope_theta = float(getattr(config, "rope_theta", 1e4))
@@ -282,9 +291,28 @@ class LlamaAttention(nn.Module):
             self._qkv = ops.fuse_projection_weights(mods)
         return self._qkv
 
+    @property
+    def gqa(self) -> bool:
+        return self.num_kv_heads != self.num_heads
+
+    def _decode_kv_pair(self):
+        """k_proj + v_proj as one operand of dense_layer_gemm_i4_multi (grouped-query decode steps: q_proj is narrower or wider, so it
+        runs as a launch of its own)."""
+        mods = [self.k_proj, self.v_proj]
+        if getattr(self, "_kvp", None) is None or self._kvp["key"] != ops.fused_key(mods):
+            self._kvp = ops.fuse_projection_weights(mods)
+        return self._kvp
+
+    def _check_cache(self, kv):
+        if kv is not None and ops._kv_dims(kv)[1] != self.num_kv_heads:
+            raise ValueError(f"a paged KV cache of {ops._kv_dims(kv)[1]} heads for a layer of {self.num_kv_heads} K/V heads "
+                             f"(num_key_value_heads; {self.num_heads} query heads)")
+
     def forward(self, hidden_states, blen: BatchLenInfo, prefill_kv: BatchedKvCacheInt4 | None,
                 decode_kv: BatchedKvCacheInt4 | None) -> torch.Tensor:
-        nh, hd = self.num_heads, self.head_dim
+        nh, hd, nkv = self.num_heads, self.head_dim, self.num_kv_heads
+        self._check_cache(prefill_kv)
+        self._check_cache(decode_kv)
         prefixes = []
         if len(blen.prefills) > 0:
             # cached tokens in front of each prefill request's chunk (host-side lengths: no synchronisation)
@@ -294,9 +322,12 @@ class LlamaAttention(nn.Module):
                 raise ValueError(f"prefill requests of {list(blen.prefills)} tokens do not fit caches of {list(prefill_kv.seqlens)} tokens")
         rows = hidden_states[0].size(0)
         pure_decode = (len(blen.prefills) == 0 and blen.decode == rows and self.fusion.kv_append
-                       and ops.decode_gemm_fits(rows, self.hidden_size, self.hidden_size))
-        fuse_qkv = (pure_decode and self.fusion.decode and hidden_states[1].dim() == 2
+                       and ops.decode_gemm_fits(rows, self.hidden_size, self.hidden_size)
+                       and (not self.gqa or ops.decode_gemm_fits(rows, self.kv_dim, self.hidden_size)))
+        fuse_qkv = (pure_decode and self.fusion.decode and hidden_states[1].dim() == 2 and not self.gqa
                     and ops.multi_gemm_fits(rows, self.hidden_size, 3, self.hidden_size))
+        fuse_kv = (pure_decode and self.fusion.decode and hidden_states[1].dim() == 2 and self.gqa
+                   and ops.multi_gemm_fits(rows, self.kv_dim, 2, self.hidden_size))
         q_proj = None if fuse_qkv else self.q_proj(hidden_states)
         if pure_decode:
             # pure decode step: k / v sums in FP32, then ONE launch quantises both per head and writes the cache slots
@@ -306,6 +337,9 @@ class LlamaAttention(nn.Module):
                 outlier, norms, outlier_scales, norm_scales = hidden_states
                 q_proj, k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, self._decode_qkv(),
                                                                  f32_mask=0b110)
+            elif fuse_kv:                                        # grouped-query: k / v (equal widths) in one launch, q_proj above
+                outlier, norms, outlier_scales, norm_scales = hidden_states
+                k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, self._decode_kv_pair(), f32_mask=0b11)
             else:
                 k32, v32 = self.k_proj.forward_f32(hidden_states), self.v_proj.forward_f32(hidden_states)
             o = _append_and_decode(self.fusion, q_proj.view(rows, nh, hd), k32, v32, decode_kv, self.layer_idx, self.rope_theta)
@@ -315,10 +349,10 @@ class LlamaAttention(nn.Module):
         outs = []
         if len(blen.prefills) > 0:
             assert prefill_kv is not None
-            k = k_u4[:blen.doff].view(-1, nh, hd // 2)
-            v = v_u4[:blen.doff].view(-1, nh, hd // 2)
-            ks = k_sz[:blen.doff].view(-1, nh, 2)
-            vs = v_sz[:blen.doff].view(-1, nh, 2)
+            k = k_u4[:blen.doff].view(-1, nkv, hd // 2)
+            v = v_u4[:blen.doff].view(-1, nkv, hd // 2)
+            ks = k_sz[:blen.doff].view(-1, nkv, 2)
+            vs = v_sz[:blen.doff].view(-1, nkv, 2)
             ops.init_kv_i4(prefill_kv, k, v, ks, vs, blen.indptr, self.layer_idx)
             if self.fusion.prefill_attn or max(prefixes) > 0:
                 # every prefill request in ONE launch, over its cached prefix and its new tokens (csrc/prefill_i4.hip)
@@ -328,6 +362,8 @@ class LlamaAttention(nn.Module):
                 outs.append(o.view(blen.doff, self.hidden_size))
             else:
                 kf, vf = dequant_kv_u4(k, ks), dequant_kv_u4(v, vs)
+                if self.gqa:                                     # query head h reads K/V head h // G (HF's repeat_kv)
+                    kf, vf = kf.repeat_interleave(nh // nkv, dim=1), vf.repeat_interleave(nh // nkv, dim=1)
                 beg = 0
                 for q_len in blen.prefills:
                     sl = slice(beg, beg + q_len)
@@ -340,9 +376,9 @@ class LlamaAttention(nn.Module):
         if blen.decode > 0:
             assert decode_kv is not None
             q = q_proj[blen.doff:].view(blen.decode, nh, hd)
-            ops.append_kv_i4(decode_kv, k_u4[blen.doff:].view(blen.decode, nh, hd // 2),
-                             v_u4[blen.doff:].view(blen.decode, nh, hd // 2), k_sz[blen.doff:].view(blen.decode, nh, 2),
-                             v_sz[blen.doff:].view(blen.decode, nh, 2), self.layer_idx)
+            ops.append_kv_i4(decode_kv, k_u4[blen.doff:].view(blen.decode, nkv, hd // 2),
+                             v_u4[blen.doff:].view(blen.decode, nkv, hd // 2), k_sz[blen.doff:].view(blen.decode, nkv, 2),
+                             v_sz[blen.doff:].view(blen.decode, nkv, 2), self.layer_idx)
             o = ops.batch_decode_i4(q.contiguous(), decode_kv, self.layer_idx, rope_theta=self.rope_theta)
             outs.append(o.view(blen.decode, self.hidden_size))
         attn = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
@@ -368,13 +404,24 @@ class LlamaDecoderLayer(nn.Module):
         at, mlp = self.self_attn, self.mlp
         rows, hs = hidden_states.shape
         il, pl = self.input_layernorm, self.post_attention_layernorm
-        if mask & 1:
+        if at.gqa:
+            # grouped-query: q and the (equal-width) k / v pair as two launches, each bit-identical to quantiser + GEMM
+            if mask & 1:
+                (q,), _ = ops.dense_layer_gemm_i4_multi_q("rmsnorm", hidden_states, at.q_proj.single(), x2=il.weight,
+                                                          reorder_index=il.reorder_index, eps=il.variance_epsilon)
+                (k32, v32), _ = ops.dense_layer_gemm_i4_multi_q("rmsnorm", hidden_states, at._decode_kv_pair(), x2=il.weight,
+                                                                reorder_index=il.reorder_index, eps=il.variance_epsilon, f32_mask=0b11)
+            else:
+                outlier, norms, outlier_scales, norm_scales = il(hidden_states)
+                (q,) = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, at.q_proj.single())
+                k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, at._decode_kv_pair(), f32_mask=0b11)
+        elif mask & 1:
             (q, k32, v32), _ = ops.dense_layer_gemm_i4_multi_q("rmsnorm", hidden_states, at._decode_qkv(), x2=il.weight, reorder_index=il.reorder_index,
                                                                eps=il.variance_epsilon, f32_mask=0b110)
         else:
             outlier, norms, outlier_scales, norm_scales = il(hidden_states)
             q, k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, at._decode_qkv(), f32_mask=0b110)
-        splits = ops.decode_splits(rows, decode_kv) if (mask & 2) and self.fusion.merge_in_o_proj else 1
+        splits = ops.decode_splits(rows, decode_kv, at.num_heads) if (mask & 2) and self.fusion.merge_in_o_proj else 1
         if splits >= 2 and ops.merge_q_gemm_fits(rows, hs, 1, hs, splits):
             # the KV-split merge in front of o_proj's quantiser, inside o_proj's launch (round 6): same bits, a launch fewer
             part = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta, merge=False)
@@ -400,24 +447,31 @@ class LlamaDecoderLayer(nn.Module):
         return self.fusion.q_mask if rows <= 1 else self.fusion.q_mask2
 
     def _fused_q_fits(self, rows):
-        """every projection of the layer is a shape atom_gemm_w4a4_multi_q takes at this batch size (asked once per batch size)"""
+        """every projection of the layer is a shape atom_gemm_w4a4_multi_q takes at this batch size (asked once per batch size and mask)"""
         ok = getattr(self, "_fq_ok", None)
         if ok is None:
             ok = self._fq_ok = {}
-        if rows not in ok:
-            hs, inter = self.hidden_size, self.mlp.intermediate_size
+        mask = self._q_mask_for(rows)
+        key = (rows, mask)
+        if key not in ok:
+            at, hs, inter = self.self_attn, self.hidden_size, self.mlp.intermediate_size
             # only the ops the mask selects have to fit (each with ITS quantiser's bounds); the others run as separate launches
-            need = (("rmsnorm", hs, 3, hs), ("reorder", hs, 1, hs), ("add_rmsnorm", inter, 2, hs), ("silu_mul", hs, 1, inter))
-            ok[rows] = all(ops.multi_q_gemm_fits(q, rows, n, nseg, k) for bit, (q, n, nseg, k) in enumerate(need) if (self._q_mask_for(rows) >> bit) & 1)
+            # (grouped-query attention: bit 1 is two launches, q_proj alone and the k / v pair)
+            qkv = (("rmsnorm", hs, 1, hs), ("rmsnorm", at.kv_dim, 2, hs)) if at.gqa else (("rmsnorm", hs, 3, hs),)
+            need = (qkv, (("reorder", hs, 1, hs),), (("add_rmsnorm", inter, 2, hs),), (("silu_mul", hs, 1, inter),))
+            ok[key] = all(ops.multi_q_gemm_fits(q, rows, n, nseg, k) for bit, ops_bit in enumerate(need) if (mask >> bit) & 1
+                          for (q, n, nseg, k) in ops_bit)
             # the launches that take the un-fused operands in _decode_fused_q
-            ok[rows] = ok[rows] and ops.multi_gemm_fits(rows, hs, 3, hs) and ops.multi_gemm_fits(rows, inter, 2, hs) and ops.multi_gemm_fits(rows, hs, 1, inter)
-        return ok[rows]
+            qkv_fit = (ops.multi_gemm_fits(rows, hs, 1, hs) and ops.multi_gemm_fits(rows, at.kv_dim, 2, hs)) if at.gqa else ops.multi_gemm_fits(rows, hs, 3, hs)
+            ok[key] = ok[key] and qkv_fit and ops.multi_gemm_fits(rows, inter, 2, hs) and ops.multi_gemm_fits(rows, hs, 1, inter)
+        return ok[key]
 
     def forward(self, hidden_states, blen: BatchLenInfo, prefill_kv, decode_kv) -> torch.Tensor:
         rows = hidden_states.size(0) if torch.is_tensor(hidden_states) else 0
         fu = self.fusion
         if (fu.q_decode and self._q_mask_for(rows) and fu.decode and fu.kv_append and 0 < rows <= 2 and hidden_states.dim() == 2 and hidden_states.is_contiguous()
                 and len(blen.prefills) == 0 and blen.decode == rows and decode_kv is not None and self._fused_q_fits(rows)):
+            self.self_attn._check_cache(decode_kv)
             return self._decode_fused_q(hidden_states, decode_kv, self._q_mask_for(rows))
         attn = self.self_attn(self.input_layernorm(hidden_states), blen, prefill_kv, decode_kv)
         residual, normed = self.post_attention_layernorm.forward_add(attn, hidden_states)   # fused residual add

@@ -611,11 +611,22 @@ def quant_append_kv_i4(kv, k_f32: torch.Tensor, v_f32: torch.Tensor, layer_idx: 
     L.check(st, "atom_kv_quant_append_f32")
 
 
-def decode_splits(batch: int, kv) -> int:
+def _qo_heads(num_qo_heads: int, num_kv_heads: int) -> int:
+    """grouped-query attention: query head h reads the cache's K/V head h // G -- the query head count must be a multiple of the cache's"""
+    if num_qo_heads < 1 or num_qo_heads % num_kv_heads:
+        raise ValueError(f"{num_qo_heads} query heads on a cache of {num_kv_heads} K/V heads: not a multiple (grouped-query attention)")
+    return num_qo_heads
+
+
+def decode_splits(batch: int, kv, num_qo_heads: int = None) -> int:
     """How many partial states per (sequence, head) batch_decode_i4 produces for this cache (1: none; small batches: one per workgroup of
-    four KV-split waves)."""
+    four KV-split waves).  ``num_qo_heads``: the query heads of a grouped-query call (default: the cache's head count)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
-    return int(L.lib().atom_batch_decode_i4_splits(int(batch), num_heads, page_size, int(getattr(kv, "max_pages", 0))))
+    max_pages = int(getattr(kv, "max_pages", 0))
+    if num_qo_heads is None or num_qo_heads == num_heads:
+        return int(L.lib().atom_batch_decode_i4_splits(int(batch), num_heads, page_size, max_pages))
+    nq = _qo_heads(int(num_qo_heads), num_heads)
+    return int(L.lib().atom_batch_decode_gqa_i4_splits(int(batch), nq, num_heads, page_size, max_pages))
 
 
 def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True):
@@ -624,10 +635,15 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     ``append_kv=(k_f32, v_f32)`` (round 6): quant_append_kv_i4 of this step's FP32 k / v projections inside the same launch
     (atom_batch_decode_append_i4) -- same cache contents, same output, one launch fewer.
     ``merge=False`` (only where decode_splits(batch, kv) >= 2): no merge launch -- returns the split partial states float32
-    [batch, heads, splits, 130] (a tensor of their own, not the shared workspace) for dense_layer_gemm_i4_merge_q."""
+    [batch, heads, splits, 130] (a tensor of their own, not the shared workspace) for dense_layer_gemm_i4_merge_q.
+    Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G); then the GQA op
+    (atom_batch_decode_gqa_i4: each K/V tile read once per group, the prefill op's fp16 matrix-core numerics) runs, ``merge=False``
+    returns [batch, q heads, decode_splits(batch, kv, q heads), 130], and ``append_kv`` is refused (append with quant_append_kv_i4)."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
+    if q.dim() == 3 and q.size(1) != num_heads:
+        return _batch_decode_gqa_i4(q, kv, layer_idx, rope_theta, rope_scale, append_kv, merge)
     assert q.shape == (batch, num_heads, head_dim)
     lib = L.lib()
     max_pages = int(getattr(kv, "max_pages", 0))
@@ -662,6 +678,35 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     return o if merge else part
 
 
+def _batch_decode_gqa_i4(q, kv, layer_idx, rope_theta, rope_scale, append_kv, merge):
+    num_layers, num_kv_heads, page_size, head_dim = _kv_dims(kv)
+    batch, nq = q.size(0), _qo_heads(q.size(1), num_kv_heads)
+    assert q.shape == (batch, nq, head_dim) and q.is_contiguous()
+    if append_kv is not None:
+        raise ValueError("append_kv= is not built for grouped-query attention: append with quant_append_kv_i4 first")
+    for t in (kv.data, kv.param):
+        if not t.is_cuda:
+            raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
+    assert batch == kv.last_page_offset.numel()
+    lib = L.lib()
+    max_pages = int(getattr(kv, "max_pages", 0))
+    ws_bytes = lib.atom_batch_decode_gqa_i4_workspace_bytes(batch, nq, num_kv_heads, page_size, max_pages)
+    if not merge:
+        splits = lib.atom_batch_decode_gqa_i4_splits(batch, nq, num_kv_heads, page_size, max_pages)
+        assert splits >= 2 and ws_bytes == batch * nq * splits * 130 * 4, "merge=False needs a split KV range (decode_splits)"
+        part = torch.empty((batch, nq, splits, 130), dtype=torch.float32, device=q.device)
+        o, ws = None, part
+    else:
+        o = torch.empty_like(q)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+    st = lib.atom_batch_decode_gqa_i4(L.ptr(o), q.data_ptr(), kv.data.data_ptr(), kv.param.data_ptr(), kv.indptr.data_ptr(),
+                                      kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(), batch, num_layers, int(layer_idx), nq,
+                                      num_kv_heads, page_size, head_dim, float(rope_theta), float(rope_scale), max_pages, L.ptr(ws),
+                                      ws_bytes, L.current_stream(q.device))
+    L.check(st, "atom_batch_decode_gqa_i4")
+    return o if merge else part
+
+
 
 def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
                      max_q_len: int = None):
@@ -669,20 +714,33 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     [T, heads, 128] (not yet rotated); qo_indptr int32 [batch + 1] on the device: sequence b's queries are rows
     qo_indptr[b] .. qo_indptr[b+1] and its LAST positions in the cache (already written there, init_kv_i4).  ``max_q_len``: host-side
     bound of every sequence's query count (default T; it sizes the grid).  No host synchronisation: capturable in a graph.  With one
-    query per sequence the output is batch_decode_i4's (fp16 matrix-core operands: within rounding of it)."""
+    query per sequence the output is batch_decode_i4's (fp16 matrix-core operands: within rounding of it).
+    Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G,
+    atom_batch_prefill_gqa_i4: each staged K/V tile serves the whole group)."""
     _require_cuda_half(q, "q")
     for t in (qo_indptr, kv.data, kv.param):
         if not t.is_cuda:
             raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     total = q.size(0)
-    assert q.shape == (total, num_heads, head_dim) and q.is_contiguous()
+    nq = _qo_heads(q.size(1), num_heads) if q.dim() == 3 else num_heads
+    assert q.shape == (total, nq, head_dim) and q.is_contiguous()
     assert qo_indptr.dtype == torch.int32 and qo_indptr.is_contiguous()
     batch = kv.last_page_offset.numel()
     assert qo_indptr.numel() == batch + 1
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
     max_pages = int(getattr(kv, "max_pages", 0))
+    if nq != num_heads:
+        ws_bytes = lib.atom_batch_prefill_gqa_i4_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        st = lib.atom_batch_prefill_gqa_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, kv.data.data_ptr(),
+                                           kv.param.data_ptr(), kv.indptr.data_ptr(), kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(),
+                                           batch, num_layers, int(layer_idx), nq, num_heads, page_size, head_dim, float(rope_theta),
+                                           float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_prefill_gqa_i4")
+        return o
     ws_bytes = lib.atom_batch_prefill_i4_workspace_bytes(total, batch, num_heads, page_size, max_q, max_pages)
     ws = _workspace(q.device, ws_bytes) if ws_bytes else None
     o = torch.empty_like(q)

@@ -6,6 +6,7 @@ code written against the reference's objects runs on these.  Host-side only; the
 Pool layout (reference kvcache.py:17-26, page.cuh:78-110):
     buf    uint8 [capacity, num_layers, 2, num_heads, block_len, head_dim // 2]   packed u4, K at [.., 0, ..], V at [.., 1, ..]
     param  fp16  [capacity, num_layers, 2, num_heads, block_len, 2]              (scale, zero) per token and head
+num_heads is the model's K/V head count: num_key_value_heads for a grouped-query model (its query heads share them, ops.batch_decode_i4).
 """
 from __future__ import annotations
 

@@ -460,6 +460,33 @@ int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int6
                           int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Grouped-query attention (GQA) over the same cache: the cache holds num_kv_heads heads, q / o are fp16 [rows, num_qo_heads, 128],
+ * and query head h reads K/V head h / G, G = num_qo_heads / num_kv_heads (HF's repeat_kv).  Decode and prefill compute what the two
+ * entry points above compute on the cache with every K/V head repeated G times, without that copy: a workgroup serves a (sequence,
+ * K/V head) pair -- or a query block of it -- for all G query heads of the group, so each K/V tile is read from memory and
+ * de-quantised once per group (csrc/prefill_i4.hip, batch_prefill_kernel<true>).
+ * Numerics of BOTH entry points are the prefill op's: q, the rotated keys, the softmax weights and the de-quantised values are rounded
+ * to fp16 as matrix-core operands, FP32 accumulation and softmax (the GQA decode op is the prefill kernel with one query per sequence).
+ * num_qo_heads == num_kv_heads: the calls forward to atom_batch_decode_i4 / atom_batch_prefill_i4 (their bits, workspace sizes and
+ * split counts).  The decode op's partial states (o == NULL, splits >= 2) keep the layout float [batch][num_qo_heads][splits][130], for
+ * atom_gemm_w4a4_multi_merge_q; its split count is sized by batch x num_kv_heads.
+ * Errors: those of the MHA entry points, and ATOM_ERR_SHAPE for num_kv_heads < 1, num_qo_heads < 1 or num_qo_heads % num_kv_heads != 0
+ * (checked before any pointer; the size queries return 0 there).  The cache's K/V are appended by atom_kv_append_i4 /
+ * atom_kv_quant_append_f32 with num_heads = num_kv_heads. */
+size_t atom_batch_decode_gqa_i4_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq);
+int atom_batch_decode_gqa_i4_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq);
+int atom_batch_decode_gqa_i4(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                             const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                             int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                             int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
+size_t atom_batch_prefill_gqa_i4_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                 int max_q_len, int max_pages_per_seq);
+int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                              const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                              int batch, int num_layers, int layer_idx, int num_qo_heads, int num_kv_heads, int page_size, int head_dim,
+                              float rope_theta, float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised
  * asymmetrically to n_bits in FP16 opmath -- scale = ((max - min) * clip).clamp(1e-5) / (2^n - 1), base =

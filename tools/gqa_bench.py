@@ -1,0 +1,125 @@
+"""Bench of grouped-query attention (GQA) over the INT4 paged KV cache (atom_batch_decode_gqa_i4 / atom_batch_prefill_gqa_i4,
+csrc/prefill_i4.hip), 32 query heads on 8 K/V heads, pages of 16 tokens, warm caches:
+    python tools/gqa_bench.py [--iters K] [--warmup W] [--only decode|prefill|layer|NAME]   (on the GPU box)
+
+Per shape, on the same box in one run:
+  gqa        the GQA op: 32 query heads on the 8-head cache
+  mha_kv     the MHA op on a cache of 8 heads (8 query heads: the same KV bytes)
+  mha_rep    the MHA op on the cache replicated to 32 heads (the only way to run a GQA model before the GQA ops)
+and a Llama-3-8B-shaped decode layer (hidden 4096, 32 / 8 heads, intermediate 14336) at context 1024: one decode step per batch size.
+Prints one line per shape and a JSON line with everything."""
+import argparse
+import json
+import os
+import sys
+import types
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from atom_amd import ops  # noqa: E402
+from atom_amd.utils import BatchLenInfo  # noqa: E402
+from atom_amd.utils.kvcache import BatchedKvCacheInt4, KvCacheInt4, KvPoolInt4  # noqa: E402
+
+NQ, NKV, BLOCK = 32, 8, 16
+G = NQ // NKV
+DECODE = {f"decode_b{b}_c{c}": (b, c) for c in (1024, 4096) for b in (1, 16, 64)}
+PREFILL = {"1x2048": [(0, 2048)], "8x512": [(0, 512)] * 8, "8_on_4000": [(4000, 8)]}
+LAYER = {f"layer_b{b}_c1024": b for b in (1, 16, 64)}
+
+
+def _time(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def _caches(seqlens, heads=NKV, layers=1):
+    """a random cache of `heads` heads, and the same contents replicated to NQ heads"""
+    dev = torch.device("cuda")
+    pool = KvPoolInt4(layers, heads, 128, sum(-(-s // BLOCK) for s in seqlens) + 1, BLOCK, dev)
+    pool.buf.copy_(torch.randint(0, 256, pool.buf.shape, device=dev, dtype=torch.uint8))
+    pool.param.copy_((torch.rand(pool.param.shape, device=dev) * 0.2 + 0.01).half())
+    kv = BatchedKvCacheInt4([KvCacheInt4(pool, s) for s in seqlens])
+    rep = types.SimpleNamespace(data=kv.data.repeat_interleave(G, dim=3).contiguous(), param=kv.param.repeat_interleave(G, dim=3).contiguous(),
+                                indptr=kv.indptr, indicies=kv.indicies, last_page_offset=kv.last_page_offset, max_pages=kv.max_pages)
+    return pool, kv, rep
+
+
+def decode(name, batch, ctx, iters, warmup):
+    pool, kv, rep = _caches([ctx] * batch)
+    q = torch.randn((batch, NQ, 128), device="cuda").half()
+    q8 = q[:, :NKV].contiguous()
+    r = {"shape": name, "batch": batch, "ctx": ctx, "kv_bytes": batch * ctx * NKV * 136,       # K + V codes and (scale, zero) halves
+         "splits_gqa": ops.decode_splits(batch, kv, NQ), "splits_mha_rep": ops.decode_splits(batch, rep)}
+    r["gqa_us"] = _time(lambda: ops.batch_decode_i4(q, kv, 0), iters, warmup)
+    r["mha_kv_us"] = _time(lambda: ops.batch_decode_i4(q8, kv, 0), iters, warmup)
+    r["mha_rep_us"] = _time(lambda: ops.batch_decode_i4(q, rep, 0), iters, warmup)
+    r["gqa_over_mha_kv"] = r["gqa_us"] / r["mha_kv_us"]
+    r["gqa_over_mha_rep"] = r["gqa_us"] / r["mha_rep_us"]
+    print(f"DECODE  {name:18s} gqa {r['gqa_us']:8.1f} us  mha(8 heads) {r['mha_kv_us']:8.1f} us ({r['gqa_over_mha_kv']:.2f}x)  "
+          f"mha(replicated 32) {r['mha_rep_us']:8.1f} us ({r['gqa_over_mha_rep']:.2f}x)  splits {r['splits_gqa']}", flush=True)
+    return r
+
+
+def prefill(name, seqs, iters, warmup):
+    seqlens = [a + n for a, n in seqs]
+    qlens = [n for _, n in seqs]
+    pool, kv, rep = _caches(seqlens)
+    T, mq = sum(qlens), max(qlens)
+    q = torch.randn((T, NQ, 128), device="cuda").half()
+    q8 = q[:, :NKV].contiguous()
+    qo = torch.tensor([0] + torch.tensor(qlens).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+    r = {"shape": name, "seqs": len(seqs), "prefix": seqs[0][0], "q_len": qlens[0]}
+    r["gqa_us"] = _time(lambda: ops.batch_prefill_i4(q, qo, kv, 0, max_q_len=mq), iters, warmup)
+    r["mha_kv_us"] = _time(lambda: ops.batch_prefill_i4(q8, qo, kv, 0, max_q_len=mq), iters, warmup)
+    r["mha_rep_us"] = _time(lambda: ops.batch_prefill_i4(q, qo, rep, 0, max_q_len=mq), iters, warmup)
+    r["gqa_over_mha_rep"] = r["gqa_us"] / r["mha_rep_us"]
+    print(f"PREFILL {name:18s} gqa {r['gqa_us']:8.1f} us  mha(8 heads) {r['mha_kv_us']:8.1f} us  mha(32 heads) {r['mha_rep_us']:8.1f} us "
+          f"({r['gqa_over_mha_rep']:.2f}x)", flush=True)
+    return r
+
+
+def layer(name, batch, iters, warmup):
+    from atom_amd.e2e import LlamaDecoderLayer
+    cfg = types.SimpleNamespace(hidden_size=4096, num_attention_heads=NQ, num_key_value_heads=NKV, intermediate_size=14336, rms_norm_eps=1e-5,
+                                rope_theta=5e5)
+    dev = torch.device("cuda")
+    lay = LlamaDecoderLayer(cfg, layer_idx=0).to(dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for mod in lay.modules():
+        if type(mod).__name__ == "LinearInt4":
+            mod.load_fp16_weight((torch.randn(mod.out_features, mod.in_features, device=dev, generator=g) * 0.02).half())
+    pool, kv, _ = _caches([1024] * batch)          # 1024 tokens per sequence, the last one the slot every timed step writes
+    x = (torch.randn(batch, 4096, device=dev) * 0.5).half()
+    blen = BatchLenInfo([], batch, dev)
+    r = {"shape": name, "batch": batch, "ctx": 1024}
+    r["layer_us"] = _time(lambda: lay(x, blen, None, kv), iters, warmup)
+    print(f"LAYER   {name:18s} Llama-3-8B-shaped decode layer {r['layer_us']:8.1f} us", flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--only", default=None)
+    a = ap.parse_args()
+
+    def want(kind, name):
+        return a.only in (None, kind, name)
+    out = {"decode": [decode(n, b, c, a.iters, a.warmup) for n, (b, c) in DECODE.items() if want("decode", n)],
+           "prefill": [prefill(n, s, a.iters, a.warmup) for n, s in PREFILL.items() if want("prefill", n)],
+           "layer": [layer(n, b, a.iters, a.warmup) for n, b in LAYER.items() if want("layer", n)]}
+    print(json.dumps({"gqa_bench": out}))
+
+
+if __name__ == "__main__":
+    main()
