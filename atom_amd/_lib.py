@@ -29,6 +29,7 @@ WS_WEIGHT_CACHED = 0x1000  # ATOM_WS_WEIGHT_CACHED: the workspace already holds 
 B_SCALE_PAIRS = 0x2000     # ATOM_B_SCALE_PAIRS: output channels 2j, 2j+1 share their weight scales (weight_channel_group = 2)
 WS_VERIFY = 0x4000         # ATOM_WS_VERIFY: debug call -- the two assertions above are checked on the device first (synchronises)
 Q_REORDER, Q_RMSNORM, Q_ADD_RMSNORM, Q_SILU_MUL = 1, 2, 3, 4     # atom_gemm_w4a4_multi_q: q_op
+KV_STEP_OVERFLOW, KV_STEP_BAD_LENGTH = 1, 2                      # ATOM_KV_STEP_*: status bits of atom_kv_step_i4
 F6_PITCH = 104
 
 _vp = ctypes.c_void_p
@@ -88,6 +89,7 @@ SIGNATURES = {
     "atom_batch_decode_gqa_i4": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_batch_prefill_gqa_i4_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 6),
     "atom_batch_prefill_gqa_i4": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_kv_step_i4": (_int, [_vp] * 7 + [_int] * 4 + [_vp]),
 }
 
 _lib = None

@@ -1,0 +1,145 @@
+// Device-side step of the INT4 paged KV cache's page tables (atom_kv_step_i4): what BatchedKvCacheInt4 builds on the host for
+// every new token -- kv_indptr / kv_indices / last_page_offset of kv_i4.hip -- rebuilt in ONE launch from data that stays at fixed
+// device addresses, so a captured decode step can be replayed for the next token.
+//
+//   page_table  i32 [batch, cap]   the pages RESERVED for each sequence, in order (read only)
+//   row_pages   i32 [batch]        how many entries of each row are reserved pages (read only; clamped into 0 .. cap)
+//   lens        i32 [2, batch]     the lengths, double-buffered: row state[1] & 1 is current, the launch writes the other row
+//   state       i32 [4]            [0] status bits (ATOM_KV_STEP_OVERFLOW / _BAD_LENGTH, only ever set here), [1] parity of `lens`,
+//                                  [2] arrival counter of the launch's workgroups (0 between launches), [3] unused
+//
+// Every sequence's new length is len + add unless that needs more than its row_pages pages: then it keeps its length and the overflow
+// bit is set.  A length outside 0 .. row_pages * page_size (a corrupted buffer) is clamped into it and flagged, so no page count above
+// a row's reserve and no index from outside a row ever reaches the tables.  The tables are rebuilt whole: kv_indptr is an exclusive prefix sum of the page
+// counts, and a sequence that gains a page moves every later sequence's entries, so there is nothing to patch in place.
+//
+// Grid (groups of 64 sequences) x (slices of the copy).  A workgroup does not wait for any other: it sums the page counts of all
+// sequences in front of its group itself (256 threads, wave64 shuffle reduction + LDS), wave 0 scans the group's own 64 counts
+// (__shfl_up, 6 steps), then the four waves copy the group's rows, lane j of slice s taking entries s * 64 + j, + slices * 64, ...
+// Why the lengths are double-buffered: every workgroup reads ALL current lengths while slice 0 of each group writes the new ones.  The
+// last workgroup to arrive (one agent-scope atomic per workgroup, after its reads) flips the parity for the next launch; nothing in
+// a launch ever reads what the same launch wrote.
+#include "common.h"
+#include "kv_attn.h"
+
+namespace atom {
+
+constexpr int kStepRows = 64;       // sequences per workgroup group: one lane each in the scan
+constexpr int kStepThreads = 256;
+
+struct KvStepParams {
+  const int32_t *table, *rows;
+  int32_t *lens, *indptr, *indices, *lpo, *state;
+  int batch, cap, P, add;
+};
+
+// new length of a sequence and its status bits; its reserve holds min(row_pages, cap) * P tokens
+__device__ __forceinline__ int step_len(int len, int add, int row_pages, int cap, int P, int &flag) {
+  const int maxlen = min(max(row_pages, 0), cap) * P;
+  flag = 0;
+  if (len < 0) { len = 0; flag = ATOM_KV_STEP_BAD_LENGTH; }
+  if (len > maxlen) { len = maxlen; flag = ATOM_KV_STEP_BAD_LENGTH; }
+  if (add > maxlen - len) { flag |= ATOM_KV_STEP_OVERFLOW; return len; }
+  return len + add;
+}
+
+__global__ __launch_bounds__(kStepThreads) void kv_step_kernel(KvStepParams p) {
+  __shared__ int s_part[kStepThreads / 64];
+  __shared__ int s_off[kStepRows], s_cnt[kStepRows];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int parity = p.state[1] & 1;
+  const int32_t *cur = p.lens + (int64_t)parity * p.batch;
+  int32_t *nxt = p.lens + (int64_t)(parity ^ 1) * p.batch;
+  const int row0 = blockIdx.x * kStepRows;
+
+  // pages of every sequence in front of this group
+  int acc = 0, flag;
+  for (int r = tid; r < row0; r += kStepThreads) acc += (step_len(cur[r], p.add, p.rows[r], p.cap, p.P, flag) + p.P - 1) / p.P;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  if (lane == 0) s_part[wave] = acc;
+
+  // the group's own sequences: one lane each, inclusive scan of the page counts over the wave
+  const int row = row0 + lane;
+  int len = 0, cnt = 0, inc = 0;
+  flag = 0;
+  if (wave == 0) {
+    if (row < p.batch) {
+      len = step_len(cur[row], p.add, p.rows[row], p.cap, p.P, flag);
+      cnt = (len + p.P - 1) / p.P;
+    }
+    inc = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += t;
+    }
+    s_off[lane] = inc - cnt;
+    s_cnt[lane] = cnt;
+  }
+  __syncthreads();
+  const int base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+
+  if (wave == 0 && blockIdx.y == 0 && row < p.batch) {
+    nxt[row] = len;
+    p.lpo[row] = len > 0 ? (len - 1) % p.P + 1 : 0;       // an empty sequence: no page, offset 0 (what the attention ops skip)
+    p.indptr[row + 1] = base + inc;
+    if (row == 0) p.indptr[0] = 0;
+    if (flag) atomicOr(&p.state[0], flag);
+  }
+
+  // compaction: the first cnt entries of each row (cnt <= cap: the reads stay inside the row, the writes below batch * cap)
+  const int rows_here = min(kStepRows, p.batch - row0);
+  const int stride = gridDim.y * 64;
+  for (int r = wave; r < rows_here; r += kStepThreads / 64) {
+    const int n = s_cnt[r];
+    const int32_t *src = p.table + (int64_t)(row0 + r) * p.cap;
+    int32_t *dst = p.indices + base + s_off[r];
+    for (int j = blockIdx.y * 64 + lane; j < n; j += stride) dst[j] = src[j];
+  }
+
+  // arrival: this workgroup has read everything it needs of the current lengths (their values went into LDS in front of the barrier
+  // above).  No data passes between workgroups inside a launch, so the counter needs no fence (an agent-scope fence costs microseconds
+  // here): it only tells the last workgroup that nobody reads the parity any more; its two stores are for the NEXT launch.
+  if (tid == 0) {
+    const int total = gridDim.x * gridDim.y;
+    if (__hip_atomic_fetch_add(&p.state[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == total - 1) {
+      __hip_atomic_store(&p.state[2], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      p.state[1] = parity ^ 1;
+    }
+  }
+}
+
+// slices of the copy (gridDim.y)
+static int step_slices(int batch, int cap) {
+  // a slice is 64 entries of every row per pass; enough slices that a workgroup makes at most 4 passes over a row, at most 16,
+  // and no more than 1024 workgroups in all
+  const int groups = (batch + kStepRows - 1) / kStepRows;
+  int s = (cap + 255) / 256;
+  s = s > 16 ? 16 : s;
+  while (s > 1 && (int64_t)s * groups > 1024) --s;
+  return s;
+}
+
+}  // namespace atom
+
+using namespace atom;
+
+extern "C" {
+
+int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                    int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, void *stream) {
+  if (!page_table || !row_pages || !lens || !kv_indptr || !kv_indices || !last_page_offset || !state) return ATOM_ERR_INVALID_ARG;
+  if (add < 0) return ATOM_ERR_INVALID_ARG;
+  if (batch < 1 || cap < 1 || page_size < 16 || (page_size % 16) != 0) return ATOM_ERR_SHAPE;
+  if ((int64_t)cap * page_size > 0x7fffffff || (int64_t)batch * cap > 0x7fffffff) return ATOM_ERR_SHAPE;
+  for (const void *q : {(const void *)page_table, (const void *)row_pages, (const void *)lens, (const void *)kv_indptr, (const void *)kv_indices,
+                        (const void *)last_page_offset, (const void *)state})
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
+  KvStepParams p{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add};
+  const dim3 grid((unsigned)((batch + kStepRows - 1) / kStepRows), (unsigned)step_slices(batch, cap));
+  hipLaunchKernelGGL(kv_step_kernel, grid, dim3(kStepThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
+  return check_launch();
+}
+
+}  // extern "C"

@@ -2,3 +2,4 @@
 (e2e/punica-atom/punica/models/llama.py): the 4-tuple (outlier, norms, outlier_scales, norm_scales) flows between ops."""
 from .llama import (LinearInt4, LlamaAttention, LlamaDecoderLayer, LlamaForCausalLM, LlamaMLP, LlamaModel,  # noqa: F401
                     LlamaRMSNorm, LlamaRMSNormInt4)
+from .generate import DecodeGraph, generate  # noqa: F401

@@ -611,6 +611,24 @@ def quant_append_kv_i4(kv, k_f32: torch.Tensor, v_f32: torch.Tensor, layer_idx: 
     L.check(st, "atom_kv_quant_append_f32")
 
 
+def kv_step_i4(kv, add: int = 1):
+    """NEW (page tables stepped on the device): every sequence of a utils.StaticBatchedKvCacheInt4 gains ``add`` tokens (0: none) and
+    its ``indptr`` / ``indicies`` / ``last_page_offset`` are rebuilt in place from its padded page table (atom_kv_step_i4) -- one
+    launch on the current stream, no host synchronisation, capturable.  A sequence that would outgrow its reserved pages keeps its
+    length and sets the cache's status word (read by ``kv.sync_host()``)."""
+    tensors = (kv.page_table, kv.row_pages, kv.lengths, kv.indptr, kv.indicies, kv.last_page_offset, kv.state)
+    for t in tensors:
+        if not t.is_cuda:
+            raise L.AtomHipError("KV-cache page tables must live on the GPU: no CPU fallback")
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    batch, cap = kv.page_table.shape
+    assert kv.row_pages.numel() == batch and kv.lengths.numel() == 2 * batch and kv.indptr.numel() == batch + 1
+    assert kv.indicies.numel() == batch * cap and kv.last_page_offset.numel() == batch and kv.state.numel() == 4
+    st = L.lib().atom_kv_step_i4(*(t.data_ptr() for t in tensors), batch, cap, kv.page_size, int(add),
+                                  L.current_stream(kv.page_table.device))
+    L.check(st, "atom_kv_step_i4")
+
+
 def _qo_heads(num_qo_heads: int, num_kv_heads: int) -> int:
     """grouped-query attention: query head h reads the cache's K/V head h // G -- the query head count must be a multiple of the cache's"""
     if num_qo_heads < 1 or num_qo_heads % num_kv_heads:

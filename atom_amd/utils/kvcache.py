@@ -2,6 +2,8 @@
 KvCacheInt4 :58-98, BatchedKvCacheInt4 :101-128): same class / property / method names and the same tensor layouts, so
 code written against the reference's objects runs on these.  Host-side only; the device work is in atom_amd.ops
 (init_kv_i4 / append_kv_i4 / batch_decode_i4 -> csrc/kv_i4.hip, batch_prefill_i4 -> csrc/prefill_i4.hip).
+``StaticBatchedKvCacheInt4`` (not in the reference) keeps the page tables at fixed device addresses and advances them on the device
+(ops.kv_step_i4 -> csrc/kv_step.hip), for decode steps replayed from a captured graph.
 
 Pool layout (reference kvcache.py:17-26, page.cuh:78-110):
     buf    uint8 [capacity, num_layers, 2, num_heads, block_len, head_dim // 2]   packed u4, K at [.., 0, ..], V at [.., 1, ..]
@@ -65,6 +67,22 @@ class KvCacheInt4:
         for _ in range(n):
             self.acquire_one()
 
+    def reserve(self, n: int):
+        """Allocate the pages that ``n`` more tokens will need, without adding a token: ``acquire_one`` then allocates nothing until
+        they are used up.  A sequence holding spare pages must be ``trim()``med before it is handed to ``BatchedKvCacheInt4``, which
+        counts every page of the list as part of the sequence."""
+        if n < 0:
+            raise ValueError("n must be non-negative")
+        while len(self._indicies) * self._pool.block_len < self._seqlen + n:
+            self._indicies.append(self._pool.alloc_block())
+
+    def trim(self):
+        """Return the spare pages (those beyond ceil(seqlen / block_len)) to the pool."""
+        keep = -(-self._seqlen // self._pool.block_len)
+        for idx in self._indicies[keep:]:
+            self._pool.free_block(idx)
+        del self._indicies[keep:]
+
     def release(self):
         for idx in self._indicies:
             self._pool.free_block(idx)
@@ -93,3 +111,72 @@ class BatchedKvCacheInt4:
     @property
     def page_size(self):
         return self.data.size(-2)
+
+
+class StaticBatchedKvCacheInt4:
+    """Page tables of a batch at FIXED device addresses, advanced on the device: takes the place of a ``BatchedKvCacheInt4`` in every
+    op and module, for a decode loop that replays one captured step.  The pages for ``reserve`` more tokens per sequence are taken
+    from the pool up front (``KvCacheInt4.reserve``); ``step()`` is one launch (ops.kv_step_i4) that adds a token to every sequence and
+    rebuilds ``indptr`` / ``indicies`` / ``last_page_offset`` in place.  The host does not follow along: ``seqlens`` and the
+    sequences' ``seqlen`` are those of construction or of the last ``sync_host()``.  ``max_pages`` is the static row width ``cap`` of
+    the page table, so the attention ops size their KV split by the reserve, not by the current lengths.
+    While this object is open the sequences hold spare pages: build no ``BatchedKvCacheInt4`` from them before ``close()``."""
+
+    def __init__(self, kv: Sequence[KvCacheInt4], reserve: int):
+        assert len(kv) > 0
+        pool = kv[0].pool
+        assert all(c.pool is pool for c in kv)
+        assert len({id(c) for c in kv}) == len(kv)
+        device = pool.buf.device
+        for c in kv:
+            c.reserve(reserve)
+        self._kv = list(kv)
+        batch, cap = len(kv), max(1, max(len(c.indicies) for c in kv))
+        self.data = pool.buf
+        self.param = pool.param
+        self.max_pages = cap
+        self.seqlens = [c.seqlen for c in kv]
+        # rows padded with the sequence's last page (the device never copies the padding: row_pages bounds every row)
+        rows = [list(c.indicies) + [c.indicies[-1] if c.indicies else 0] * (cap - len(c.indicies)) for c in kv]
+        self.page_table = torch.tensor(rows, dtype=torch.int32, device=device)
+        self.row_pages = torch.tensor([len(c.indicies) for c in kv], dtype=torch.int32, device=device)
+        # lengths [2, batch] (double-buffered, atom_kv_step_i4) and the state words in ONE buffer: sync_host() is one copy
+        self._dev = torch.tensor(self.seqlens + [0] * batch + [0, 0, 0, 0], dtype=torch.int32, device=device)
+        self.lengths = self._dev[:2 * batch]
+        self.state = self._dev[2 * batch:]
+        self.indptr = torch.zeros(batch + 1, dtype=torch.int32, device=device)
+        self.indicies = torch.zeros(batch * cap, dtype=torch.int32, device=device)
+        self.last_page_offset = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.step(0)
+
+    @property
+    def page_size(self):
+        return self.data.size(-2)
+
+    def step(self, add: int = 1):
+        """One launch on the current stream: every sequence gains ``add`` tokens (0: rebuild the tables only).  Capturable."""
+        from .. import ops
+        ops.kv_step_i4(self, add)
+
+    def sync_host(self):
+        """Read the lengths and the status word back (one copy, the only synchronisation) and bring ``seqlens`` and the sequences'
+        ``seqlen`` up to date.  Raises if a sequence ran out of reserved pages (it kept its last legal length) or a stored length was
+        out of range; the status word is cleared."""
+        batch = len(self._kv)
+        host = self._dev.tolist()
+        status, parity = host[2 * batch], host[2 * batch + 1] & 1
+        self.seqlens = host[parity * batch:(parity + 1) * batch]
+        for c, n in zip(self._kv, self.seqlens):
+            c._seqlen = n
+        if status:
+            self.state[0].zero_()
+            raise RuntimeError(f"StaticBatchedKvCacheInt4: status {status} (1: a sequence needed more than its reserved pages and was not "
+                               f"advanced, 2: a stored length was out of range); lengths now {self.seqlens}")
+
+    def close(self):
+        """``sync_host()``, then every sequence returns its spare pages: they are ordinary ``KvCacheInt4`` again."""
+        try:
+            self.sync_host()
+        finally:
+            for c in self._kv:
+                c.trim()

@@ -487,6 +487,29 @@ int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, 
                               float rope_theta, float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* Page tables stepped on the device (csrc/kv_step.hip): rebuilds kv_indptr / kv_indices / last_page_offset -- the layout above, what
+ * every attention and append entry point reads -- in ONE launch from buffers at fixed addresses, so that a captured decode step can
+ * be replayed for the next token with no host work in between.
+ *   page_table int32 [batch, cap]  the pages reserved for each sequence, in order (read only)
+ *   row_pages  int32 [batch]       how many entries of each row are reserved pages (read only; clamped into 0 .. cap); the entries
+ *                                  behind them are never copied
+ *   lens       int32 [2, batch]    the lengths, double-buffered: row (state[1] & 1) is current; the launch writes the other row and
+ *                                  flips state[1] (every workgroup reads all current lengths, so they cannot be updated in place)
+ *   state      int32 [4]           [0] status bits, only ever SET by the launch (the caller reads and clears them);
+ *                                  [1] parity of `lens`; [2] the launch's arrival counter, 0 between launches; [3] unused.  Zero it once.
+ *   kv_indptr int32 [batch+1], kv_indices int32 [batch * cap] (the first kv_indptr[batch] are meaningful), last_page_offset int32 [batch]
+ * Sequence b's new length is len_b + add (add = 1: a decode step; add = 0: rebuild the tables of the current lengths) unless that
+ * needs more than row_pages[b] pages: then it keeps its length and ATOM_KV_STEP_OVERFLOW is set.  A stored length outside
+ * 0 .. row_pages[b] * page_size is clamped into that range and ATOM_KV_STEP_BAD_LENGTH is set.  So no page count above a sequence's
+ * reserve (hence none above `cap`) and no index from outside its row ever reaches the tables: capacity is an error the caller reads later, never a fault.  An empty sequence has no page and
+ * last_page_offset 0.  Launches that share buffers must be ordered on the device (one stream, or a captured chain).
+ * Errors: ATOM_ERR_INVALID_ARG for a null pointer or add < 0; ATOM_ERR_SHAPE for batch < 1, cap < 1, page_size not a multiple of 16,
+ * cap * page_size or batch * cap beyond int32; ATOM_ERR_ALIGN for a pointer that is not 4-byte aligned. */
+#define ATOM_KV_STEP_OVERFLOW 1
+#define ATOM_KV_STEP_BAD_LENGTH 2
+int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                    int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, void *stream);
+
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised
  * asymmetrically to n_bits in FP16 opmath -- scale = ((max - min) * clip).clamp(1e-5) / (2^n - 1), base =
