@@ -1,6 +1,8 @@
-// Shared by the INT4 paged-KV attention ops (kv_i4.hip: decode, prefill_i4.hip: prefill): the head size, the argument check of
-// the cache tables, and the merge of KV-split partial states float [rows][heads][splits][130] (128 un-normalised values, running
-// maximum in base 2, denominator).
+// Shared by the INT4 paged-KV attention ops (kv_i4.hip: append and decode, prefill_i4.hip: prefill and grouped-query attention): the
+// head size; the cache's arguments, their check and their kernel-argument form; and the KV-split partial states float
+// [rows][heads][splits][130] (128 un-normalised values, running maximum in base 2, denominator) -- their size, the rule for a
+// workspace that cannot hold them, the merge kernel and its ONLY launch (launch_merge).  Each file keeps its own plan (DecodePlan,
+// PrefillPlan: splits and launch geometry), computed by one function that its queries and its launcher both call.
 #pragma once
 #include "common.h"
 
@@ -73,12 +75,48 @@ __global__ __launch_bounds__(128) void decode_merge_kernel(const float *ws, half
   o[bh * kHeadDim + dim] = (half_t)(den > 0.f ? acc / den : 0.f);
 }
 
+// ---- host side
+struct KvParams {     // the cache as the append and decode kernels take it
+  uint8_t *data;
+  half_t *param;
+  const int32_t *indptr, *indices, *last_page_offset;
+  int batch, L, layer, N, P;
+};
+
+static KvParams kv_params(const void *kv_data, const void *kv_param, const int32_t *indptr, const int32_t *indices, const int32_t *lpo,
+                          int batch, int L, int layer, int N, int P) {
+  KvParams kv;
+  kv.data = (uint8_t *)kv_data, kv.param = (half_t *)kv_param;
+  kv.indptr = indptr, kv.indices = indices, kv.last_page_offset = lpo;
+  kv.batch = batch, kv.L = L, kv.layer = layer, kv.N = N, kv.P = P;
+  return kv;
+}
+
 static int check_kv(const void *kv_data, const void *kv_param, const int32_t *indptr, const int32_t *indices,
                     const int32_t *lpo, int batch, int L, int layer, int N, int P, int D) {
   if (!kv_data || !kv_param || !indptr || !indices || !lpo) return ATOM_ERR_INVALID_ARG;
   if (D != kHeadDim || batch < 1 || L < 1 || layer < 0 || layer >= L || N < 1 || P < 16 || (P % 16) != 0) return ATOM_ERR_SHAPE;
   if (!aligned16(kv_data) || (reinterpret_cast<uintptr_t>(kv_param) & 3u)) return ATOM_ERR_ALIGN;
   return ATOM_OK;
+}
+
+static size_t partial_state_bytes(int64_t rows_times_heads, int splits) {
+  return (size_t)rows_times_heads * splits * (kHeadDim + 2) * sizeof(float);
+}
+
+// splits > 1 leave their partial states in the caller's workspace; where it is missing, too small or misaligned the op runs unsplit
+static bool workspace_holds(const void *ws, size_t ws_bytes, int64_t rows_times_heads, int splits) {
+  return ws && ws_bytes >= partial_state_bytes(rows_times_heads, splits) && aligned16(ws);
+}
+
+static void launch_merge(const void *ws, void *o, int64_t rows_times_heads, int splits, hipStream_t s) {
+  const dim3 grid((unsigned)rows_times_heads), block(128);
+  if (splits <= 8)
+    hipLaunchKernelGGL(decode_merge_kernel<8>, grid, block, 0, s, (const float *)ws, (half_t *)o, splits);
+  else if (splits <= 16)
+    hipLaunchKernelGGL(decode_merge_kernel<16>, grid, block, 0, s, (const float *)ws, (half_t *)o, splits);
+  else
+    hipLaunchKernelGGL(decode_merge_kernel<32>, grid, block, 0, s, (const float *)ws, (half_t *)o, splits);
 }
 
 }  // namespace atom

@@ -25,6 +25,10 @@
 // De-quantisation is folded: the zero point of V is accumulated as a scalar (o = sum p*s*u - sum p*z).  Every quad runs
 // its own online softmax over its token subsequence; the 16 quads (and the KV splits, through a small FP32 workspace)
 // are merged once at the end.
+//
+// Host side: decode_plan() is the one place that decides a decode call's waves per pair, their grouping and the partial states they
+// leave; the two queries (workspace bytes, splits) and the launcher read it.  The cache's argument check, the partial states' size
+// and the merge launch are kv_attn.h's.
 #include <math.h>
 
 #include <cstdlib>
@@ -32,13 +36,6 @@
 #include "kv_attn.h"
 
 namespace atom {
-
-struct KvParams {
-  uint8_t *data;
-  half_t *param;
-  const int32_t *indptr, *indices, *last_page_offset;
-  int batch, L, layer, N, P;
-};
 
 // ------------------------------------------------------------------------------------------------ append
 struct AppendParams {
@@ -232,7 +229,7 @@ __device__ __forceinline__ TileRegs load_tile(const TileBase &tb, int64_t page, 
 // no merge launch (4.7 us of a decode step at batch 16).  A workgroup is always 12 waves = a CU's resident set at this kernel's
 // registers: 12 / splits pairs x splits (a 6-wave workgroup per pair left every second wave slot empty -- the second one does not fit
 // beside the first's 2 + 2 + 1 + 1 waves per SIMD -- and cost 38.5 us instead of 27.3: profiles/r06/ab_decode_ring.txt).  Used when
-// pairs alone fill the chip and splits divides 12 (batch_decode_impl).  The merge below is decode_merge_kernel's, operation for
+// pairs alone fill the chip and splits divides 12 (decode_plan).  The merge below is decode_merge_kernel's, operation for
 // operation: same bits.
 constexpr int kWgmWaves = 12;
 #ifndef ATOM_DECODE_DP
@@ -645,16 +642,24 @@ static int decode_splits_total(int batch, int N, int max_pages, int P) {
   return best;
 }
 
-// The plan of a decode call: waves per (sequence, head) pair, and how many of them share a workgroup and leave ONE partial state
-// (kInner where the pairs do not fill the chip and the count divides; the pairs-fill-the-chip case merges ALL of a pair's waves in
-// one workgroup: batch_decode_impl's wgm).  decode_splits() = partial states per pair as the merge / the workspace see them.
-static int decode_inner(int batch, int N, int total) {
-  if ((int64_t)batch * N >= ATOM_TUNE("ATOM_DECODE_WGM_PAIRS", 256) && kWgmWaves % total == 0) return 1;   // (wgm)
-  return (ATOM_TUNE("ATOM_DECODE_INNER", 1) && total >= kInner && total % kInner == 0) ? kInner : 1;
-}
-static int decode_splits(int batch, int N, int max_pages, int P) {
-  const int total = decode_splits_total(batch, N, max_pages, P);
-  return total / decode_inner(batch, N, total);
+// The plan of a decode call: `total` waves per (sequence, head) pair; `inner` of them share a workgroup and leave ONE partial state
+// (kInner where the count divides); `splits` = total / inner partial states per pair, as the merge and the workspace see them.  Where
+// the pairs alone fill the chip and total divides a workgroup's 12 waves, ALL of a pair's waves merge in one workgroup (wgm: one
+// launch, no workspace, same split count and merge arithmetic -- the same bits as kernel + decode_merge_kernel) -- given somewhere to
+// put the output.  The queries do not know `o` and ask with have_o = false: they report the partial states that a call without `o`
+// (the consumer merges) leaves in the workspace, which a wgm call then does not touch.
+struct DecodePlan {
+  int total, inner, splits;
+  bool wgm;
+};
+static DecodePlan decode_plan(int batch, int N, int max_pages, int P, bool have_o) {
+  DecodePlan pl;
+  pl.total = decode_splits_total(batch, N, max_pages, P);
+  const bool fills = (int64_t)batch * N >= ATOM_TUNE("ATOM_DECODE_WGM_PAIRS", 256) && kWgmWaves % pl.total == 0;
+  pl.wgm = fills && have_o && pl.total > 1;
+  pl.inner = (!fills && ATOM_TUNE("ATOM_DECODE_INNER", 1) && pl.total >= kInner && pl.total % kInner == 0) ? kInner : 1;
+  pl.splits = pl.total / pl.inner;
+  return pl;
 }
 
 }  // namespace atom
@@ -675,8 +680,7 @@ int atom_kv_append_i4(void *kv_data, void *kv_param, const int32_t *kv_indptr, c
   if (!aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(k_param) & 3u) ||
       (reinterpret_cast<uintptr_t>(v_param) & 3u))
     return ATOM_ERR_ALIGN;
-  AppendParams p{{(uint8_t *)kv_data, (half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
-                  layer_idx, num_heads, page_size},
+  AppendParams p{kv_params(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads, page_size),
                  (const uint8_t *)k, (const uint8_t *)v, (const half_t *)k_param, (const half_t *)v_param,
                  append_indptr, total_tokens};
   hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)total_tokens), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
@@ -691,8 +695,7 @@ int atom_kv_quant_append_f32(void *kv_data, void *kv_param, const int32_t *kv_in
   if (st != ATOM_OK) return st;
   if (!k_f32 || !v_f32) return ATOM_ERR_INVALID_ARG;
   if (!aligned16(k_f32) || !aligned16(v_f32)) return ATOM_ERR_ALIGN;
-  QuantAppendParams p{{(uint8_t *)kv_data, (half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
-                       layer_idx, num_heads, page_size},
+  QuantAppendParams p{kv_params(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads, page_size),
                       (const float *)k_f32, (const float *)v_f32};
   hipLaunchKernelGGL(kv_quant_append_kernel, dim3((unsigned)(((int64_t)batch * 2 * num_heads + 7) / 8)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), p);
@@ -701,11 +704,11 @@ int atom_kv_quant_append_f32(void *kv_data, void *kv_param, const int32_t *kv_in
 
 size_t atom_batch_decode_i4_workspace_bytes(int batch, int num_heads, int page_size, int max_pages_per_seq) {
   if (batch < 1 || num_heads < 1 || page_size < 16) return 0;
-  const int s = decode_splits(batch, num_heads, max_pages_per_seq, page_size);
-  return s > 1 ? (size_t)batch * num_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+  const int s = decode_plan(batch, num_heads, max_pages_per_seq, page_size, false).splits;
+  return s > 1 ? partial_state_bytes((int64_t)batch * num_heads, s) : 0;
 }
 
-static int batch_decode_impl(void *o, const void *q, const float *k32, const float *v32, void *kv_data, void *kv_param,
+static int batch_decode_impl(void *o, const void *q, const float *k32, const float *v32, const void *kv_data, const void *kv_param,
                              const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int batch,
                              int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
                              float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
@@ -714,54 +717,40 @@ static int batch_decode_impl(void *o, const void *q, const float *k32, const flo
   if (st != ATOM_OK) return st;
   if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
   if ((o && !aligned16(o)) || !aligned16(q)) return ATOM_ERR_ALIGN;
-  int total = decode_splits_total(batch, num_heads, max_pages_per_seq, page_size);     // waves per (sequence, head) pair
-  // sequences x heads fill the chip on their own: the splits become the waves of one workgroup and merge in LDS -- one launch, no
-  // workspace (same split count, same merge arithmetic: the same bits as kernel + decode_merge_kernel)
-  const bool wgm = o && total > 1 && kWgmWaves % total == 0 && (int64_t)batch * num_heads >= ATOM_TUNE("ATOM_DECODE_WGM_PAIRS", 256);
-  int inner = wgm ? 1 : decode_inner(batch, num_heads, total);
-  int splits = total / inner;                           // partial states per pair (what the merge and the workspace see)
-  const size_t need = (size_t)batch * num_heads * splits * (kHeadDim + 2) * sizeof(float);
-  if (!wgm && splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) { total = 1; inner = 1; splits = 1; }
+  DecodePlan pl = decode_plan(batch, num_heads, max_pages_per_seq, page_size, o != nullptr);
+  const int64_t pairs = (int64_t)batch * num_heads;
+  if (!pl.wgm && pl.splits > 1 && !workspace_holds(workspace, workspace_bytes, pairs, pl.splits)) pl = DecodePlan{1, 1, 1, false};
   // o == NULL: the split partial states stay in the workspace un-merged (atom_batch_decode_i4_splits() of them; the consumer merges:
   // atom_gemm_w4a4_multi_merge_q) -- only meaningful when the KV range IS split
-  if (!o && splits < 2) return ATOM_ERR_INVALID_ARG;
-  DecodeParams p{{(uint8_t *)kv_data, (half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
-                  layer_idx, num_heads, page_size},
-                 make_fastdiv((unsigned)num_heads), make_fastdiv((unsigned)total), make_fastdiv((unsigned)(page_size >> 4)),
-                 make_fastdiv((unsigned)page_size), wgm ? kWgmWaves / total : 1,
-                 (const half_t *)q, (half_t *)o, (float *)workspace, total,
+  if (!o && pl.splits < 2) return ATOM_ERR_INVALID_ARG;
+  const int ppw = pl.wgm ? kWgmWaves / pl.total : 1;    // (sequence, head) pairs per workgroup
+  DecodeParams p{kv_params(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads, page_size),
+                 make_fastdiv((unsigned)num_heads), make_fastdiv((unsigned)pl.total), make_fastdiv((unsigned)(page_size >> 4)),
+                 make_fastdiv((unsigned)page_size), ppw,
+                 (const half_t *)q, (half_t *)o, (float *)workspace, pl.total,
                  1.0f / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, k32, v32};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (wgm) {
-    const int ppw = kWgmWaves / total;                  // (sequence, head) pairs per workgroup
-    hipLaunchKernelGGL(batch_decode_kernel<true>, dim3((unsigned)((batch * num_heads + ppw - 1) / ppw)), dim3(64 * kWgmWaves), 0, s, p);
-    return check_launch();
-  }
-  if (inner == kInner)
-    hipLaunchKernelGGL((batch_decode_kernel<false, kInner>), dim3((unsigned)(batch * num_heads), (unsigned)splits), dim3(64 * kInner), 0, s, p);
+  const dim3 grid((unsigned)pairs, (unsigned)pl.splits);
+  if (pl.wgm)
+    hipLaunchKernelGGL(batch_decode_kernel<true>, dim3((unsigned)((pairs + ppw - 1) / ppw)), dim3(64 * kWgmWaves), 0, s, p);
+  else if (pl.inner == kInner)
+    hipLaunchKernelGGL((batch_decode_kernel<false, kInner>), grid, dim3(64 * kInner), 0, s, p);
   else
-    hipLaunchKernelGGL(batch_decode_kernel<false>, dim3((unsigned)(batch * num_heads), (unsigned)splits), dim3(64), 0, s, p);
-  if (splits > 1 && o) {
-    if (splits <= 8)
-      hipLaunchKernelGGL(decode_merge_kernel<8>, dim3((unsigned)(batch * num_heads)), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-    else if (splits <= 16)
-      hipLaunchKernelGGL(decode_merge_kernel<16>, dim3((unsigned)(batch * num_heads)), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-    else
-      hipLaunchKernelGGL(decode_merge_kernel<32>, dim3((unsigned)(batch * num_heads)), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-  }
+    hipLaunchKernelGGL(batch_decode_kernel<false>, grid, dim3(64), 0, s, p);
+  if (!pl.wgm && pl.splits > 1 && o) launch_merge(workspace, o, pairs, pl.splits, s);
   return check_launch();
 }
 
 int atom_batch_decode_i4_splits(int batch, int num_heads, int page_size, int max_pages_per_seq) {
   if (batch < 1 || num_heads < 1 || page_size < 16) return 0;
-  return decode_splits(batch, num_heads, max_pages_per_seq, page_size);
+  return decode_plan(batch, num_heads, max_pages_per_seq, page_size, false).splits;
 }
 
 int atom_batch_decode_i4(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
                          const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers,
                          int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
                          int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
-  return batch_decode_impl(o, q, nullptr, nullptr, const_cast<void *>(kv_data), const_cast<void *>(kv_param), kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
+  return batch_decode_impl(o, q, nullptr, nullptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
                            num_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace, workspace_bytes, stream);
 }
 

@@ -32,6 +32,10 @@
 // Short chunks on long prefixes (few query blocks, many key tiles): the KV range of a block is split over `splits` workgroups that
 // write the decode op's partial states float [rows][heads][splits][130] to the workspace, merged by decode_merge_kernel (kv_attn.h)
 // with the query rows as its "batch".
+//
+// Host side: the three entry points (prefill, grouped-query prefill, grouped-query decode) are one kernel and one host path:
+// prefill_plan() decides rows, query blocks and splits for the workspace queries and for launch_prefill(), which checks the arguments,
+// fills PrefillParams by name, launches and merges (launch_merge, kv_attn.h).
 #include <math.h>
 
 #include <algorithm>
@@ -349,18 +353,60 @@ static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages) 
   return best;
 }
 
-// Prefill: the rows of a (sequence, K/V head) are max_q_len * G
-static int gqa_prefill_rows(int64_t total_q, int max_q_len, int G) {
-  return (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
+// The plan of a call: query rows of a (sequence, K/V head) at most -- max_q_len * G, or G for the decode entry (one query per
+// sequence) --, the query blocks they make, and the KV splits by the entry's policy.
+struct PrefillPlan {
+  int rows, nqb, splits;
+};
+static PrefillPlan prefill_plan(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages) {
+  PrefillPlan pl;
+  pl.rows = decode ? G : (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
+  pl.nqb = (int)(((int64_t)pl.rows + kPfRows - 1) / kPfRows);
+  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages) : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages);
+  return pl;
 }
 
-static void launch_merge(const float *ws, half_t *o, int64_t rows, int splits, hipStream_t s) {
-  if (splits <= 8)
-    hipLaunchKernelGGL(decode_merge_kernel<8>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
-  else if (splits <= 16)
-    hipLaunchKernelGGL(decode_merge_kernel<16>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
+static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages) {
+  if (total_q < 1 || batch < 1 || num_kv_heads < 1 || P < 16 || max_q_len < 1) return 0;
+  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages).splits;
+  return s > 1 ? partial_state_bytes(total_q * num_kv_heads * G, s) : 0;
+}
+
+// The one host path of batch_prefill_kernel.  decode: the grouped-query decode entry -- one query per sequence (no qo_indptr, total_q =
+// batch), and `o` may be NULL: the partial states stay in the workspace un-merged, as atom_batch_decode_i4 leaves them.  The prefill
+// entries refuse total_q / max_q_len (shape) before they look at alignment; the decode entry has no such arguments.
+static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                          const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                          int batch, int num_layers, int layer_idx, int G, int num_kv_heads, int page_size, int head_dim, float rope_theta,
+                          float rope_scale, int max_pages, void *workspace, size_t workspace_bytes, void *stream) {
+  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
+                          page_size, head_dim);
+  if (st != ATOM_OK) return st;
+  if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f) || (!decode && (!o || !qo_indptr))) return ATOM_ERR_INVALID_ARG;
+  if (!decode && (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1)) return ATOM_ERR_SHAPE;
+  if ((o && !aligned16(o)) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
+  PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages);
+  const int num_qo_heads = num_kv_heads * G;
+  const int64_t rows_heads = total_q * num_qo_heads;
+  if (pl.splits > 1 && !workspace_holds(workspace, workspace_bytes, rows_heads, pl.splits)) pl.splits = 1;
+  if (!o && pl.splits < 2) return ATOM_ERR_INVALID_ARG;
+  const int64_t grid = (int64_t)pl.nqb * batch * num_kv_heads * pl.splits;
+  if (grid > 0x7fffffff || rows_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
+  PrefillParams p;                                        // by name: the fields' order is the kernel's business
+  p.data = (const uint8_t *)kv_data, p.param = (const half_t *)kv_param;
+  p.kv_indptr = kv_indptr, p.kv_indices = kv_indices, p.last_page_offset = last_page_offset, p.qo_indptr = qo_indptr;
+  p.q = (const half_t *)q, p.o = (half_t *)o, p.ws = (float *)workspace;
+  p.batch = batch, p.L = num_layers, p.layer = layer_idx, p.N = num_kv_heads, p.P = page_size;
+  p.nqb = pl.nqb, p.splits = pl.splits;
+  p.qk_scale = kLog2e / sqrtf((float)kHeadDim), p.log2_theta = log2f(rope_theta), p.rope_inv_scale = 1.0f / rope_scale;
+  p.G = G, p.Nq = num_qo_heads;                           // (batch_prefill_kernel<false> reads neither)
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (G == 1 && !decode)                                  // the MHA entry: the GQA entries forward G = 1 to the MHA ops
+    hipLaunchKernelGGL(batch_prefill_kernel<false>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
   else
-    hipLaunchKernelGGL(decode_merge_kernel<32>, dim3((unsigned)rows), dim3(128), 0, s, ws, o, splits);
+    hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  if (pl.splits > 1 && o) launch_merge(workspace, o, rows_heads, pl.splits, s);
+  return check_launch();
 }
 
 }  // namespace atom
@@ -371,53 +417,22 @@ extern "C" {
 
 size_t atom_batch_prefill_i4_workspace_bytes(int64_t total_q, int batch, int num_heads, int page_size, int max_q_len,
                                              int max_pages_per_seq) {
-  if (total_q < 1 || batch < 1 || num_heads < 1 || page_size < 16 || max_q_len < 1) return 0;
-  const int s = prefill_splits(batch, num_heads, (int)std::min<int64_t>(max_q_len, total_q), page_size, max_pages_per_seq);
-  return s > 1 ? (size_t)total_q * num_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+  return prefill_workspace_bytes(false, total_q, max_q_len, batch, 1, num_heads, page_size, max_pages_per_seq);
 }
 
 int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
                           const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
                           int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
-  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads,
-                          page_size, head_dim);
-  if (st != ATOM_OK) return st;
-  if (!o || !q || !qo_indptr || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
-  if (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1) return ATOM_ERR_SHAPE;
-  if (!aligned16(o) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
-  const int mq = (int)std::min<int64_t>(max_q_len, total_q);
-  const int nqb = (mq + kPfRows - 1) / kPfRows;
-  int splits = prefill_splits(batch, num_heads, mq, page_size, max_pages_per_seq);
-  const size_t need = (size_t)total_q * num_heads * splits * (kHeadDim + 2) * sizeof(float);
-  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
-  const int64_t grid = (int64_t)nqb * batch * num_heads * splits;
-  if (grid > 0x7fffffff || (int64_t)total_q * num_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
-  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, qo_indptr,
-                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_heads, page_size, nqb, splits,
-                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(batch_prefill_kernel<false>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
-  if (splits > 1) {
-    const unsigned rows = (unsigned)(total_q * num_heads);
-    if (splits <= 8)
-      hipLaunchKernelGGL(decode_merge_kernel<8>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-    else if (splits <= 16)
-      hipLaunchKernelGGL(decode_merge_kernel<16>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-    else
-      hipLaunchKernelGGL(decode_merge_kernel<32>, dim3(rows), dim3(128), 0, s, (const float *)workspace, (half_t *)o, splits);
-  }
-  return check_launch();
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, 1, num_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
+                        workspace_bytes, stream);
 }
 
 size_t atom_batch_prefill_gqa_i4_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
                                                  int max_q_len, int max_pages_per_seq) {
-  const int G = gqa_group(num_qo_heads, num_kv_heads);
-  if (G == 0) return 0;
-  if (G == 1) return atom_batch_prefill_i4_workspace_bytes(total_q, batch, num_qo_heads, page_size, max_q_len, max_pages_per_seq);
-  if (total_q < 1 || batch < 1 || page_size < 16 || max_q_len < 1) return 0;
-  const int s = prefill_splits(batch, num_kv_heads, gqa_prefill_rows(total_q, max_q_len, G), page_size, max_pages_per_seq);
-  return s > 1 ? (size_t)total_q * num_qo_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+  const int G = gqa_group(num_qo_heads, num_kv_heads);   // (G = 1 is the MHA plan: the same function)
+  return G ? prefill_workspace_bytes(false, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages_per_seq) : 0;
 }
 
 int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
@@ -427,47 +442,22 @@ int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, 
                               void *stream) {
   const int G = gqa_group(num_qo_heads, num_kv_heads);
   if (G == 0) return ATOM_ERR_SHAPE;
-  if (G == 1)
-    return atom_batch_prefill_i4(o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
-                                 num_layers, layer_idx, num_qo_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq,
-                                 workspace, workspace_bytes, stream);
-  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
-                          page_size, head_dim);
-  if (st != ATOM_OK) return st;
-  if (!o || !q || !qo_indptr || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
-  if (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1) return ATOM_ERR_SHAPE;
-  if (!aligned16(o) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
-  const int rows = gqa_prefill_rows(total_q, max_q_len, G);
-  const int nqb = (int)(((int64_t)rows + kPfRows - 1) / kPfRows);
-  int splits = prefill_splits(batch, num_kv_heads, rows, page_size, max_pages_per_seq);
-  const size_t need = (size_t)total_q * num_qo_heads * splits * (kHeadDim + 2) * sizeof(float);
-  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
-  const int64_t grid = (int64_t)nqb * batch * num_kv_heads * splits;
-  if (grid > 0x7fffffff || (int64_t)total_q * num_qo_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
-  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, qo_indptr,
-                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_kv_heads, page_size, nqb, splits,
-                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, G, num_qo_heads};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
-  if (splits > 1) launch_merge((const float *)workspace, (half_t *)o, total_q * num_qo_heads, splits, s);
-  return check_launch();
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
+                        workspace_bytes, stream);
 }
 
 size_t atom_batch_decode_gqa_i4_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq) {
   const int G = gqa_group(num_qo_heads, num_kv_heads);
-  if (G == 0) return 0;
   if (G == 1) return atom_batch_decode_i4_workspace_bytes(batch, num_qo_heads, page_size, max_pages_per_seq);
-  if (batch < 1 || page_size < 16) return 0;
-  const int s = gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
-  return s > 1 ? (size_t)batch * num_qo_heads * s * (kHeadDim + 2) * sizeof(float) : 0;
+  return G ? prefill_workspace_bytes(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq) : 0;
 }
 
 int atom_batch_decode_gqa_i4_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq) {
   const int G = gqa_group(num_qo_heads, num_kv_heads);
-  if (G == 0) return 0;
   if (G == 1) return atom_batch_decode_i4_splits(batch, num_qo_heads, page_size, max_pages_per_seq);
-  if (batch < 1 || page_size < 16) return 0;
-  return gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
+  if (G == 0 || batch < 1 || page_size < 16) return 0;
+  return prefill_plan(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq).splits;
 }
 
 int atom_batch_decode_gqa_i4(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
@@ -480,26 +470,9 @@ int atom_batch_decode_gqa_i4(void *o, const void *q, const void *kv_data, const 
     return atom_batch_decode_i4(o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
                                 num_qo_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace, workspace_bytes,
                                 stream);
-  const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
-                          page_size, head_dim);
-  if (st != ATOM_OK) return st;
-  if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
-  if ((o && !aligned16(o)) || !aligned16(q)) return ATOM_ERR_ALIGN;
-  int splits = gqa_decode_splits(batch, num_kv_heads, page_size, max_pages_per_seq);
-  const size_t need = (size_t)batch * num_qo_heads * splits * (kHeadDim + 2) * sizeof(float);
-  if (splits > 1 && (!workspace || workspace_bytes < need || !aligned16(workspace))) splits = 1;
-  // o == NULL: the partial states stay in the workspace un-merged, as atom_batch_decode_i4 leaves them
-  if (!o && splits < 2) return ATOM_ERR_INVALID_ARG;
-  const int nqb = (G + kPfRows - 1) / kPfRows;
-  const int64_t grid = (int64_t)nqb * batch * num_kv_heads * splits;
-  if (grid > 0x7fffffff || (int64_t)batch * num_qo_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
-  PrefillParams p{(const uint8_t *)kv_data, (const half_t *)kv_param, kv_indptr, kv_indices, last_page_offset, nullptr,
-                  (const half_t *)q, (half_t *)o, (float *)workspace, batch, num_layers, layer_idx, num_kv_heads, page_size, nqb, splits,
-                  kLog2e / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, G, num_qo_heads};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
-  if (splits > 1 && o) launch_merge((const float *)workspace, (half_t *)o, (int64_t)batch * num_qo_heads, splits, s);
-  return check_launch();
+  return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -565,20 +565,31 @@ def _kv_dims(kv):
     return num_layers, num_heads, page_size, half_dim * 2
 
 
-def _kv_append(kv, k, v, k_param, v_param, append_indptr, layer_idx, what):
-    for t in (kv.data, kv.param, k, v, k_param, v_param):
+def _require_cuda(*tensors):
+    for t in tensors:
         if not t.is_cuda:
             raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
+
+
+def _kv_args(kv, layer_idx, num_qo_heads=None):
+    """The cache as every C entry point takes it: its five pointers; (batch, layers, layer, [query heads: the grouped-query entries,]
+    K/V heads, page size, head dim); the host's bound of a sequence's pages (0: unknown -- no KV split)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
+    ptrs = tuple(t.data_ptr() for t in (kv.data, kv.param, kv.indptr, kv.indicies, kv.last_page_offset))
+    heads = (num_heads,) if num_qo_heads is None else (num_qo_heads, num_heads)
+    dims = (kv.last_page_offset.numel(), num_layers, int(layer_idx)) + heads + (page_size, head_dim)
+    return ptrs, dims, int(getattr(kv, "max_pages", 0))
+
+
+def _kv_append(kv, k, v, k_param, v_param, append_indptr, layer_idx, what):
+    _require_cuda(kv.data, kv.param, k, v, k_param, v_param)
+    ptrs, dims, _ = _kv_args(kv, layer_idx)
+    num_heads, head_dim = dims[3], dims[5]
     total = k.size(0)
     assert k.shape == v.shape == (total, num_heads, head_dim // 2) and k.dtype == v.dtype == torch.uint8
     assert k_param.numel() == v_param.numel() == total * num_heads * 2 and k_param.dtype == torch.float16
-    batch = kv.last_page_offset.numel()
-    st = L.lib().atom_kv_append_i4(kv.data.data_ptr(), kv.param.data_ptr(), kv.indptr.data_ptr(),
-                                    kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(), k.contiguous().data_ptr(),
-                                    v.contiguous().data_ptr(), k_param.contiguous().data_ptr(),
-                                    v_param.contiguous().data_ptr(), L.ptr(append_indptr), total, batch, num_layers,
-                                    int(layer_idx), num_heads, page_size, head_dim, L.current_stream(k.device))
+    st = L.lib().atom_kv_append_i4(*ptrs, k.contiguous().data_ptr(), v.contiguous().data_ptr(), k_param.contiguous().data_ptr(),
+                                    v_param.contiguous().data_ptr(), L.ptr(append_indptr), total, *dims, L.current_stream(k.device))
     L.check(st, what)
 
 
@@ -595,19 +606,20 @@ def append_kv_i4(kv, k, v, k_param, v_param, layer_idx: int):
     _kv_append(kv, k, v, k_param, v_param, None, layer_idx, "atom_kv_append_i4")
 
 
+def _require_kv_f32(kv, k_f32, v_f32):
+    """this step's FP32 k / v projections [batch, heads * 128] of the fused appends"""
+    _require_cuda(k_f32, v_f32)
+    num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
+    for t in (k_f32, v_f32):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (kv.last_page_offset.numel(), num_heads * head_dim)
+
+
 def quant_append_kv_i4(kv, k_f32: torch.Tensor, v_f32: torch.Tensor, layer_idx: int):
     """NEW (fused decode step): quantise the FP32 k / v projections [batch, heads*128] per head (the _o4 epilogue) and
     append them as the last token of every sequence.  Same cache contents as dense_layer_gemm_i4_o4 + append_kv_i4."""
-    num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
-    batch = kv.last_page_offset.numel()
-    for t in (k_f32, v_f32):
-        if not t.is_cuda:
-            raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (batch, num_heads * head_dim)
-    st = L.lib().atom_kv_quant_append_f32(kv.data.data_ptr(), kv.param.data_ptr(), kv.indptr.data_ptr(),
-                                          kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(), k_f32.data_ptr(),
-                                          v_f32.data_ptr(), batch, num_layers, int(layer_idx), num_heads, page_size, head_dim,
-                                          L.current_stream(k_f32.device))
+    _require_kv_f32(kv, k_f32, v_f32)
+    ptrs, dims, _ = _kv_args(kv, layer_idx)
+    st = L.lib().atom_kv_quant_append_f32(*ptrs, k_f32.data_ptr(), v_f32.data_ptr(), *dims, L.current_stream(k_f32.device))
     L.check(st, "atom_kv_quant_append_f32")
 
 
@@ -647,6 +659,17 @@ def decode_splits(batch: int, kv, num_qo_heads: int = None) -> int:
     return int(L.lib().atom_batch_decode_gqa_i4_splits(int(batch), nq, num_heads, page_size, max_pages))
 
 
+def _decode_outputs(q, merge, ws_bytes, splits):
+    """(o, workspace, what the op returns) of a decode call.  merge=False: no `o`; the partial states go to a tensor of their own"""
+    if merge:
+        o = torch.empty_like(q)
+        return o, (_workspace(q.device, ws_bytes) if ws_bytes else None), o
+    batch, heads = q.shape[:2]
+    assert splits >= 2 and ws_bytes == batch * heads * splits * 130 * 4, "merge=False needs a split KV range (decode_splits)"
+    part = torch.empty((batch, heads, splits, 130), dtype=torch.float32, device=q.device)
+    return None, part, part
+
+
 def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True):
     """Decode attention over the INT4 paged cache, RoPE fused.  Reference: punica/ops/__init__.py:21-30 ->
     FlashInferBatchDecodeKernel_i4 (rope_theta 1e4, rope_scale 1 hard-coded there).  q fp16 [batch, heads, 128].
@@ -660,70 +683,27 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
-    if q.dim() == 3 and q.size(1) != num_heads:
-        return _batch_decode_gqa_i4(q, kv, layer_idx, rope_theta, rope_scale, append_kv, merge)
-    assert q.shape == (batch, num_heads, head_dim)
-    lib = L.lib()
-    max_pages = int(getattr(kv, "max_pages", 0))
-    ws_bytes = lib.atom_batch_decode_i4_workspace_bytes(batch, num_heads, page_size, max_pages)
-    if not merge:
-        splits = lib.atom_batch_decode_i4_splits(batch, num_heads, page_size, max_pages)
-        assert splits >= 2 and ws_bytes == batch * num_heads * splits * 130 * 4, "merge=False needs a split KV range (decode_splits)"
-        part = torch.empty((batch, num_heads, splits, 130), dtype=torch.float32, device=q.device)
-        o, ws = None, part
-    else:
-        o = torch.empty_like(q)
-        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
-    if append_kv is not None:
-        k32, v32 = append_kv
-        for t in (k32, v32):
-            if not t.is_cuda:
-                raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (batch, num_heads * head_dim)
-        assert batch == kv.last_page_offset.numel()
-        st = lib.atom_batch_decode_append_i4(L.ptr(o), q.data_ptr(), k32.data_ptr(), v32.data_ptr(), kv.data.data_ptr(),
-                                             kv.param.data_ptr(), kv.indptr.data_ptr(), kv.indicies.data_ptr(),
-                                             kv.last_page_offset.data_ptr(), batch, num_layers, int(layer_idx), num_heads, page_size,
-                                             head_dim, float(rope_theta), float(rope_scale), max_pages, L.ptr(ws), ws_bytes,
-                                             L.current_stream(q.device))
-        L.check(st, "atom_batch_decode_append_i4")
-        return o if merge else part
-    st = lib.atom_batch_decode_i4(L.ptr(o), q.data_ptr(), kv.data.data_ptr(), kv.param.data_ptr(),
-                                  kv.indptr.data_ptr(), kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(), batch,
-                                  num_layers, int(layer_idx), num_heads, page_size, head_dim, float(rope_theta),
-                                  float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
-    L.check(st, "atom_batch_decode_i4")
-    return o if merge else part
-
-
-def _batch_decode_gqa_i4(q, kv, layer_idx, rope_theta, rope_scale, append_kv, merge):
-    num_layers, num_kv_heads, page_size, head_dim = _kv_dims(kv)
-    batch, nq = q.size(0), _qo_heads(q.size(1), num_kv_heads)
-    assert q.shape == (batch, nq, head_dim) and q.is_contiguous()
-    if append_kv is not None:
+    gqa = q.dim() == 3 and q.size(1) != num_heads
+    nq = _qo_heads(q.size(1), num_heads) if gqa else num_heads
+    assert q.shape == (batch, nq, head_dim)
+    if gqa and append_kv is not None:
         raise ValueError("append_kv= is not built for grouped-query attention: append with quant_append_kv_i4 first")
-    for t in (kv.data, kv.param):
-        if not t.is_cuda:
-            raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
+    _require_cuda(kv.data, kv.param)
     assert batch == kv.last_page_offset.numel()
+    ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq if gqa else None)
     lib = L.lib()
-    max_pages = int(getattr(kv, "max_pages", 0))
-    ws_bytes = lib.atom_batch_decode_gqa_i4_workspace_bytes(batch, nq, num_kv_heads, page_size, max_pages)
-    if not merge:
-        splits = lib.atom_batch_decode_gqa_i4_splits(batch, nq, num_kv_heads, page_size, max_pages)
-        assert splits >= 2 and ws_bytes == batch * nq * splits * 130 * 4, "merge=False needs a split KV range (decode_splits)"
-        part = torch.empty((batch, nq, splits, 130), dtype=torch.float32, device=q.device)
-        o, ws = None, part
-    else:
-        o = torch.empty_like(q)
-        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
-    st = lib.atom_batch_decode_gqa_i4(L.ptr(o), q.data_ptr(), kv.data.data_ptr(), kv.param.data_ptr(), kv.indptr.data_ptr(),
-                                      kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(), batch, num_layers, int(layer_idx), nq,
-                                      num_kv_heads, page_size, head_dim, float(rope_theta), float(rope_scale), max_pages, L.ptr(ws),
-                                      ws_bytes, L.current_stream(q.device))
-    L.check(st, "atom_batch_decode_gqa_i4")
-    return o if merge else part
-
+    name = "atom_batch_decode_gqa_i4" if gqa else "atom_batch_decode_i4"
+    plan = dims[:1] + dims[3:-1] + (max_pages,)              # (batch, [query heads,] K/V heads, page size, max_pages): what the plan queries take
+    ws_bytes = getattr(lib, name + "_workspace_bytes")(*plan)
+    o, ws, ret = _decode_outputs(q, merge, ws_bytes, None if merge else getattr(lib, name + "_splits")(*plan))
+    new_kv = ()
+    if append_kv is not None:                                # (the MHA op only)
+        _require_kv_f32(kv, *append_kv)
+        name, new_kv = "atom_batch_decode_append_i4", tuple(t.data_ptr() for t in append_kv)
+    st = getattr(lib, name)(L.ptr(o), q.data_ptr(), *new_kv, *ptrs, *dims, float(rope_theta), float(rope_scale), max_pages, L.ptr(ws),
+                            ws_bytes, L.current_stream(q.device))
+    L.check(st, name)
+    return ret
 
 
 def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
@@ -736,38 +716,25 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G,
     atom_batch_prefill_gqa_i4: each staged K/V tile serves the whole group)."""
     _require_cuda_half(q, "q")
-    for t in (qo_indptr, kv.data, kv.param):
-        if not t.is_cuda:
-            raise L.AtomHipError("KV-cache operands must live on the GPU: no CPU fallback")
+    _require_cuda(qo_indptr, kv.data, kv.param)
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     total = q.size(0)
     nq = _qo_heads(q.size(1), num_heads) if q.dim() == 3 else num_heads
     assert q.shape == (total, nq, head_dim) and q.is_contiguous()
     assert qo_indptr.dtype == torch.int32 and qo_indptr.is_contiguous()
-    batch = kv.last_page_offset.numel()
+    ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq)     # the grouped-query entry: at G = 1 it IS the MHA entry (it forwards)
+    batch = dims[0]
     assert qo_indptr.numel() == batch + 1
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
-    max_pages = int(getattr(kv, "max_pages", 0))
-    if nq != num_heads:
-        ws_bytes = lib.atom_batch_prefill_gqa_i4_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
-        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
-        o = torch.empty_like(q)
-        st = lib.atom_batch_prefill_gqa_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, kv.data.data_ptr(),
-                                           kv.param.data_ptr(), kv.indptr.data_ptr(), kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(),
-                                           batch, num_layers, int(layer_idx), nq, num_heads, page_size, head_dim, float(rope_theta),
-                                           float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
-        L.check(st, "atom_batch_prefill_gqa_i4")
-        return o
-    ws_bytes = lib.atom_batch_prefill_i4_workspace_bytes(total, batch, num_heads, page_size, max_q, max_pages)
+    ws_bytes = lib.atom_batch_prefill_gqa_i4_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
     ws = _workspace(q.device, ws_bytes) if ws_bytes else None
     o = torch.empty_like(q)
-    st = lib.atom_batch_prefill_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, kv.data.data_ptr(),
-                                   kv.param.data_ptr(), kv.indptr.data_ptr(), kv.indicies.data_ptr(), kv.last_page_offset.data_ptr(),
-                                   batch, num_layers, int(layer_idx), num_heads, page_size, head_dim, float(rope_theta),
-                                   float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
-    L.check(st, "atom_batch_prefill_i4")
+    st = lib.atom_batch_prefill_gqa_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
+                                       float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+    L.check(st, "atom_batch_prefill_i4" if nq == num_heads else "atom_batch_prefill_gqa_i4")
     return o
+
 
 def kv_fake_quant(x: torch.Tensor, n_bits: int = 4, clip: float = 1.0) -> torch.Tensor:
     """Asymmetric per-head-vector fake quantisation of a [batch, heads, seq, 128] fp16 tensor (any strides over the first
