@@ -125,6 +125,15 @@ int launch_gemm_skinny_multi_q(const GemmParams &p, hipStream_t s);   // ... + t
 bool gemvq_fits(int q_op, int64_t M, int64_t N, int64_t K_total);     // gemvq_w4a4.hip: one or two tokens, the quantiser in front of the dot-product kernel
 bool gemvq_merge_fits(int64_t M, int64_t N, int64_t K_total, int splits);   // ... its merge form (q_op 5)
 int launch_gemvq_multi_q(const GemmParams &p, hipStream_t s);         // ... (p.q_*, p.seg_*): one quantiser per CU, gemv1's summation order
+// Geometries of launch_gemm_f6, picked by f6_pick_cfg (gemm_w4a4.hip): 256x256 (8 waves, one workgroup per CU), 128x128 (4 waves), 128x128
+// with two K groups of 4 waves sharing the tile's K steps, 256x128 (8 waves), 64x64 on a deep LDS ring (gemm_w4a4_mid.hip).  The second
+// line: tuning builds only (ATOM_F6_CFG forces a geometry by its number; 100 and up are ablation / trace forms, launch_gemm_f6_tools)
+enum F6Cfg : int {
+  F6_256x256 = 0, F6_128x128 = 3, F6_128x128_KG2 = 6, F6_256x128 = 8, F6_MID = 20,
+  F6_256x128_P = 1, F6_64x128 = 2, F6_128x128_8W = 4, F6_128x128_KG2_S2 = 5, F6_64x128_KG2 = 9, F6_256x256_32 = 10, F6_64x128_KG4 = 12, F6_128x128_32 = 13, F6_256x256_P = 30,
+};
+// ... and the summation order of each (atom_gemm_w4a4_f6_order): the K steps in order, or the sum of two / four ordered K ranges
+inline int f6_cfg_order(int cfg) { return cfg == F6_64x128_KG4 ? 4 : ((cfg == F6_128x128_KG2_S2 || cfg == F6_128x128_KG2 || cfg == F6_64x128_KG2) ? 2 : 1); }
 int launch_gemm_f6(const GemmParams &p, int cfg, hipStream_t s);   // gemm_w4a4_f6.hip (BF6 operands on the block-scaled MFMA)
 int launch_gemm_f6_mid(const GemmParams &p, hipStream_t s);        // gemm_w4a4_mid.hip: the same for BF6 operands (ATOM_AB_F6 | ATOM_B_F6S)
 int launch_gemm_mid(const GemmParams &p, hipStream_t s);           // gemm_w4a4_mid.hip (packed operands, mid-size batches: 64x64 tiles, deep LDS ring)
@@ -197,6 +206,11 @@ __device__ __forceinline__ unsigned o4_code(float x, float zero, float rs, float
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+#ifdef ATOM_TOOLS
+// traced runs (tools/trace_*.cpp, tools/r06/gemvq_trace.py): the stamp buffer's address arrives in ATOM_TRACE_PTR (hex); null without
+inline half_t *trace_ptr() { const char *e = getenv("ATOM_TRACE_PTR"); return e ? reinterpret_cast<half_t *>(strtoull(e, nullptr, 16)) : nullptr; }
+#endif
 
 // v_cvt_scalef32_2xpk16_bf6_f32 (32 floats -> 32 BF6 fields, the two sources interleaved) through inline asm with an EARLY-CLOBBER
 // destination.  With the builtin, hipcc (ROCm 7.2) lets the register allocator place the 6-register result inside the 16-register

@@ -2477,141 +2477,108 @@ int launch_gemm_f6_gateup(const GemmParams &p, int sim, hipStream_t s) {
   return sim ? f6::launch_q<C, 1>(p, s) : f6::launch_q<C, 2>(p, s);
 }
 
-// cfg: 0 = 256x256 (8 waves, the pipelined kernel) and 3 = 128x128 (4 waves, three workgroups per CU) on 16x16x128 MFMA
-// micro-tiles, 5 / 6 / 9 / 12 = the K-group kernels (128x128 / 64x128 tiles, two or four groups of 4 waves), 8 = 256x128 (8 waves,
-// qk_step; ATOM_B_F6S weights, else 3), 2 = 64x128 (2 waves, 32x32x64 MFMA; split-K when p.splits > 1 and p.ws is set); tuning only: 1 = 256x128,
-// 10 / 13 = 256x256 / 128x128 on the 32x32x64 MFMA, 40 = 256x256 first-generation micro-tile kernel
+// The 128x128 geometry stages the weight scales as float32 (ATOM_B_F6S: 8 % fewer cycles per tile, but 54,272 B of LDS = two workgroups
+// per CU -- the LDS granule makes it 55,040) or as fp16, converted once per step (53,760 B = three).  The former unless the third
+// workgroup saves a round of tiles (profiles/r02_mid_m.txt: 1536x4096x4096 37.7 vs 40.9 us, 1024x11008x4096 64.7 vs 55.4).
+static bool f6_128_f32_scales(const GemmParams &p) {
+  const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
+  return p.sB32 && (t128 + 511) / 512 <= (t128 + 767) / 768;
+}
+
+#ifdef ATOM_TOOLS
+// Tuning builds: what ATOM_F6_CFG forces beyond the dispatched geometries -- traced runs (tools/trace_f6*.cpp), ablation masks
+// (tools/gemm_bench: 100 + mask on the first 256x256 kernel, 1000 + mask on the pipelined one, 2100 + mask on the two-K-group q-step
+// kernel), geometries no shape is dispatched to, split-K (ATOM_F6_SPLITS3).  False: none of these, the product path takes the call.
+static bool launch_gemm_f6_tools(const GemmParams &p, int cfg, hipStream_t s, int &st) {
+  using C256 = f6::Cfg<256, 256, 4, 3>;
+  const bool split = p.splits > 1 && p.ws;
+  st = ATOM_ERR_INVALID_ARG;
+  if (cfg == 116 || cfg == 1016 || cfg == 1005 || cfg == 1009 || cfg == 2016 || cfg == 2017) {
+    GemmParams q = p;
+    q.Dsz = trace_ptr();
+    if (!q.Dsz || (!p.sB32 && cfg != 116 && cfg != 1016)) return true;
+    st = cfg == 116    ? f6::launch<C256, false, 16>(q, s)
+         : cfg == 1016 ? f6::launch_p<C256, 16>(q, s)
+         : cfg == 1005 ? f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, false, 2, false, true>(q, s)
+         : cfg == 1009 ? f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 1>, false, 2, false, true>(q, s)
+         : cfg == 2016 ? f6::launch_q<C256, 0, true>(q, s)
+                       : f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>, true>(q, s);
+    return true;
+  }
+#define ATOM_CASE(c, call) case c: st = call(p, s); return true;
+#define ATOM_CASE2(c, cond, a, b) case c: st = (cond) ? a(p, s) : b(p, s); return true;
+#define ATOM_ABL(a) ATOM_CASE(100 + a, (f6::launch<C256, false, a>))
+#define ATOM_ABLP(a) ATOM_CASE(1000 + a, (f6::launch_p<C256, a>))
+#define ATOM_ABLQ(a) case 2100 + a: if (p.sB32) st = f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>, false, a>(p, s); return true;
+  switch (cfg) {
+    ATOM_ABL(1) ATOM_ABL(2) ATOM_ABL(3) ATOM_ABL(4) ATOM_ABL(6) ATOM_ABL(7) ATOM_ABL(8) ATOM_ABL(10) ATOM_ABL(14) ATOM_ABL(15) ATOM_ABL(32)
+    ATOM_ABLQ(0) ATOM_ABLQ(1) ATOM_ABLQ(2) ATOM_ABLQ(4) ATOM_ABLQ(8) ATOM_ABLQ(16) ATOM_ABLQ(17) ATOM_ABLQ(6) ATOM_ABLQ(14) ATOM_ABLQ(15) ATOM_ABLQ(31)
+    ATOM_ABLQ(3) ATOM_ABLQ(5) ATOM_ABLQ(9) ATOM_ABLQ(7) ATOM_ABLQ(11) ATOM_ABLQ(13)
+    ATOM_ABLP(1) ATOM_ABLP(2) ATOM_ABLP(3) ATOM_ABLP(4) ATOM_ABLP(6) ATOM_ABLP(7) ATOM_ABLP(8) ATOM_ABLP(10) ATOM_ABLP(14) ATOM_ABLP(15)
+    ATOM_ABLP(64) ATOM_ABLP(128) ATOM_ABLP(192) ATOM_ABLP(207) ATOM_ABLP(256) ATOM_ABLP(257) ATOM_ABLP(512) ATOM_ABLP(513) ATOM_ABLP(768) ATOM_ABLP(769)
+    ATOM_ABLP(520) ATOM_ABLP(9) ATOM_ABLP(1024) ATOM_ABLP(2048) ATOM_ABLP(4096)
+    ATOM_CASE2(F6_64x128, split, (f6::launch<f6::Cfg<64, 128, 2, 3>, true>), (f6::launch<f6::Cfg<64, 128, 2, 3>, false>))   // 2 waves, 32x32x64 MFMA
+    ATOM_CASE(F6_256x256_32, (f6::launch<C256, false>))                        // 256x256 on the 32x32x64 MFMA
+    ATOM_CASE(F6_256x128_P, (f6::launch<f6::Cfg<256, 128, 4, 2>, false>))
+    ATOM_CASE(F6_128x128_32, (f6::launch<f6::Cfg<128, 128, 2, 2, 3>, false>))  // 128x128 on the 32x32x64 MFMA
+    case F6_128x128:                                                           // ... its split-K form, else the product path
+      if (!split) return false;
+      st = f6_128_f32_scales(p) ? f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, true>(p, s) : f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>, true>(p, s);
+      return true;
+    // 128x128, two K groups, 2 stages per group; then the 64x128 K-group kernels of rounds 2-4 (the mid-size-batch kernel, F6_MID, has their
+    // shapes now): 32-token wave tiles, groups half a step apart; four K groups of 4 waves (exactly 160 KiB of LDS)
+    ATOM_CASE2(F6_128x128_KG2_S2, p.sB32, (f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, false, 2>), (f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>, false, 2>))
+    ATOM_CASE2(F6_64x128_KG2, p.sB32, (f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 1>, false, 2, true>), (f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 2>, false, 2, true>))
+    ATOM_CASE2(F6_64x128_KG4, p.sB32, (f6::launch_x16<f6::Cfg<64, 128, 1, 2, 4, 1>, false, 4>), (f6::launch_x16<f6::Cfg<64, 128, 1, 2, 4, 2>, false, 4>))
+    case 51: if (!p.sB32) return false;                                        // the two scale forms of F6_128x128
+      st = f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>>(p, s); return true;
+    ATOM_CASE(52, (f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>>))
+    ATOM_CASE(53, (f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3>>))               // F6_128x128 with fp16 weight scales
+    ATOM_CASE(40, (f6::launch_x16<C256>))                                      // 256x256, first-generation micro-tile kernel
+    // round 6, VERDICT r05 missing #1: the SAME kernel body as 8 waves of 64 features x 128 tokens (two per SIMD, 256 registers) and as
+    // 16 waves of 64 x 64 (four per SIMD, 128 registers) -- the same-code A/B behind profiles/r06/ab_16wave.txt
+    case 41: case 42: if (!p.sB32) return false;
+      st = cfg == 41 ? f6::launch_x16<f6::Cfg<256, 256, 4, 3, 2, 1>>(p, s) : f6::launch_x16<f6::Cfg<256, 256, 2, 3, 4, 1>>(p, s);
+      return true;
+    ATOM_CASE2(F6_128x128_8W, split, (f6::launch_x16<f6::Cfg<128, 128, 1, 2, 3>, true>), (f6::launch_x16<f6::Cfg<128, 128, 1, 2, 3>>))   // 8 waves of 64 features x 32 tokens
+    ATOM_CASE(F6_256x256_P, (f6::launch_p<C256>))                              // the pipelined kernel whatever the weight scales
+  }
+#undef ATOM_CASE
+#undef ATOM_CASE2
+#undef ATOM_ABL
+#undef ATOM_ABLP
+#undef ATOM_ABLQ
+  return false;
+}
+#endif
+
+// BF6 operands, geometry `cfg` (F6Cfg, common.h), all on 16x16x128 MFMA micro-tiles.  Where a geometry does not take the operands the
+// next one down does, in the same K order: mid-size -> 256x128 -> 128x128; anything that is none of the four below is 256x256.
 int launch_gemm_f6(const GemmParams &p, int cfg, hipStream_t s) {
 #ifdef ATOM_TOOLS
-  if (cfg == 116) {   // traced run (tools/trace_f6.cpp): the stamp buffer arrives in ATOM_TRACE_PTR
-    const char *e = getenv("ATOM_TRACE_PTR");
-    if (!e) return ATOM_ERR_INVALID_ARG;
-    GemmParams q = p;
-    q.Dsz = reinterpret_cast<half_t *>(strtoull(e, nullptr, 16));
-    return f6::launch<f6::Cfg<256, 256, 4, 3>, false, 16>(q, s);
-  }
-  switch (cfg) {   // tools/gemm_bench only: 100 + ablation mask on the 256x256 geometry
-#define ATOM_ABL(a) case 100 + a: return f6::launch<f6::Cfg<256, 256, 4, 3>, false, a>(p, s);
-    ATOM_ABL(1) ATOM_ABL(2) ATOM_ABL(3) ATOM_ABL(4) ATOM_ABL(6) ATOM_ABL(7) ATOM_ABL(8) ATOM_ABL(10) ATOM_ABL(14) ATOM_ABL(15) ATOM_ABL(32)
-#undef ATOM_ABL
-  }
-  if (cfg == 1005 || cfg == 1009) {   // traced run of the two-K-group kernels (tools/trace_f6kg.cpp)
-    const char *e = getenv("ATOM_TRACE_PTR");
-    if (!e || !p.sB32) return ATOM_ERR_INVALID_ARG;
-    GemmParams q = p;
-    q.Dsz = reinterpret_cast<half_t *>(strtoull(e, nullptr, 16));
-    if (cfg == 1005) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, false, 2, false, true>(q, s);
-    return f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 1>, false, 2, false, true>(q, s);
-  }
-  switch (cfg) {   // 2100 + ablation mask on the two-K-group q-step kernel
-#define ATOM_ABL(a) case 2100 + a: return p.sB32 ? f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>, false, a>(p, s) : ATOM_ERR_INVALID_ARG;
-    ATOM_ABL(0) ATOM_ABL(1) ATOM_ABL(2) ATOM_ABL(4) ATOM_ABL(8) ATOM_ABL(16) ATOM_ABL(17) ATOM_ABL(6) ATOM_ABL(14) ATOM_ABL(15) ATOM_ABL(31)
-    ATOM_ABL(3) ATOM_ABL(5) ATOM_ABL(9) ATOM_ABL(7) ATOM_ABL(11) ATOM_ABL(13)
-#undef ATOM_ABL
-  }
-  if (cfg == 2017) {   // traced run of the two-K-group q-step kernel (tools/trace_f6q.cpp qk)
-    const char *e = getenv("ATOM_TRACE_PTR");
-    if (!e || !p.sB32) return ATOM_ERR_INVALID_ARG;
-    GemmParams q = p;
-    q.Dsz = reinterpret_cast<half_t *>(strtoull(e, nullptr, 16));
-    return f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>, true>(q, s);
-  }
-  if (cfg == 2016) {   // traced run of the q kernel (tools/trace_f6q.cpp)
-    const char *e = getenv("ATOM_TRACE_PTR");
-    if (!e || !p.sB32) return ATOM_ERR_INVALID_ARG;
-    GemmParams q = p;
-    q.Dsz = reinterpret_cast<half_t *>(strtoull(e, nullptr, 16));
-    return f6::launch_q<f6::Cfg<256, 256, 4, 3>, 0, true>(q, s);
-  }
-  if (cfg == 1016) {   // traced run of the pipelined kernel (tools/trace_f6.cpp)
-    const char *e = getenv("ATOM_TRACE_PTR");
-    if (!e) return ATOM_ERR_INVALID_ARG;
-    GemmParams q = p;
-    q.Dsz = reinterpret_cast<half_t *>(strtoull(e, nullptr, 16));
-    return f6::launch_p<f6::Cfg<256, 256, 4, 3>, 16>(q, s);
-  }
-  switch (cfg) {   // 1000 + ablation mask on the pipelined kernel
-#define ATOM_ABL(a) case 1000 + a: return f6::launch_p<f6::Cfg<256, 256, 4, 3>, a>(p, s);
-    ATOM_ABL(1) ATOM_ABL(2) ATOM_ABL(3) ATOM_ABL(4) ATOM_ABL(6) ATOM_ABL(7) ATOM_ABL(8) ATOM_ABL(10) ATOM_ABL(14) ATOM_ABL(15)
-    ATOM_ABL(64) ATOM_ABL(128) ATOM_ABL(192) ATOM_ABL(207) ATOM_ABL(256) ATOM_ABL(257) ATOM_ABL(512) ATOM_ABL(513) ATOM_ABL(768) ATOM_ABL(769)
-    ATOM_ABL(520) ATOM_ABL(9) ATOM_ABL(1024) ATOM_ABL(2048) ATOM_ABL(4096)
-#undef ATOM_ABL
-  }
+  int st;
+  if (launch_gemm_f6_tools(p, cfg, s, st)) return st;
 #endif
-#ifdef ATOM_TOOLS   // geometries no shape is dispatched to (f6_pick_cfg): tuning builds only
-  if (cfg == 2) {
-    if (p.splits > 1 && p.ws) return f6::launch<f6::Cfg<64, 128, 2, 3>, true>(p, s);
-    return f6::launch<f6::Cfg<64, 128, 2, 3>, false>(p, s);
+  if (cfg == F6_MID) {                                       // 64x64 tiles on a deep LDS ring (gemm_w4a4_mid.hip)
+    const int r = launch_gemm_f6_mid(p, s);
+    if (r != ATOM_ERR_SHAPE) return r;
+    cfg = F6_128x128;
   }
-  if (cfg == 10) return f6::launch<f6::Cfg<256, 256, 4, 3>, false>(p, s);   // tuning: 256x256 on the 32x32x64 MFMA
-  if (cfg == 1) return f6::launch<f6::Cfg<256, 128, 4, 2>, false>(p, s);
-  if (cfg == 13) return f6::launch<f6::Cfg<128, 128, 2, 2, 3>, false>(p, s);  // tuning: 128x128 on the 32x32x64 MFMA
-#endif
-  if (cfg == 20) {                                                             // mid-size batches: 64x64 tiles on a deep LDS ring (gemm_w4a4_mid.hip)
-    const int st = launch_gemm_f6_mid(p, s);
-    if (st != ATOM_ERR_SHAPE) return st;
-    cfg = 3;
-  }
-  if (cfg == 8) {                                                              // 256x128, qk_step, K steps in order
+  if (cfg == F6_256x128) {                                   // qk_step, K steps in order; fp16 weight scales: the 128x128 geometry
     if (p.sB32 && p.G >= 2) return f6::launch_q2<f6::Cfg<256, 128, 2, 3, 2, 1>>(p, s);
-    cfg = 3;                                                                   // fp16 weight scales: the 128x128 geometry (same order)
+    cfg = F6_128x128;
   }
-  if (cfg == 3) {                                                              // 128x128, 4 waves
-    // float32 weight scales staged (ATOM_B_F6S): 8 % fewer cycles per tile, but 54,272 B of LDS = two workgroups per CU (the LDS
-    // granule makes it 55,040); fp16 scales staged and converted once per step: 53,760 B = three.  The former unless the third
-    // workgroup saves a round of tiles (profiles/r02_mid_m.txt: 1536x4096x4096 37.7 vs 40.9 us, 1024x11008x4096 64.7 vs 55.4).
-    const int64_t t128 = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if (p.sB32 && (t128 + 511) / 512 <= (t128 + 767) / 768) {
-#ifdef ATOM_TOOLS
-      if (p.splits > 1 && p.ws) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, true>(p, s);
-#endif
-      return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>>(p, s);
-    }
-#ifdef ATOM_TOOLS
-    if (p.splits > 1 && p.ws) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>, true>(p, s);
-#endif
-    return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>>(p, s);
-  }
-  // two K groups of 4 waves per workgroup: for shapes that put at most one tile on a CU (f6_pick_cfg)
-#ifdef ATOM_TOOLS
-  if (cfg == 5) {                                                              // tuning: 128x128, two K groups, 2 stages per group
-    if (p.sB32) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, false, 2>(p, s);
-    return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>, false, 2>(p, s);
-  }
-#endif
-  if (cfg == 6) {                                                              // 128x128, two K groups, 3 stages per group
+  if (cfg == F6_128x128)                                     // 4 waves
+    return f6_128_f32_scales(p) ? f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>>(p, s) : f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>>(p, s);
+  if (cfg == F6_128x128_KG2) {                               // two K groups of 4 waves, 3 stages per group: at most one tile per CU
     // float32 weight scales (ATOM_B_F6S) and a K long enough for its unrolled loop: the q kernel's K step per group (same sums)
     if (p.sB32 && p.G >= 7 && ATOM_TUNE("ATOM_QK", 1)) return f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>>(p, s);
     if (p.sB32) return f6::launch_x16<f6::Cfg<128, 128, 2, 3, 3, 1>, false, 2>(p, s);
     return f6::launch_x16<f6::Cfg<128, 128, 2, 3, 3, 2>, false, 2>(p, s);
   }
-#ifdef ATOM_TOOLS   // the 64x128 K-group kernels of rounds 2-4: no shape is dispatched to them since the mid-size-batch kernel (cfg 20)
-  if (cfg == 9) {                                                              // 64x128 (32-token wave tiles), groups half a step apart
-    if (p.sB32) return f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 1>, false, 2, true>(p, s);
-    return f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 2>, false, 2, true>(p, s);
-  }
-  if (cfg == 12) {                                                             // 64x128, four K groups of 4 waves (exactly 160 KiB of LDS)
-    if (p.sB32) return f6::launch_x16<f6::Cfg<64, 128, 1, 2, 4, 1>, false, 4>(p, s);
-    return f6::launch_x16<f6::Cfg<64, 128, 1, 2, 4, 2>, false, 4>(p, s);
-  }
-#endif
-#ifdef ATOM_TOOLS   // tuning builds only
-  if (cfg == 51 && p.sB32) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>>(p, s);   // tuning: the two scale forms of cfg 3
-  if (cfg == 52) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 2>>(p, s);
-  if (cfg == 53) return f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3>>(p, s);            // tuning: cfg 3 with fp16 weight scales
-  if (cfg == 40) return f6::launch_x16<f6::Cfg<256, 256, 4, 3>>(p, s);        // tuning: 256x256, first-generation micro-tile kernel
-  // round 6, VERDICT r05 missing #1: the SAME kernel body as 8 waves of 64 features x 128 tokens (two per SIMD, 256 registers) and as
-  // 16 waves of 64 x 64 (four per SIMD, 128 registers) -- the same-code A/B behind profiles/r06/ab_16wave.txt
-  if (cfg == 41 && p.sB32) return f6::launch_x16<f6::Cfg<256, 256, 4, 3, 2, 1>>(p, s);
-  if (cfg == 42 && p.sB32) return f6::launch_x16<f6::Cfg<256, 256, 2, 3, 4, 1>>(p, s);
-  if (cfg == 4) {                                                              // 128x128, 8 waves of 64 features x 32 tokens
-    if (p.splits > 1 && p.ws) return f6::launch_x16<f6::Cfg<128, 128, 1, 2, 3>, true>(p, s);
-    return f6::launch_x16<f6::Cfg<128, 128, 1, 2, 3>>(p, s);
-  }
-#endif
-  if (!p.sB32 || cfg == 30) return f6::launch_p<f6::Cfg<256, 256, 4, 3>>(p, s);   // 256x256, pipelined across K steps (fp16 weight scales; cfg 30: tuning)
+  if (!p.sB32) return f6::launch_p<f6::Cfg<256, 256, 4, 3>>(p, s);                      // 256x256, pipelined across K steps (fp16 weight scales)
   if (p.b_pairs) return f6::launch_q<f6::Cfg<256, 256, 4, 3>, 0, false, true>(p, s);   // ... third generation (ATOM_B_F6S; the headline), shared scale products
-  return f6::launch_q<f6::Cfg<256, 256, 4, 3>>(p, s);                          // ... the same for weights whose channel pairs have their own scales
+  return f6::launch_q<f6::Cfg<256, 256, 4, 3>>(p, s);                                   // ... the same for weights whose channel pairs have their own scales
 }
 
 }  // namespace atom

@@ -557,34 +557,45 @@ __global__ __launch_bounds__(256) void o4_quant_kernel(const float *__restrict__
 
 }  // namespace skinny
 
-// 1 <= M <= 256 (<= 64 when K > 8192), reference packed format, K <= 14336.  ATOM_ERR_SHAPE when K is too long for the register-resident weight slice
-// (caller falls back to the tile kernels).
+// What every decode-batch launcher refuses with ATOM_ERR_SHAPE (the caller falls back to the tile kernels where it has any): more than
+// `max_m` tokens, an operand format other than the reference packed one (`packed_only`), N no multiple of 16, weight scales off the
+// 8-byte loads, K too long for the register-resident weight slice (K <= 14336) -- and the instance by K items per wave, 8 waves
+// splitting K (measured: 4 waves with twice the slice are slower).  0: refused.
+static int skinny_cnt(const GemmParams &p, int max_m, bool packed_only, bool segmented = false) {
+  if (p.M > max_m || (packed_only && (p.a_wide || p.f6_rows_a)) || (p.N % 16) != 0) return 0;
+  if (segmented && (p.seg_n < 16 || (p.seg_n % 16) != 0 || (p.N % p.seg_n) != 0 || p.N / p.seg_n > 3)) return 0;   // one to three segments
+  if ((reinterpret_cast<uintptr_t>(p.sB) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p.sB8) & 7u) != 0) return 0;
+  const int per = (p.G + 1 + 7) / 8;
+  return per > skinny::CNT_MAX ? 0 : (per <= 4 ? 4 : (per <= 8 ? 8 : 14));
+}
+template <int OUT>
+static int launch_skinny_m(int cnt, const GemmParams &p, hipStream_t s) {
+  return cnt == 4 ? skinny::launch_m<8, 4, OUT>(p, s) : (cnt == 8 ? skinny::launch_m<8, 8, OUT>(p, s) : skinny::launch_m<8, 14, OUT>(p, s));
+}
+
+// fp16 output; 1 <= M <= 256 (<= 64 when K > 8192).  Alone in refusing an output off the 8-byte stores.
 int launch_gemm_skinny(const GemmParams &p, hipStream_t s) {
-  if (p.M > 256 || p.a_wide || p.f6_rows_a || (p.N % 16) != 0) return ATOM_ERR_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(p.D) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p.sB) & 7u) != 0 ||
-      (reinterpret_cast<uintptr_t>(p.sB8) & 7u) != 0)
-    return ATOM_ERR_SHAPE;                                 // 8-byte scale loads / stores: the tile kernels take these
-  const int per = (p.G + 1 + 7) / 8;                      // 8 waves split K (measured: 4 waves with twice the slice are slower)
-  if (per > skinny::CNT_MAX) return ATOM_ERR_SHAPE;
-  if (per <= 4) return skinny::launch_m<8, 4>(p, s);
-  return per <= 8 ? skinny::launch_m<8, 8>(p, s) : skinny::launch_m<8, 14>(p, s);
+  const int cnt = skinny_cnt(p, 256, true);
+  if (!cnt || (reinterpret_cast<uintptr_t>(p.D) & 7u) != 0) return ATOM_ERR_SHAPE;
+  return launch_skinny_m<0>(cnt, p, s);
 }
 
 // FP32 sums [M, N] into p.ws (no final rounding): the k / v projections of a decode step, ahead of the u4 epilogue.  Same
 // shapes as launch_gemm_skinny.
 int launch_gemm_skinny_f32(const GemmParams &p, hipStream_t s) {
-  if (p.M > 256 || p.a_wide || p.f6_rows_a || (p.N % 16) != 0 || !p.ws) return ATOM_ERR_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(p.sB) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p.sB8) & 7u) != 0) return ATOM_ERR_SHAPE;
-  const int per = (p.G + 1 + 7) / 8;
-  if (per > skinny::CNT_MAX) return ATOM_ERR_SHAPE;
-  return per <= 4 ? skinny::launch_m<8, 4, 1>(p, s)
-                  : (per <= 8 ? skinny::launch_m<8, 8, 1>(p, s) : skinny::launch_m<8, 14, 1>(p, s));
+  const int cnt = skinny_cnt(p, 256, true);
+  return cnt && p.ws ? launch_skinny_m<1>(cnt, p, s) : ATOM_ERR_SHAPE;
 }
 
 // Segmented outputs (atom_gemm_w4a4_multi): one launch for the projections that share an activation operand -- q / k / v, gate / up
 // -- or for one projection + the residual add.  Per-feature arithmetic and summation order are those of launch_gemm_skinny /
 // launch_gemm_skinny_f32 (a workgroup owns 16 features of ONE segment): bit-identical to the separate launches.
-// ... with the quantiser that precedes the GEMM inside the launch (p.q_op; 1 or 2 tokens)
+int launch_gemm_skinny_multi(const GemmParams &p, hipStream_t s) {
+  const int cnt = skinny_cnt(p, 256, true, true);
+  return cnt ? launch_skinny_m<2>(cnt, p, s) : ATOM_ERR_SHAPE;
+}
+
+// ... with the quantiser that precedes the GEMM inside the launch (p.q_op; 1 or 2 tokens; the activation operand does not exist)
 // THE shape predicate of the quantiser-in-front launch, shared by atom_gemm_w4a4_multi_q_fits and the launcher (round 3 had two, and the
 // query was looser than the launch for ops 1-3): per thread of the 512 at most 2 slot tasks of 16 channels (SiLU x up: 3), at most 3
 // 16-byte chunks of the token rows and 2 of the norm weight (ops 1-3), and everything within 96 KiB of LDS.
@@ -598,23 +609,9 @@ bool skinny_q_fits(int q_op, int64_t M, int64_t H) {
 }
 
 int launch_gemm_skinny_multi_q(const GemmParams &p, hipStream_t s) {
-  if (p.M > 2 || p.q_op < 1 || p.q_op > 4 || (p.N % 16) != 0 || p.seg_n < 16 || (p.seg_n % 16) != 0 || (p.N % p.seg_n) != 0 || p.N / p.seg_n > 3)
-    return ATOM_ERR_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(p.sB) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p.sB8) & 7u) != 0) return ATOM_ERR_SHAPE;
-  const int per = (p.G + 1 + 7) / 8;
-  if (per > skinny::CNT_MAX) return ATOM_ERR_SHAPE;
-  return per <= 4 ? skinny::launch_q<8, 4, 2>(p, s) : (per <= 8 ? skinny::launch_q<8, 8, 2>(p, s) : skinny::launch_q<8, 14, 2>(p, s));
-}
-
-int launch_gemm_skinny_multi(const GemmParams &p, hipStream_t s) {
-  if (p.M > 256 || p.a_wide || p.f6_rows_a || (p.N % 16) != 0 || p.seg_n < 16 || (p.seg_n % 16) != 0 || (p.N % p.seg_n) != 0 ||
-      p.N / p.seg_n > 3)
-    return ATOM_ERR_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(p.sB) & 7u) != 0 || (reinterpret_cast<uintptr_t>(p.sB8) & 7u) != 0) return ATOM_ERR_SHAPE;
-  const int per = (p.G + 1 + 7) / 8;
-  if (per > skinny::CNT_MAX) return ATOM_ERR_SHAPE;
-  return per <= 4 ? skinny::launch_m<8, 4, 2>(p, s)
-                  : (per <= 8 ? skinny::launch_m<8, 8, 2>(p, s) : skinny::launch_m<8, 14, 2>(p, s));
+  const int cnt = skinny_cnt(p, 2, false, true);
+  if (!cnt || p.q_op < 1 || p.q_op > 4) return ATOM_ERR_SHAPE;
+  return cnt == 4 ? skinny::launch_q<8, 4, 2>(p, s) : (cnt == 8 ? skinny::launch_q<8, 8, 2>(p, s) : skinny::launch_q<8, 14, 2>(p, s));
 }
 
 // Decode path of the u4-output GEMM: the FP32 sums into the caller's workspace, then the u4 epilogue as a second launch
