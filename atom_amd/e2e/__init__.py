@@ -3,3 +3,4 @@
 from .llama import (LinearInt4, LlamaAttention, LlamaDecoderLayer, LlamaForCausalLM, LlamaMLP, LlamaModel,  # noqa: F401
                     LlamaRMSNorm, LlamaRMSNormInt4)
 from .generate import DecodeGraph, generate  # noqa: F401
+from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4  # noqa: F401

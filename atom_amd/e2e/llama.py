@@ -497,13 +497,16 @@ class LlamaModel(nn.Module):
     """reference llama.py:306-340: embedding -> decoder layers -> final norm over a flat [tokens, hidden] batch (prefill requests
     first, then one row per decode request).  Plain ``nn.Module`` (the reference derives from transformers' PreTrainedModel only for
     ``from_pretrained``; here ``load_state_dict(model.export.load_packed(path))`` fills it) and every layer gets its own
-    ``layer_idx`` (the reference passes 0 to all of them, "Hack for memory", :313-314)."""
+    ``layer_idx`` (the reference passes 0 to all of them, "Hack for memory", :313-314).  ``layer_class``: the decoder layer a subclass
+    stacks instead (e2e/mixtral.py)."""
+
+    layer_class = LlamaDecoderLayer
 
     def __init__(self, config):
         super().__init__()
         self.config = config
         self.embed_tokens = nn.Embedding(config.vocab_size, config.hidden_size, getattr(config, "pad_token_id", None), dtype=torch.float16)
-        self.layers = nn.ModuleList([LlamaDecoderLayer(config, i) for i in range(config.num_hidden_layers)])
+        self.layers = nn.ModuleList([self.layer_class(config, i) for i in range(config.num_hidden_layers)])
         self.norm = LlamaRMSNorm(config.hidden_size, eps=config.rms_norm_eps)
 
     @torch.no_grad()
@@ -515,12 +518,14 @@ class LlamaModel(nn.Module):
 
 
 class LlamaForCausalLM(nn.Module):
-    """reference llama.py:343-364: returns (logits, hidden_states)."""
+    """reference llama.py:343-364: returns (logits, hidden_states).  ``model_class``: the body a subclass puts under the head."""
+
+    model_class = LlamaModel
 
     def __init__(self, config):
         super().__init__()
         self.config = config
-        self.model = LlamaModel(config)
+        self.model = self.model_class(config)
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False, dtype=torch.float16)
 
     @torch.no_grad()

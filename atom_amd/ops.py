@@ -857,3 +857,88 @@ def gate_up_silu_quant_f6(a6, a_keeper, a_keeper_scale, fused, *, quant_mode="ke
                                                   L.current_stream(a6.device))
     L.check(st, "atom_gemm_w4a4_silu_mul_quant_f6")
     return _ret(*outs)
+
+
+# ------------------------------------------------------------------------------------------------ sparse mixture of experts
+class MoeRoute:
+    """The device tables of atom_moe_route_topk (include/atom_hip.h) for T tokens, E experts and top_k slots per token."""
+    __slots__ = ("tokens", "experts", "top_k", "topk_ids", "topk_w", "expert_indptr", "row_token", "slot_row", "tile_expert",
+                 "tile_row0", "n_tiles")
+
+    def __init__(self, tokens, experts, top_k, **tables):
+        self.tokens, self.experts, self.top_k = int(tokens), int(experts), int(top_k)
+        for k, v in tables.items():
+            setattr(self, k, v)
+
+    @property
+    def rows(self) -> int:
+        return self.tokens * self.top_k
+
+
+def moe_max_tiles(rows: int, experts: int) -> int:
+    """Upper bound of the tile count for any routing of ``rows`` routed rows over ``experts`` experts (64-row tiles)."""
+    return int(L.lib().atom_moe_max_tiles(int(rows), int(experts)))
+
+
+def moe_route_topk(logits: torch.Tensor, top_k: int) -> MoeRoute:
+    """Router of a sparse MoE block in ONE launch, nothing read back: the top_k experts per token (largest logit first, the lower
+    index on equal logits), their renormalised softmax weights (fp16), and the tables the routed GEMM and the combine read -- rows
+    grouped by expert in ascending token order.  Reference: model/qMixtralLayer.py:313-317 + the expert mask of :321-341."""
+    _require_cuda_half(logits, "logits")
+    t, e = logits.shape
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=logits.device)
+    mt = moe_max_tiles(t * top_k, e)
+    r = MoeRoute(t, e, top_k, topk_ids=i32(t, top_k), topk_w=torch.empty((t, top_k), dtype=torch.float16, device=logits.device),
+                 expert_indptr=i32(e + 1), row_token=i32(t * top_k), slot_row=i32(t, top_k), tile_expert=i32(max(mt, 1)),
+                 tile_row0=i32(max(mt, 1)), n_tiles=i32(1))
+    st = L.lib().atom_moe_route_topk(logits.data_ptr(), t, e, int(top_k), r.topk_ids.data_ptr(), r.topk_w.data_ptr(),
+                                     r.expert_indptr.data_ptr(), r.row_token.data_ptr(), r.slot_row.data_ptr(),
+                                     r.tile_expert.data_ptr(), r.tile_row0.data_ptr(), r.n_tiles.data_ptr(),
+                                     L.current_stream(logits.device))
+    L.check(st, "atom_moe_route_topk")
+    return r
+
+
+def moe_gemm_i4(a, a_scale, a_keeper, a_keeper_scale, experts, route: MoeRoute, *, gather: bool, nseg=1, scale_layout="ref"):
+    """The routed GEMM: every routed row of ``route`` times ITS expert's weight, one launch for all experts.  ``experts`` = (b4 u8
+    [E, N, K4/2], b8 i8 [E, N, 128], sb f16 [E, G, N], sb8 f16 [E, N]) stacked packed weights; ``gather=True``: ``a`` holds one
+    quantised row per TOKEN (and so do the scales) and row r reads token route.row_token[r]; ``gather=False``: ``a`` holds the routed
+    rows themselves.  Returns ``nseg`` (1 or 2) tensors fp16 [rows, N / nseg] -- gate and up of one launch.  Bit-identical to
+    dense_layer_gemm_i4_fp16's tile kernels on each expert's rows."""
+    b4, b8, sb, sb8 = experts
+    for t in (a, a_scale, a_keeper, a_keeper_scale, b4, b8, sb, sb8):
+        if not t.is_cuda:
+            raise L.AtomHipError("all GEMM operands must live on the GPU: no CPU fallback")
+        if not t.is_contiguous():
+            raise ValueError("routed GEMM operands must be contiguous")
+    e, n, k4h = b4.shape
+    a_rows, rows = a.size(0), route.rows
+    k = a.size(1) * 2 + a_keeper.size(1)
+    assert e == route.experts and a.size(1) == k4h and nseg in (1, 2) and n % nseg == 0
+    assert a_rows == (route.tokens if gather else rows)
+    n_seg = n // nseg
+    outs = [torch.empty((rows, n_seg), dtype=torch.float16, device=a.device) for _ in range(nseg)]
+    st = L.lib().atom_moe_gemm_w4a4_f16(a.data_ptr(), b4.data_ptr(), a_scale.data_ptr(), sb.data_ptr(), a_keeper.data_ptr(), b8.data_ptr(),
+                                        a_keeper_scale.data_ptr(), sb8.data_ptr(), route.row_token.data_ptr() if gather else None,
+                                        route.expert_indptr.data_ptr(), route.tile_expert.data_ptr(), route.tile_row0.data_ptr(),
+                                        route.n_tiles.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr() if nseg > 1 else None,
+                                        a_rows, rows, e, n_seg, nseg, k, GROUP_SIZE, GROUP_SIZE, _LAYOUTS[scale_layout],
+                                        L.current_stream(a.device))
+    L.check(st, "atom_moe_gemm_w4a4_f16")
+    return tuple(outs)
+
+
+def moe_combine(y: torch.Tensor, route: MoeRoute, residual: torch.Tensor = None) -> torch.Tensor:
+    """out[t] = residual[t] + sum over token t's slots, in ascending expert id, of half(y[slot_row[t, k]] * topk_w[t, k]) -- fp16
+    adds into a zero accumulator, the residual last (reference qMixtralLayer.py:344-348, :434)."""
+    _require_cuda_half(y, "y")
+    rows, h = y.shape
+    assert rows == route.rows
+    if residual is not None:
+        _require_cuda_half(residual, "residual")
+        assert residual.shape == (route.tokens, h)
+    out = torch.empty((route.tokens, h), dtype=torch.float16, device=y.device)
+    st = L.lib().atom_moe_combine_f16(y.data_ptr(), route.slot_row.data_ptr(), route.topk_ids.data_ptr(), route.topk_w.data_ptr(),
+                                      L.ptr(residual), out.data_ptr(), route.tokens, route.top_k, h, L.current_stream(y.device))
+    L.check(st, "atom_moe_combine_f16")
+    return out

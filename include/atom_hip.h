@@ -559,6 +559,55 @@ int atom_gemm_w4a4_silu_mul_quant_f6(const void *A_f6, const void *Bgu_f6s, cons
                                      int quant_mode, float clip, int scale_layout, void *o_outliers, void *o_norms_f6,
                                      void *outlier_scales, void *norm_scales, void *xq, void *stream);
 
+/*
+ * Sparse mixture of experts (Mixtral) on the W4A4 path -- csrc/moe_w4a4.hip; no reference kernels: the reference runs the block as a
+ * Python loop over the experts with a host read per expert (model/qMixtralLayer.py:302-350).  Three launches with no host work between
+ * them.  T tokens, E experts, R = T * top_k routed rows.
+ *
+ * atom_moe_route_topk: the routing tables of logits fp16 [T, E] in ONE launch (one workgroup), all outputs on the device:
+ *   topk_ids      int32 [T, top_k]  the experts with the top_k largest logits, largest first; of equal logits the LOWER expert index wins
+ *   topk_w        fp16  [T, top_k]  w_k = exp(l_k - l_max) / sum_{j selected} exp(l_j - l_max) in FP32, rounded to fp16 (= softmax, topk,
+ *                                   renormalise, .to(half) of qMixtralLayer.py:313-317: the full softmax's denominator cancels)
+ *   expert_indptr int32 [E + 1]     rows per expert, prefix-summed
+ *   row_token     int32 [R]         the token of each routed row: rows grouped by expert, ascending token order within an expert --
+ *                                   by construction (ballot ranks and prefix sums), never by the order of atomics
+ *   slot_row      int32 [T, top_k]  the row that holds slot (t, k)
+ *   tile_expert, tile_row0 int32 [atom_moe_max_tiles(R, E)]  the tile table: for each expert in order, one tile per started 64 rows
+ *                                   (entries from n_tiles on are not written)
+ *   n_tiles       int32 [1]
+ * atom_moe_max_tiles(R, E) = R / 64 + min(E, R) bounds n_tiles for any routing (host function).
+ * Errors: ATOM_ERR_INVALID_ARG for a null pointer; ATOM_ERR_SHAPE unless 2 <= E <= 64, 1 <= top_k <= min(8, E), T >= 1, R < 2^31;
+ * ATOM_ERR_ALIGN for a table that is not 4-byte aligned.
+ *
+ * atom_moe_gemm_w4a4_f16: the routed ("grouped") GEMM.  For every routed row r of expert e (expert_indptr[e] <= r < expert_indptr[e+1])
+ * and feature n:  D[r, n] = contract(A[row_index ? row_index[r] : r], B_e[n])  with exactly the arithmetic of atom_gemm_w4a4_f16 in
+ * tile-kernel order (atom_gemm_w4a4_packed_order == 1): bit-identical to that entry point on the expert's gathered rows, whatever tile
+ * a row lands in.  Packed reference format only: A4 uint8 [A_rows, K4/2], A8 int8 [A_rows, 128], sA / sA8 per `scale_layout` (REF or
+ * PLAIN) over A_rows rows and indexed by the SOURCE row (the gather applies to the scales too); stacked weights B4 uint8 [E, N, K4/2],
+ * B8 int8 [E, N, 128], sB fp16 [E, G, N], sB8 fp16 [E, N]; row_index int32 [R] (values in 0 .. A_rows - 1) or NULL = the identity; the
+ * tables of atom_moe_route_topk (or any tables of that form).  N = nseg * N_seg features (nseg 1 or 2): segment s goes to its own
+ * contiguous out_s fp16 [R, N_seg] (gate and up of one launch, ready for atom_silu_mul_quant_f16).  Rows >= R of the outputs are never
+ * written.  Grid: atom_moe_max_tiles(R, E) * (N / 64) workgroups, sized on the host from R alone; workgroups beyond *n_tiles leave
+ * before touching memory.  64 x 64 tiles over the whole K range (the kernel of gemm_w4a4_mid.hip with the tile looked up).
+ * Constraints: N_seg % 64 == 0, K_total as atom_gemm_w4a4_f16, 1 <= E <= 64, 1 <= R < 2^31, A_rows * K4/2 < 2^32 and N * K4/2 < 2^32
+ * (32-bit lane offsets); ATOM_ERR_SHAPE otherwise; null pointers / a bad layout ATOM_ERR_INVALID_ARG; ATOM_ERR_ALIGN as there.
+ *
+ * atom_moe_combine_f16: out[t, :] = residual[t, :] + sum_k half(y[slot_row[t, k], :] * topk_w[t, k]), y fp16 [R, H]: the slots of a
+ * token are added in ASCENDING EXPERT ID into an fp16 accumulator that starts at zero, every add as torch adds two half tensors --
+ * half(float(a) + float(b)) --, the residual last (NULL: none): expert(x) * routing_weight, index_add_ into zeros in expert order,
+ * residual + hidden of qMixtralLayer.py:344-348, :434.  H % 8 == 0 (16-byte loads and stores), top_k <= 8.
+ */
+int64_t atom_moe_max_tiles(int64_t R, int E);
+int atom_moe_route_topk(const void *logits, int64_t T, int E, int top_k, int32_t *topk_ids, void *topk_w, int32_t *expert_indptr,
+                        int32_t *row_token, int32_t *slot_row, int32_t *tile_expert, int32_t *tile_row0, int32_t *n_tiles, void *stream);
+int atom_moe_gemm_w4a4_f16(const void *A4, const void *B4, const void *sA, const void *sB, const void *A8, const void *B8,
+                           const void *sA8, const void *sB8, const int32_t *row_index, const int32_t *expert_indptr,
+                           const int32_t *tile_expert, const int32_t *tile_row0, const int32_t *n_tiles, void *out0, void *out1,
+                           int64_t A_rows, int64_t R, int E, int64_t N_seg, int nseg, int64_t K_total, int group, int keeper,
+                           int scale_layout, void *stream);
+int atom_moe_combine_f16(const void *y, const int32_t *slot_row, const int32_t *topk_ids, const void *topk_w, const void *residual,
+                         void *out, int64_t T, int top_k, int64_t H, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
