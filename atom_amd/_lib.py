@@ -94,6 +94,9 @@ SIGNATURES = {
     "atom_moe_route_topk": (_int, [_vp, _i64, _int, _int] + [_vp] * 9),
     "atom_moe_gemm_w4a4_f16": (_int, [_vp] * 15 + [_i64, _i64, _int, _i64, _int, _i64, _int, _int, _int, _vp]),
     "atom_moe_combine_f16": (_int, [_vp] * 6 + [_i64, _int, _i64, _vp]),
+    "atom_bgmv_f16": (_int, [_vp] * 5 + [_i64] * 7 + [_f32, _vp]),
+    "atom_add_lora_f16": (_int, [_vp] * 7 + [_i64] * 8 + [_f32, _vp]),
+    "atom_kv_quant_u4_f16": (_int, [_vp] * 3 + [_i64, _int, _int, _vp]),
 }
 
 _lib = None

@@ -11,6 +11,30 @@ namespace atom {
 constexpr int kHeadDim = 128;
 constexpr float kLog2e = 1.4426950408889634f;
 
+// the u4 epilogue on one 128-value head vector held by 32 lanes (4 values each; both halves of a wave at once): returns the lane's four
+// codes as 16 bits and the vector's (scale, zero) as a half2 bit pattern -- what the cache stores
+__device__ __forceinline__ unsigned short quant_head_u4(const v4f &x, unsigned &sz) {
+  float lo = fminf(fminf(x[0], x[1]), fminf(x[2], x[3])), hi = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+#pragma unroll
+  for (int k = 16; k >= 1; k >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, k));
+    hi = fmaxf(hi, __shfl_xor(hi, k));
+  }
+  const float scale = (hi - lo) / 15.f, zero = -lo, rs = 1.0f / scale;
+  unsigned w = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float t = (x[k] + zero) * rs;
+    float tr = truncf(t);
+    if (fabsf(t - tr) >= 0.5f) tr += copysignf(1.0f, t);
+    tr = fminf(fmaxf(tr, 0.f), 15.f);
+    if (scale == 0.f) tr = 0.f;
+    w |= (unsigned)(int)tr << (4 * k);
+  }
+  sz = (unsigned)__builtin_bit_cast(unsigned short, f2h(scale)) | ((unsigned)__builtin_bit_cast(unsigned short, f2h(zero)) << 16);
+  return (unsigned short)w;
+}
+
 // out[b,h,:] = sum_s o_s * 2^(m_s - M) / sum_s d_s * 2^(m_s - M)
 // Round 6: every split's (value, m, d) is requested before the first one is used -- in batches of 8 splits with compile-time bounds.
 // The partial states were written by waves on other XCDs, so each request is a trip to memory (~1.5 us): the two run-time loops of

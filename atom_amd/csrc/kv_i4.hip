@@ -95,30 +95,7 @@ struct QuantAppendParams {
 
 // Half a wave per (sequence, K / V, head) vector; the grid covers them all at once.  (Round 2 ran one workgroup per SEQUENCE that
 // walked its 2 N head vectors eight at a time: 5.6 us at batch 1 -- a chain of 8 dependent round trips on one CU.)
-// the u4 epilogue on one 128-value head vector held by 32 lanes (4 values each; both halves of a wave at once): returns the lane's four
-// codes as 16 bits and the vector's (scale, zero) as a half2 bit pattern -- what the cache stores
-__device__ __forceinline__ unsigned short quant_head_u4(const v4f &x, unsigned &sz) {
-  float lo = fminf(fminf(x[0], x[1]), fminf(x[2], x[3])), hi = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
-#pragma unroll
-  for (int k = 16; k >= 1; k >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, k));
-    hi = fmaxf(hi, __shfl_xor(hi, k));
-  }
-  const float scale = (hi - lo) / 15.f, zero = -lo, rs = 1.0f / scale;
-  unsigned w = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float t = (x[k] + zero) * rs;
-    float tr = truncf(t);
-    if (fabsf(t - tr) >= 0.5f) tr += copysignf(1.0f, t);
-    tr = fminf(fmaxf(tr, 0.f), 15.f);
-    if (scale == 0.f) tr = 0.f;
-    w |= (unsigned)(int)tr << (4 * k);
-  }
-  sz = (unsigned)__builtin_bit_cast(unsigned short, f2h(scale)) | ((unsigned)__builtin_bit_cast(unsigned short, f2h(zero)) << 16);
-  return (unsigned short)w;
-}
-
+// (the u4 epilogue on a head vector: quant_head_u4, kv_attn.h)
 __global__ __launch_bounds__(256) void kv_quant_append_kernel(QuantAppendParams p) {
   const int l = threadIdx.x & 31;
   const int P = p.kv.P, N = p.kv.N;

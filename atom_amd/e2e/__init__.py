@@ -4,3 +4,4 @@ from .llama import (LinearInt4, LlamaAttention, LlamaDecoderLayer, LlamaForCausa
                     LlamaRMSNorm, LlamaRMSNormInt4)
 from .generate import DecodeGraph, generate  # noqa: F401
 from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4  # noqa: F401
+from .llama_lora import LlamaDecoderLayerWithLora, LlamaForCausalLMWithLora, LlamaModelWithLora  # noqa: F401

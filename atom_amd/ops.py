@@ -942,3 +942,68 @@ def moe_combine(y: torch.Tensor, route: MoeRoute, residual: torch.Tensor = None)
                                       L.ptr(residual), out.data_ptr(), route.tokens, route.top_k, h, L.current_stream(y.device))
     L.check(st, "atom_moe_combine_f16")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ multi-adapter LoRA (fp16)
+def _lora_tables(y, x, indicies, seg_indptr):
+    """(int32 ids, S, seg_indptr) of a LoRA op: one id per row, or one per segment of ``seg_indptr`` (int32 [S + 1], on the device)."""
+    _require_cuda_half(y, "y")
+    _require_cuda_half(x, "x")
+    if not indicies.is_cuda:
+        raise L.AtomHipError("indicies must live on the GPU: the LoRA ops have no CPU fallback")
+    if indicies.dtype not in (torch.int32, torch.int64) or indicies.dim() != 1:
+        raise TypeError(f"indicies must be a 1-d int32 or int64 tensor, got {indicies.dtype} {tuple(indicies.shape)}")
+    ids = indicies.contiguous() if indicies.dtype == torch.int32 else indicies.to(torch.int32)   # (a launch, not a host read)
+    assert x.dim() == 2 and y.dim() == 2 and x.size(0) == y.size(0)
+    if seg_indptr is None:
+        assert ids.numel() == x.size(0), "one adapter id per row"
+    else:
+        assert seg_indptr.is_cuda and seg_indptr.dtype == torch.int32 and seg_indptr.is_contiguous()
+        assert seg_indptr.numel() == ids.numel() + 1, "one adapter id per segment"
+    return ids, ids.numel()
+
+
+def bgmv(y: torch.Tensor, x: torch.Tensor, w_T_all: torch.Tensor, indicies: torch.Tensor, layer_idx: int, scale: float, *,
+         seg_indptr: torch.Tensor = None):
+    """Reference punica/ops/__init__.py:62-91: ``y[i] += scale * x[i] @ w_T_all[indicies[i], layer_idx].T`` in place, FP32 sums and one
+    rounding.  y fp16 [B, H2], x fp16 [B, H1], w_T_all fp16 [capacity, L, H2, H1], indicies int64 or int32 [B]; an id of -1 (any id
+    outside 0 .. capacity - 1) leaves its rows untouched.  ``seg_indptr`` (int32 [S + 1], device): ``indicies`` holds one id per
+    SEGMENT of rows seg_indptr[s] .. seg_indptr[s + 1] - 1 (a prefill request), and rows from seg_indptr[S] on are not written.
+    One of H1, H2 is the rank (a multiple of 8 in 8 .. 64), the other a multiple of 64."""
+    ids, s = _lora_tables(y, x, indicies, seg_indptr)
+    _require_cuda_half(w_T_all, "w_T_all")
+    cap, nl, h2, h1 = w_T_all.shape
+    assert x.size(1) == h1 and y.size(1) == h2
+    st = L.lib().atom_bgmv_f16(y.data_ptr(), x.data_ptr(), w_T_all.data_ptr(), ids.data_ptr(), L.ptr(seg_indptr), x.size(0), s, h1, h2,
+                               cap, nl, int(layer_idx), float(scale), L.current_stream(y.device))
+    L.check(st, "atom_bgmv_f16")
+
+
+def add_lora(y: torch.Tensor, x: torch.Tensor, wa_T_all: torch.Tensor, wb_T_all: torch.Tensor, indicies: torch.Tensor, layer_idx: int,
+             scale: float, *, seg_indptr: torch.Tensor = None):
+    """Reference punica/ops/__init__.py:94-124: ``y[i] += scale * half(x[i] @ wa_T_all[id, layer_idx].T) @ wb_T_all[id, layer_idx].T`` in
+    place -- two bgmv passes, the rank-wide intermediate rounded to fp16 between them.  wa_T_all fp16 [capacity, L, r, H1], wb_T_all
+    fp16 [capacity, L, H2, r]; H1, H2 multiples of 64, r a multiple of 8 in 8 .. 64; ``indicies`` / ``seg_indptr`` as ``bgmv``."""
+    ids, s = _lora_tables(y, x, indicies, seg_indptr)
+    _require_cuda_half(wa_T_all, "wa_T_all")
+    _require_cuda_half(wb_T_all, "wb_T_all")
+    cap, nl, r, h1 = wa_T_all.shape
+    h2 = wb_T_all.size(2)
+    assert wb_T_all.shape == (cap, nl, h2, r) and x.size(1) == h1 and y.size(1) == h2
+    t = torch.empty((x.size(0), r), dtype=torch.float16, device=x.device)
+    st = L.lib().atom_add_lora_f16(y.data_ptr(), x.data_ptr(), wa_T_all.data_ptr(), wb_T_all.data_ptr(), ids.data_ptr(),
+                                   L.ptr(seg_indptr), t.data_ptr(), x.size(0), s, h1, h2, r, cap, nl, int(layer_idx), float(scale),
+                                   L.current_stream(y.device))
+    L.check(st, "atom_add_lora_f16")
+
+
+def kv_quant_u4(k: torch.Tensor):
+    """NEW: fp16 k (or v) [T, kv_heads, 128] -> (packed u8 [T, kv_heads, 64], params fp16 [T, kv_heads, 2]) in the form ``init_kv_i4`` /
+    ``append_kv_i4`` take: the per-head quantiser of ``quant_append_kv_i4`` applied to ``k.float()``, without a cache."""
+    _require_cuda_half(k, "k")
+    t, heads, d = k.shape
+    packed = torch.empty((t, heads, d // 2), dtype=torch.uint8, device=k.device)
+    params = torch.empty((t, heads, 2), dtype=torch.float16, device=k.device)
+    st = L.lib().atom_kv_quant_u4_f16(k.data_ptr(), packed.data_ptr(), params.data_ptr(), t, heads, d, L.current_stream(k.device))
+    L.check(st, "atom_kv_quant_u4_f16")
+    return packed, params

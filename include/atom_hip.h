@@ -608,6 +608,45 @@ int atom_moe_gemm_w4a4_f16(const void *A4, const void *B4, const void *sA, const
 int atom_moe_combine_f16(const void *y, const int32_t *slot_row, const int32_t *topk_ids, const void *topk_w, const void *residual,
                          void *out, int64_t T, int top_k, int64_t H, void *stream);
 
+/*
+ * Multi-adapter LoRA on fp16 activations beside the 4-bit base -- csrc/lora_f16.hip (the reference's punica.ops bgmv / add_lora,
+ * e2e/punica-atom/punica/ops/__init__.py:62-124, whose kernels it no longer compiles), generalised from rows to row SEGMENTS.
+ *
+ * atom_bgmv_f16: for every segment s -- rows seg_indptr[s] .. seg_indptr[s+1]-1, or row s when seg_indptr is NULL -- with adapter
+ * a = seg_adapter[s]:
+ *     a < 0 or a >= capacity:  the segment's rows of y are not touched (an id is never turned into an address unless 0 <= a < capacity)
+ *     else:  y[i, n] = half( float(y[i, n]) + scale * SUM_h float(x[i, h]) * float(W[a, layer_idx, n, h]) )
+ *   x fp16 [rows, H1]; y fp16 [rows, H2], updated in place; W fp16 [capacity, L, H2, H1]; seg_adapter int32 [S] and seg_indptr int32
+ *   [S + 1] (or NULL) on the device.  FP32 accumulation in the kernel's own (fixed) order, ONE rounding to fp16, at the store.  Rows at
+ *   or beyond seg_indptr[S] (and beyond `rows`) are never written; an empty segment costs nothing.  One of H1, H2 is the adapter rank --
+ *   a multiple of 8 in 8 .. 64 --, the other a multiple of 64 (or a rank too).  Two regimes: with a segment table, 16-row tiles of one
+ *   segment on v_mfma_f32_16x16x32_f16 (a tile across a segment's end masks its rows), a grid of rows / 16 + S row tiles sized on the
+ *   host, every workgroup finding its segment in the device table and leaving before it touches memory when it has none; without
+ *   one (decode: a row per segment) dot-product kernels.  One thread writes an output element, no atomics, no split of the h sum
+ *   across workgroups: a row's result depends on nothing but that row, its adapter and the shapes.  No host read, no
+ *   synchronisation: capturable.
+ * atom_add_lora_f16: y += scale * half(x A_a^T) B_a^T as two such passes: t[i, :] = half(SUM_h x[i, h] A[a, layer_idx, :, h]) into the
+ *   caller's fp16 workspace t [rows, rank] (written, not added to: the "zeroed t, scale 1" of the reference; rows of segments without
+ *   an adapter keep what t held and are not read), then y[i, n] = half(float(y[i, n]) + scale * SUM_j float(t[i, j]) B[a, layer_idx, n, j]).
+ *   Without a segment table (one-row segments) both passes run in ONE launch, t rounded to fp16 in LDS and the caller's t untouched:
+ *   the same operations in the same order, so the same bits as two atom_bgmv_f16 calls (the first into a zeroed t with scale 1).
+ *   A = wa fp16 [capacity, L, rank, H1], B = wb fp16 [capacity, L, H2, rank]; H1 % 64 == 0, H2 % 64 == 0, rank % 8 == 0 in 8 .. 64.
+ * Errors of both (all checked before any launch): ATOM_ERR_INVALID_ARG for a null y, x, weight, seg_adapter or t; ATOM_ERR_SHAPE unless
+ * rows >= 1, 1 <= S <= rows (S == rows when seg_indptr is NULL), capacity >= 1, 0 <= layer_idx < L and the widths are as above;
+ * ATOM_ERR_ALIGN unless y, x, the weights and t are 16-byte and the tables 4-byte aligned.
+ *
+ * atom_kv_quant_u4_f16: k fp16 [T, kv_heads, 128] -> packed u8 [T, kv_heads, 64] + param fp16 [T, kv_heads, 2] (scale, zero): the
+ * per-head u4 quantiser of atom_kv_quant_append_f32 (the same device function) on float(k), written to plain tensors in the form
+ * atom_kv_append_i4 takes -- for k / v that get an adapter's delta added before they are quantised.  head_dim must be 128;
+ * ATOM_ERR_SHAPE unless T >= 1, kv_heads >= 1; ATOM_ERR_ALIGN unless k and packed are 16-byte and param 4-byte aligned.
+ */
+int atom_bgmv_f16(void *y, const void *x, const void *w, const int32_t *seg_adapter, const int32_t *seg_indptr, int64_t rows, int64_t S,
+                  int64_t H1, int64_t H2, int64_t capacity, int64_t L, int64_t layer_idx, float scale, void *stream);
+int atom_add_lora_f16(void *y, const void *x, const void *wa, const void *wb, const int32_t *seg_adapter, const int32_t *seg_indptr,
+                      void *t, int64_t rows, int64_t S, int64_t H1, int64_t H2, int64_t rank, int64_t capacity, int64_t L,
+                      int64_t layer_idx, float scale, void *stream);
+int atom_kv_quant_u4_f16(const void *k, void *packed, void *param, int64_t T, int kv_heads, int head_dim, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
