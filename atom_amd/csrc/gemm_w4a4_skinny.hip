@@ -296,7 +296,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a4_skinny_kernel(GemmParams p)
             const half_t xh = *reinterpret_cast<const half_t *>(rowbuf + m * H * 2 + off * 2);
             if constexpr (QOP >= 2) {
               const half_t wg = *reinterpret_cast<const half_t *>(wbuf + off * 2);
-              v[k] = (float)(half_t)(((float)xh * (float)wg) * rv);                    // RMSNorm.cuh:145-151
+              v[k] = round_h(((float)xh * (float)wg) * rv);                            // RMSNorm.cuh:145-151 (FP32 product, THEN half)
             } else {
               v[k] = (float)xh;
             }

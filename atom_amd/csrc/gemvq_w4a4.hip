@@ -468,7 +468,7 @@ __global__ __launch_bounds__(NTH) void gemvq_w4a4_kernel(GemmParams p) {
             const half_t xh = *reinterpret_cast<const half_t *>(rowbuf + m * H * 2 + off * 2);
             if constexpr (NORM) {
               const half_t wg = *reinterpret_cast<const half_t *>(wbuf + off * 2);
-              v[k] = (float)(half_t)(((float)xh * (float)wg) * rv);                    // RMSNorm.cuh:145-151
+              v[k] = round_h(((float)xh * (float)wg) * rv);                            // RMSNorm.cuh:145-151 (FP32 product, THEN half)
             } else {
               v[k] = (float)xh;
             }

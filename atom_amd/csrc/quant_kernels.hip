@@ -502,10 +502,10 @@ __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
           if constexpr (SIM) {
             // HF LlamaRMSNorm, half opmath: half(x * rinv) from the FP32 product, then a half multiply by the weight (the exact
             // product of two halves rounded once: what round_h(w * y) in FP32 gives)
-            const half_t y = (half_t)((float)xh[ps][k] * rinv);
+            const half_t y = f2h((float)xh[ps][k] * rinv);                      // (f2h: the FP32 product is rounded BEFORE the half rounding)
             x[ps][k] = (float)(half_t)(wg[ps][k] * y);
           } else {
-            x[ps][k] = (float)(half_t)(((float)xh[ps][k] * (float)wg[ps][k]) * rinv);   // RMSNorm.cuh:145-151
+            x[ps][k] = round_h(((float)xh[ps][k] * (float)wg[ps][k]) * rinv);           // RMSNorm.cuh:145-151 (two roundings: FP32, then half)
           }
         }
       }

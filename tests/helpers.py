@@ -163,3 +163,38 @@ def recover_fake_quant(v, qmax, group):
     assert done.all(), "fake-quantised group not reproducible by integer codes: %d of %d" % ((~done).sum(), done.size)
     codes = np.rint(x / best.astype(np.float32)[..., None]).astype(np.int32).reshape(r, h)
     return codes, best
+
+
+def assert_quant_equal(outs, ref, M, *, layout="plain", fmt=False, xq_ref=None, what=""):
+    """The outputs of an activation quantiser op (keeper codes, INT4 codes, keeper scales, group scales[, de-quantised tensor]) against
+    an oracle result (dict q4, q8, s4, s8), bit for bit, naming the first (row, group) that differs.  fmt: False packed nibbles |
+    True wide int8 (wide_codes of the oracle's codes) | "f6" BF6 records (f6_codes of the oracle's codes and scales; -0 == +0)."""
+    o8, o4, s8, s4 = outs[:4]
+    q4r = np.asarray(ref["q4"])
+    G = q4r.shape[1] // 128
+
+    def first(bad, per_group):                               # bad [M, G * per_group] or [M, G]
+        at = np.argwhere(bad)[0]
+        return f"{what}: {int(bad.sum())} differ, first at row {int(at[0])}, group {int(at[1]) // per_group}"
+
+    bad = t2n(o8)[:M] != ref["q8"]
+    assert not bad.any(), "keeper codes " + first(bad, 128).replace("group 0", "keeper")
+    if fmt == "f6":
+        got, want = t2n(o4), f6_codes(q4r, ref["s4"])
+        bad = np.transpose(f6_fields(got[:, :M]) != f6_fields(want[:, :M]), (1, 0, 2)).reshape(M, -1)
+        assert not bad.any(), "BF6 codes " + first(bad, 128)
+        bad = np.transpose((got[:, :M, 96:] != want[:, :M, 96:]).any(axis=-1), (1, 0))
+        assert not bad.any(), "BF6 in-row scales " + first(bad, 1)
+    elif fmt:
+        bad = t2n(o4)[:M] != wide_codes(q4r)
+        assert not bad.any(), "wide codes " + first(bad, 128)
+    else:
+        bad = O.unpack_int4(t2n(o4)[:M].view(np.uint8)) != q4r
+        assert not bad.any(), "int4 codes " + first(bad, 128)
+    bad = bits16(scales_plain(s4, M, layout).T) != bits16(ref["s4"])
+    assert not bad.any(), "group scales " + first(bad, 1)
+    bad = (bits16(scales_plain(s8, M, layout)) != bits16(ref["s8"]))[:, None]
+    assert not bad.any(), "keeper scales " + first(bad, 1).replace("group 0", "keeper")
+    if xq_ref is not None:
+        bad = bits16(t2n(outs[4])[:M]) != bits16(xq_ref)
+        assert not bad.any(), "de-quantised tensor " + first(bad, 128) + " (group " + str(G) + " = keeper)"

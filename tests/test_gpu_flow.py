@@ -13,9 +13,13 @@ Statements, sharp to statistical:
       the reorder wiring (input columns, gate/up output rows, q/k/v sharing k_proj's order) and the packer are the reference's;
   (2) the first quantiser of the model (RMSNorm -> gather -> INT4/INT8) reproduces the reference's tensor, counted the way
       tests/test_gpu_ref.py counts: INT4 / INT8 CODES that differ (<= 0.5 %, by one step: the a8 tolerance, torch's unspecified reduction
-      order) and, separately, (row, group) SCALES that moved (<= 3 % of the groups, by one fp16 ulp: a last-bit difference in a row's
-      variance moves a whole group's scale -- and with it all 128 of its fake-quantised values, which is why the plain count of
-      differing ELEMENTS reads 1.3 %);
+      order) and, separately, (row, group) SCALES that moved (<= 3 % of the groups, by at most two fp16 ulps: a last-bit difference in a
+      row's variance moves a group's largest value by one half ulp and with it the group's scale -- and all 128 of its fake-quantised
+      values, which is why the plain count of differing ELEMENTS reads 1.3 %.  Two ulps, not one: scale = half(half(0.9 amax) / 7), and
+      where the significand of 0.9 amax is below 1.75 the scale's is 8 / 7 of it in the same binade -- one ulp of amax is 1.14 ulps of
+      the scale, which rounds to one OR two.  The CPU oracle on this test's own input is two ulps from the reference's tensor in one
+      group (sequence 320, row 160, group 2); the kernels equal the oracle bit for bit, tests/test_gpu_quant.py.  Until the RMSNorm
+      kernels rounded half(x * r) twice, as the reference does, that group's largest value happened to land on the reference's);
   (2b) ABSOLUTE, uncalibrated: every recorded projection of the reference run (q / o / gate / down of both layers, the rows the golden
       holds) teacher-forced -- the HIP GEMM on the reference's OWN fake-quantised input (codes and scales recovered exactly) against the
       reference's OWN output: <= 1e-3 relative Frobenius, every element within 1e-2 of max(|ref|, rms) (north_star's tolerance);
@@ -213,7 +217,7 @@ def _calibrated(tag, config, tokens, ref, seqlens, gptq_q=None):
         cf, cstep, sm, sulp = h[s, "first_q_codes"]
         lines.append(f"    ... of which codes that differ {cf:.5f} (by at most {cstep} step), (row, group) scales that moved {sm:.5f} "
                      f"(by at most {sulp} fp16 ulp)")
-        if not (cf <= 5e-3 and cstep <= 1 and sm <= 3e-2 and sulp <= 1 and h[s, "first_q"] <= 1e-3):
+        if not (cf <= 5e-3 and cstep <= 1 and sm <= 3e-2 and sulp <= 2 and h[s, "first_q"] <= 1e-3):
             bad.append((s, "first quantiser", h[s, "first_q_codes"]))
         lines.append(f"seqlen {s}: rel. Frobenius vs the reference golden      HIP    ref-order   perturbed ref-order")
         for key in KEYS + ("layer0", "layer1"):

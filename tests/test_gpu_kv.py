@@ -289,3 +289,87 @@ def test_graph_capture_grows_the_workspace_safely():
         gr.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, want)
+
+
+# ------------------------------------------------------------------------------------------------ the u4 head quantiser on planted vectors
+def _planted_cache(seed):
+    """2 layers, 3 heads, pages of 16; after acquire_one() the new tokens sit in the LAST slot of a page (length 16), the FIRST slot of
+    a new page (17) and inside one (21); the pool holds random bytes"""
+    from atom_amd.utils.kvcache import BatchedKvCacheInt4
+    pool, cs, _, g = _setup([15, 16, 20], layers=2, heads=3, block=16, seed=seed)
+    for c in cs:
+        c.acquire_one()
+    kv = BatchedKvCacheInt4(cs)
+    assert [int(v) for v in t2n(kv.last_page_offset)] == [16, 1, 5]
+    return pool, kv, g
+
+
+@pytest.mark.parametrize("entry", ["quant_append_kv_i4", "batch_decode_i4(append_kv=)", "kv_quant_u4 + append_kv_i4"])
+def test_u4_head_quantiser_on_planted_vectors(entry):
+    """The three entry points that take VALUES run their copies of quant_head_u4 (csrc/kv_attn.h) on the planted 128-vectors of
+    tests/quant_planted.py -- true ties, constant vectors (scale 0), one-sided ranges, an outlier, a subnormal fp16 scale; exact in
+    fp16 and FP32 -- and the slot they write equals O.quant_o4 of the same values bit for bit, codes and (scale, zero); every other
+    byte of the pool is unchanged.  (tests/test_quant_planted_cpu.py: the rounding rule, the clamp and the extrema each move these.)"""
+    from atom_amd import ops
+    from tests import quant_planted as P
+    B, heads, layer = 3, 3, 1
+    pool, kv, g = _planted_cache(seed=21)
+    q = torch.randn((B, heads, 128), device="cuda", generator=g).half()
+    for step in range(2):                                     # 2 x (9 k + 9 v) vectors: every planted vector, in other lanes the second time
+        if step:
+            pool, kv, g = _planted_cache(seed=22)
+        k = P.u4_matrix(B, heads, seed=step * 7)
+        v = P.u4_matrix(B, heads, seed=step * 7 + B * heads)
+        data, param = t2n(pool.buf).copy(), t2n(pool.param).copy()
+        (kq, kp), (vq, vp) = O.quant_o4(k), O.quant_o4(v)
+        O.kv_append_i4(data, param, *_np_tables(kv), kq.reshape(B, heads, 64), vq.reshape(B, heads, 64), kp, vp, layer, None)
+        kt, vt = torch.from_numpy(k).cuda(), torch.from_numpy(v).cuda()
+        if entry == "quant_append_kv_i4":
+            ops.quant_append_kv_i4(kv, kt, vt, layer)
+        elif entry == "batch_decode_i4(append_kv=)":
+            ops.batch_decode_i4(q, kv, layer, append_kv=(kt, vt))
+        else:
+            (k4, ks), (v4, vs) = ops.kv_quant_u4(kt.half().view(B, heads, 128)), ops.kv_quant_u4(vt.half().view(B, heads, 128))
+            assert np.array_equal(t2n(k4), kq.reshape(B, heads, 64)) and np.array_equal(t2n(ks).view(np.uint16), kp.view(np.uint16))
+            ops.append_kv_i4(kv, k4, v4, ks, vs, layer)
+        got_d, got_p = t2n(pool.buf), t2n(pool.param).view(np.uint16)
+        bad = np.argwhere((got_d != data).any(axis=-1) | (got_p != param.view(np.uint16)).any(axis=-1))
+        assert len(bad) == 0, f"{entry}: {len(bad)} slots differ, first [page, layer, k/v, head, slot] = {bad[0]}"
+
+
+def test_gemm_o4_decode_path_on_a_planted_matrix():
+    """dense_layer_gemm_i4_o4's decode path (weight-streaming kernel + o4_quant_kernel): operands whose FP32 sums ARE planted values --
+    identity-like weights with unit scales, so that D[m, n] = a4[m, n] sA[m, n / 128] + a8[m, n % 128] sA8[m] exactly: ties on a grid of
+    half the scale, a constant head vector, an all-negative one, an outlier.  The sums come from dense_layer_gemm_i4_f32 of the same
+    operands (as test_gemm_o4_reference_extrema_mode takes them) and are checked to carry ties."""
+    from atom_amd import ops
+    from tests import quant_planted as P
+    from tests.helpers import to_device
+    M, N, K = 4, 384, 512
+    G = N // 128
+    assert ops.decode_gemm_fits(M, N, K)
+    j = np.arange(128)
+    qa4, qa8 = np.zeros((M, N), dtype=np.int8), np.zeros((M, 128), dtype=np.int8)
+    sA, sA8 = np.ones((M, G), dtype=np.float16), np.ones(M, dtype=np.float16)
+    qa8[0] = j % 31; sA8[0] = 0.25                            # lo 0, hi 7.5: scale 0.5, every odd multiple of 0.25 a tie
+    qa4[0, 128:256] = (j % 16) - 8; sA[0, 1] = 7.5            # head 1: + a multiple of 7.5 (mixed signs, still on the 0.25 grid)
+    qa8[1] = 5                                                # constant head vectors (heads 0 and 2) ...
+    qa4[1, 128:256] = (j * 5) % 16 - 8                        # ... and integers -3 .. 12 in head 1: no ties, every code
+    qa8[2] = -(j % 31) - 3; sA8[2] = 0.125                    # all negative, ties
+    qa8[3] = (j % 5) - 2; sA8[3] = 2.0 ** -6                  # small values and one outlier per head
+    qa4[3, 77::128] = 7; sA[3] = 16.0
+    d = dict(qa4=qa4, qb4=np.eye(N, dtype=np.int8), qa8=qa8, qb8=np.tile(np.eye(128, dtype=np.int8), (G, 1)), sA=sA, sA8=sA8,
+             sB=np.ones((G, N), dtype=np.float16), sB8=np.ones(N, dtype=np.float16))
+    dev = to_device(d, "plain")
+    c32 = t2n(ops.dense_layer_gemm_i4_f32(*dev, scale_layout="plain"))
+    want = qa4.astype(np.float32) * np.repeat(sA.astype(np.float32), 128, axis=1) + np.tile(qa8.astype(np.float32) * sA8.astype(np.float32)[:, None], (1, G))
+    assert np.array_equal(c32, want)                          # the sums are the planted values, exactly
+    want_q, want_sz = O.quant_o4(c32)
+    for m in ("round_rule", "clamp", "abs_extrema"):          # ... and carry what the epilogue can get wrong
+        assert (P.quant_o4(c32, mutate=m)[0] != want_q).sum() >= 64, m
+    assert (want_sz[1, [0, 2], 0] == 0).all()
+    q, sz = ops.dense_layer_gemm_i4_o4(*dev, scale_layout="plain")
+    assert np.array_equal(t2n(sz).view(np.uint16).reshape(M, G, 2), want_sz.view(np.uint16))
+    assert np.array_equal(t2n(q), want_q)
+    q2, sz2 = ops.dense_layer_gemm_i4_o4(*dev, scale_layout="plain", use_workspace=False)     # the tile kernel's epilogue: same values, same codes
+    assert torch.equal(q, q2) and torch.equal(sz.view(torch.int16), sz2.view(torch.int16))

@@ -7,7 +7,8 @@ import pytest
 import torch
 
 from oracle import atom_oracle as O
-from tests.helpers import bits16, rand_act, scales_plain, t2n, wide_codes
+from tests import quant_planted as P
+from tests.helpers import assert_quant_equal, bits16, rand_act, scales_plain, t2n, wide_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -53,8 +54,7 @@ def test_reorder_quant_bit_exact(M, H, mode, clip, layout):
     ref = O.reorder_quant(x, idx, mode, clip)
     outs = ops.reorder_fp16_i4(torch.from_numpy(x).cuda(), torch.from_numpy(idx).cuda(), quant_mode=mode,
                                clip=clip, scale_layout=layout, return_dequant=True)
-    xq_ref = O.act_dequant_sim(ref) if mode == "sim" else None
-    _check_tail(outs, ref, M, layout, exact=True, xq_ref=xq_ref)
+    _check_tail(outs, ref, M, layout, exact=True, xq_ref=O.act_dequant_sim(ref))     # (both modes: half(code x stored half scale))
 
 
 def test_reorder_quant_identity_and_edges():
@@ -64,13 +64,15 @@ def test_reorder_quant_identity_and_edges():
     x[1] = 0                                   # all-zero row: amax clamp (sim) / zero scale (kernel)
     x[2, :] = 1e-6                             # below the 1e-5 clamp
     x[3, 7] = 65504.0                          # fp16 max
-    x[4] = (np.arange(H) % 15 - 7) * 0.5       # exact ties
+    # row 4: half-integers on a grid of 0.5 with amax 3.5 -- the kernel mode's scale is 0.5 and its quotients are INTEGERS, the simulated
+    # mode's (clip 0.9) are no ties either: swapping the rounding rule moves no code of this row.  It checks exact quotients; the true
+    # ties are planted in tests/quant_planted.py (tests/test_gpu_quant_planted.py)
+    x[4] = (np.arange(H) % 15 - 7) * 0.5
     for mode, clip in [("sim", 0.9), ("kernel", 1.0)]:
         ref = O._quant_row_tail(x if mode == "sim" else x.astype(np.float32), mode, clip)
         outs = ops.reorder_fp16_i4(torch.from_numpy(x).cuda(), None, quant_mode=mode, clip=clip,
                                    scale_layout="plain", return_dequant=True)
-        _check_tail(outs, ref, M, "plain", exact=True,
-                    xq_ref=O.act_dequant_sim(ref) if mode == "sim" else None)
+        _check_tail(outs, ref, M, "plain", exact=True, xq_ref=O.act_dequant_sim(ref))
 
 
 def test_reorder_quant_golden(golden_dir):
@@ -136,11 +138,11 @@ def test_rmsnorm_quant_bit_exact(M, H, mode, clip):
     x = (rand_act(M, H, seed=M + 7 * H).astype(np.float32) * 2.0).astype(np.float16)
     w = (1.0 + 0.1 * g.standard_normal(H)).astype(np.float16)
     idx = g.permutation(H).astype(np.int16)
-    eps = 1e-5
-    ref = O.rmsnorm_reorder_quant(x, w, eps, idx, mode, clip)
-    outs = ops.rmsnorm_fp16_i4(torch.from_numpy(x).cuda(), torch.from_numpy(w).cuda(), torch.from_numpy(idx).cuda(),
-                               eps, quant_mode=mode, clip=clip, scale_layout="ref", return_dequant=True)
-    _check_tail(outs, ref, M, "ref", exact=True, xq_ref=O.act_dequant_sim(ref) if mode == "sim" else None)
+    for eps in (1e-5, 1e-6):                  # (1e-6: Llama-1 checkpoints)
+        ref = O.rmsnorm_reorder_quant(x, w, eps, idx, mode, clip)
+        outs = ops.rmsnorm_fp16_i4(torch.from_numpy(x).cuda(), torch.from_numpy(w).cuda(), torch.from_numpy(idx).cuda(),
+                                   eps, quant_mode=mode, clip=clip, scale_layout="ref", return_dequant=True)
+        _check_tail(outs, ref, M, "ref", exact=True, xq_ref=O.act_dequant_sim(ref))
 
 
 def test_rmsnorm_quant_golden(golden_dir):
@@ -229,6 +231,7 @@ def test_wide_codes_are_the_packed_codes_widened(M, H, mode, clip):
     w = ops.reorder_fp16_i4(xt, it, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=True, wide_codes=True)
     assert w[1].shape == (M, H - 128) and w[1].dtype == torch.int8
     assert np.array_equal(t2n(w[1]), wide_codes(ref["q4"]))
+    assert np.array_equal(bits16(t2n(p[4])), bits16(O.act_dequant_sim(ref)))          # (both modes)
     for a, b in zip((p[0], p[2], p[3], p[4]), (w[0], w[2], w[3], w[4])):
         assert torch.equal(a, b)
     # the two fused producers share the store path
@@ -254,16 +257,18 @@ def test_add_rmsnorm_is_add_then_rmsnorm(M, H, mode, clip):
     w = torch.from_numpy((1 + 0.1 * g.standard_normal(H)).astype(np.float16)).cuda()
     idx = torch.from_numpy(g.permutation(H).astype(np.int16)).cuda()
     s_ref = x + res
-    want = ops.rmsnorm_fp16_i4(s_ref, w, idx, 1e-5, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=True)
-    got = ops.add_rmsnorm_fp16_i4(x, res, w, idx, 1e-5, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=True)
-    assert torch.equal(got[0], s_ref)
-    for a, b in zip(got[1:], want):
-        assert torch.equal(a, b)
-    oracle = O.rmsnorm_reorder_quant(t2n(s_ref), t2n(w), 1e-5, t2n(idx), mode, clip)
-    assert np.array_equal(O.unpack_int4(t2n(got[2]).view(np.uint8)), oracle["q4"])
-    res2 = res.clone()
-    got2 = ops.add_rmsnorm_fp16_i4(x, res2, w, idx, 1e-5, inplace=True, quant_mode=mode, clip=clip, scale_layout="plain")
-    assert got2[0] is res2 and torch.equal(res2, s_ref) and torch.equal(got2[2], want[1])
+    for eps in (1e-5, 1e-6):
+        want = ops.rmsnorm_fp16_i4(s_ref, w, idx, eps, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=True)
+        got = ops.add_rmsnorm_fp16_i4(x, res, w, idx, eps, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=True)
+        assert torch.equal(got[0], s_ref)
+        for a, b in zip(got[1:], want):
+            assert torch.equal(a, b)
+        oracle = O.rmsnorm_reorder_quant(t2n(s_ref), t2n(w), eps, t2n(idx), mode, clip)
+        assert np.array_equal(O.unpack_int4(t2n(got[2]).view(np.uint8)), oracle["q4"])
+        _check_tail(got[1:], oracle, M, "plain", exact=True, xq_ref=O.act_dequant_sim(oracle))       # keeper, scales, de-quantised tensor too
+        res2 = res.clone()
+        got2 = ops.add_rmsnorm_fp16_i4(x, res2, w, idx, eps, inplace=True, quant_mode=mode, clip=clip, scale_layout="plain")
+        assert got2[0] is res2 and torch.equal(res2, s_ref) and torch.equal(got2[2], want[1])
 
 
 def test_f6_codes_from_all_three_quantisers():
@@ -291,3 +296,129 @@ def test_f6_codes_from_all_three_quantisers():
             assert np.array_equal(got[:, :M, 96:], want[:, :M, 96:])
             for a, c in zip((p[0], p[2], p[3]), (f[0], f[2], f[3])):
                 assert torch.equal(a, c)
+
+
+# ------------------------------------------------------------------------------------------------ launch branches and row loops
+def _m_big():
+    """more rows than any persistent grid: a CU holds at most 32 waves = 8 workgroups of 256 threads, so resident <= 8 * CUs and with
+    3 * 8 * CUs + 37 rows every workgroup of act_quant2_kernel takes at least three rows, odd and even trip counts occurring over the
+    XCD partitions (6181 rows on 256 CUs)"""
+    return 3 * 8 * torch.cuda.get_device_properties(0).multi_processor_count + 37
+
+
+def _norm_operands(H, seed):
+    g = np.random.default_rng(seed)
+    return (1.0 + 0.1 * g.standard_normal(H)).astype(np.float16), g.permutation(H).astype(np.int16)
+
+
+def _three_ops(M, H, mode, clip, formats, seed, eps=1e-5):
+    """reorder, RMSNorm and add-RMSNorm on M random rows (every row different: a row written from another row's data shows) against
+    the oracle: codes, keeper, both scales, the de-quantised tensor, the residual stream.  RMSNorm runs on s = half(x + residual),
+    add-RMSNorm on (x, residual): one reference for both."""
+    ops = _ops()
+    x = rand_act(M, H, seed=seed)
+    res = (np.random.default_rng(seed + 1).standard_normal((M, H)) * 3).astype(np.float16)
+    s = (x.astype(np.float32) + res.astype(np.float32)).astype(np.float16)
+    w, idx = _norm_operands(H, seed + 2)
+    xt, rt, st, wt, it = (torch.from_numpy(a).cuda() for a in (x, res, s, w, idx))
+    what = f"{M} x {H} {mode} {clip}"
+    ref = P.run("reorder", (s, idx), mode, clip)
+    for fmt in formats:
+        dq = fmt is False
+        outs = ops.reorder_fp16_i4(st, it, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=dq, wide_codes=fmt)
+        assert_quant_equal(outs, ref, M, fmt=fmt, xq_ref=ref["xq"] if dq else None, what=f"reorder {what} fmt={fmt}")
+    ref = P.run("rmsnorm", (s, w, eps, idx), mode, clip)
+    for fmt in formats:
+        dq = fmt is False
+        outs = ops.rmsnorm_fp16_i4(st, wt, it, eps, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=dq, wide_codes=fmt)
+        assert_quant_equal(outs, ref, M, fmt=fmt, xq_ref=ref["xq"] if dq else None, what=f"rmsnorm {what} fmt={fmt}")
+        outs = ops.add_rmsnorm_fp16_i4(xt, rt, wt, it, eps, quant_mode=mode, clip=clip, scale_layout="plain", return_dequant=dq, wide_codes=fmt)
+        bad = bits16(t2n(outs[0])) != bits16(s)
+        assert not bad.any(), f"add_rmsnorm {what}: residual stream, first at row {np.argwhere(bad)[0][0]}"
+        assert_quant_equal(outs[1:], ref, M, fmt=fmt, xq_ref=ref["xq"] if dq else None, what=f"add_rmsnorm {what} fmt={fmt}")
+
+
+@pytest.mark.parametrize("H", [512, 4096])
+@pytest.mark.parametrize("mode,clip", [("kernel", 1.0), ("sim", 0.9)])
+def test_row_loops_against_the_oracle(mode, clip, H):
+    """Every workgroup of the persistent kernels walks at least three rows (the LDS double buffer turns over; 4096: the RMSNorm
+    instances whose row loop is unrolled by two over compile-time buffers) and every XCD partition ends raggedly.  512, kernel mode:
+    also the wide and BF6 stores, against wide_codes() / f6_codes() of the ORACLE's codes."""
+    formats = [False, True, "f6"] if (H == 512 and mode == "kernel") else [False]
+    _three_ops(_m_big(), H, mode, clip, formats, seed=H + 17)
+
+
+@pytest.mark.parametrize("H", [5120, 12288, 16384])
+@pytest.mark.parametrize("mode,clip", [("kernel", 1.0), ("sim", 0.9)])
+def test_ragged_xcd_tails_with_several_slot_passes(mode, clip, H):
+    """67 rows: 64 workgroups or more partition the rows per XCD (nine rows each, the last XCD four); 2, 3 and 4 slots per thread
+    (NP; 3 had no norm-op test); at 16384 add-RMSNorm keeps the weights out of LDS (w_lds = false)"""
+    _three_ops(67, H, mode, clip, [False], seed=H + 3)
+
+
+@pytest.mark.parametrize("M,H", [(1031, 11008), (1025, 256), (300, 11008)])
+@pytest.mark.parametrize("mode,clip", [("kernel", 1.0), ("sim", 0.9)])
+def test_silu_mul_launch_shapes_exact(M, H, mode, clip):
+    """silu_quant2_kernel above 1024 rows: one workgroup per row walks the row's slots with stride 256 (11008: three trips); 300 rows:
+    three workgroups per row and an XCD tail.  Saturated gates (tests/quant_planted.py), so exact=True: bit for bit."""
+    ops = _ops()
+    a, b = P.silu_random(M, H, seed=M + H)
+    ref = P.run("silu_mul", (a, b), mode, clip)
+    at, bt = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    outs = ops.activate_fp16_i4(at, bt, quant_mode=mode, clip=clip, scale_layout="ref", return_dequant=True)
+    _check_tail(outs, ref, M, "ref", exact=True, xq_ref=ref["xq"])
+    for fmt in (False, "f6"):
+        outs = ops.activate_fp16_i4(at, bt, quant_mode=mode, clip=clip, scale_layout="plain", wide_codes=fmt)
+        assert_quant_equal(outs, ref, M, fmt=fmt, what=f"silu_mul {M} x {H} {mode} fmt={fmt}")
+
+
+@pytest.mark.parametrize("op", ["reorder", "rmsnorm", "add_rmsnorm", "silu_mul"])
+def test_rows_behind_m_are_untouched(op):
+    """One packed-format call per op through the C ABI into outputs eight rows longer than M, pre-filled with a sentinel (plain
+    layout: the group scales are [G, M], their guard lies behind the last group): nothing behind row M changes -- 67 rows, so that
+    the persistent kernels partition by XCD and the SiLU grid (a multiple of eight) has idle workgroups."""
+    from atom_amd import _lib as L
+    lib = L.lib()
+    M, H, PAD, SENT = 67, 1024, 8, 0x5A
+    G = H // 128 - 1
+    dev = "cuda"
+    x = torch.from_numpy(rand_act(M, H, seed=9)).cuda()
+    b = torch.from_numpy(rand_act(M, H, seed=10, outliers=False)).cuda()
+    w, idx = (torch.from_numpy(a).cuda() for a in _norm_operands(H, 11))
+    o8 = torch.full((M + PAD, 128), SENT, dtype=torch.int8, device=dev)
+    o4 = torch.full((M + PAD, (H - 128) // 2), SENT, dtype=torch.int8, device=dev)
+    s8 = torch.full((M + PAD,), SENT, dtype=torch.int8, device=dev).repeat_interleave(2).view(torch.float16)
+    s4 = torch.full((2 * (G * M + PAD),), SENT, dtype=torch.int8, device=dev).view(torch.float16)
+    xq = torch.full((M + PAD, 2 * H), SENT, dtype=torch.int8, device=dev).view(torch.float16)
+    rs = torch.full((M + PAD, 2 * H), SENT, dtype=torch.int8, device=dev).view(torch.float16)
+    tail = (o8.data_ptr(), o4.data_ptr(), s8.data_ptr(), s4.data_ptr(), xq.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    mode = L.QUANT_KERNEL
+    if op == "reorder":
+        st = lib.atom_reorder_quant_f16(x.data_ptr(), idx.data_ptr(), M, H, mode, 1.0, L.SCALE_LAYOUT_PLAIN, *tail)
+        ref = O.reorder_quant(t2n(x), t2n(idx), "kernel", 1.0)
+    elif op == "rmsnorm":
+        st = lib.atom_rmsnorm_reorder_quant_f16(x.data_ptr(), w.data_ptr(), 1e-5, idx.data_ptr(), M, H, mode, 1.0, L.SCALE_LAYOUT_PLAIN, *tail)
+        ref = O.rmsnorm_reorder_quant(t2n(x), t2n(w), 1e-5, t2n(idx), "kernel", 1.0)
+    elif op == "add_rmsnorm":
+        st = lib.atom_add_rmsnorm_reorder_quant_f16(x.data_ptr(), b.data_ptr(), rs.data_ptr(), w.data_ptr(), 1e-5, idx.data_ptr(), M, H, mode, 1.0,
+                                                    L.SCALE_LAYOUT_PLAIN, *tail)
+        ref = O.rmsnorm_reorder_quant(t2n(x + b), t2n(w), 1e-5, t2n(idx), "kernel", 1.0)
+    else:
+        st = lib.atom_silu_mul_quant_f16(x.data_ptr(), b.data_ptr(), M, H, mode, 1.0, L.SCALE_LAYOUT_PLAIN, *tail)
+        ref = None
+    assert st == 0
+    torch.cuda.synchronize()
+    sent16 = SENT | (SENT << 8)
+    assert (t2n(o8)[M:] == SENT).all() and (t2n(o4)[M:] == SENT).all()
+    assert (t2n(s8).view(np.uint16)[M:] == sent16).all() and (t2n(s4).view(np.uint16)[G * M:] == sent16).all()
+    assert (t2n(xq).view(np.uint16)[M:] == sent16).all()
+    if op == "add_rmsnorm":
+        assert (t2n(rs).view(np.uint16)[M:] == sent16).all() and torch.equal(rs[:M], x + b)
+    else:
+        assert (t2n(rs).view(np.uint16) == sent16).all()
+    if ref is not None:                                       # and the rows before M are the op's
+        assert_quant_equal((o8, o4, s8[:M], s4[:G * M].view(G, M), xq), ref, M, xq_ref=O.act_dequant_sim(ref), what=op + " into padded outputs")
+    else:
+        want = _ops().activate_fp16_i4(x, b, scale_layout="plain", return_dequant=True)
+        for got, w_ in zip((o8[:M], o4[:M], s8[:M], s4[:G * M].view(G, M), xq[:M]), want):
+            assert torch.equal(got.view(torch.uint8), w_.view(torch.uint8))
