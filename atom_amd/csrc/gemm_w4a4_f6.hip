@@ -1862,20 +1862,9 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
       if (m >= p.M) continue;
       const half_t sh = f2h(gs.s_store);
       if (keeper_blk) {
-        const float lo = __builtin_fmaf(tr[1], 256.f, tr[0] + 32896.f), hi = __builtin_fmaf(tr[3], 256.f, tr[2] + 32896.f);
-        const float lo2 = __builtin_fmaf(tr[5], 256.f, tr[4] + 32896.f), hi2 = __builtin_fmaf(tr[7], 256.f, tr[6] + 32896.f);
-        const v2u w = v2u{((unsigned)lo | ((unsigned)hi << 16)) ^ 0x80808080u, ((unsigned)lo2 | ((unsigned)hi2 << 16)) ^ 0x80808080u};
-        *reinterpret_cast<v2u *>(o.o8 + m * kKeeper + wn * 32 + kb * 8) = w;
+        *reinterpret_cast<v2u *>(o.o8 + m * kKeeper + wn * 32 + kb * 8) = pack_codes8(tr, true);
       } else {
-        typedef float v16f __attribute__((ext_vector_type(16)));
-        typedef unsigned v6u __attribute__((ext_vector_type(6)));
-        v16f ea, eb;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          ea[i] = i < 4 ? tr[2 * i] : 0.f;
-          eb[i] = i < 4 ? tr[2 * i + 1] : 0.f;
-        }
-        const v6u f = cvt_2xpk16_bf6(ea, eb);   // fields 0..7 = my 8 codes: 48 bits
+        const v6u_t f = bf6_fields(tr);         // fields 0..7 = my 8 codes: 48 bits
         uint8_t *dst = o.o6 + ((int64_t)bn * o.o6_rows + m) * PITCH;
         uint8_t *d6 = dst + wn * 24 + kb * 6;               // 2-byte aligned: 4 + 2 or 2 + 4 byte stores
         if ((kb & 1) == 0) {
@@ -1885,24 +1874,14 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
           *reinterpret_cast<unsigned short *>(d6) = (unsigned short)f[0];
           *reinterpret_cast<unsigned *>(d6 + 2) = (f[0] >> 16) | (f[1] << 16);
         }
-        if (wn == 0 && kb == 0)                             // the next GEMM reads the token scale from the row: fp16 + fp32
-          *reinterpret_cast<v2u *>(dst + 96) = v2u{(unsigned)__builtin_bit_cast(unsigned short, sh), __builtin_bit_cast(unsigned, (float)sh)};
+        if (wn == 0 && kb == 0) *reinterpret_cast<v2u *>(dst + 96) = f6_scale_words(__builtin_bit_cast(unsigned short, sh));
       }
-      if (wn == 0 && kb == 0) {
-        half_t *sd = keeper_blk ? o.s8 : (o.s4 + (int64_t)bn * o.ld4);
-        if (o.ref_layout) {
-          const int base = ref_scale_index((int)m);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) sd[base + 2 * k] = sh;
-        } else {
-          sd[m] = sh;
-        }
-      }
-      if (o.xq) {                                           // code * scale, exact in FP32, one rounding (see quant_kernels.hip)
+      if (wn == 0 && kb == 0) store_token_scale(keeper_blk ? o.s8 : (o.s4 + (int64_t)bn * o.ld4), m, sh, o.ref_layout);
+      if (o.xq) {
         v4u q;
         half_t *qv = reinterpret_cast<half_t *>(&q);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qv[j] = (half_t)__builtin_fmaf(tr[j], gs.s_dq, 0.0f);
+        for (int j = 0; j < 8; ++j) qv[j] = dequant_half(tr[j], gs);
         *reinterpret_cast<v4u *>(o.xq + m * N_inter + bn * 128 + wn * 32 + kb * 8) = q;
       }
     }

@@ -81,10 +81,11 @@ inline size_t q_lds_bytes(int q_op, int K4h, int G) {
 // QOP != 0 (one or two tokens, MBLK == 1; atom_gemm_w4a4_multi_q): the kernel starts with the quantiser that feeds this GEMM in the
 // reference's call order -- reorder (1), RMSNorm + reorder (2), residual add + RMSNorm + reorder (3), SiLU x up (4); punica/models/
 // llama.py:259-292, :85-87 -- run by EVERY workgroup on its own copy of the token rows, behind the weight loads (which are in flight
-// while it runs), and its packed operand stays in LDS.  Same arithmetic as quant_kernels.hip slot by slot (kernel-flavoured mode:
-// Reorder.cuh:137-178, RMSNorm.cuh:112-151, Activate.cuh:112-167) including the fixed-shape FP32 tree of the sum of squares (256
-// threads, chunk c -> wave (c / 64) % 4, lane c % 64): bit-identical to the separate launch, which costs a launch boundary and a
-// round trip through HBM more than the GEMM itself at this size.
+// while it runs), and its packed operand stays in LDS.  The arithmetic is quant_math.h's, the functions the stand-alone kernels of
+// quant_kernels.hip call (kernel-flavoured mode: Reorder.cuh:137-178, RMSNorm.cuh:112-151, Activate.cuh:112-167); this file only
+// stages the rows (256 threads per row for the sum of squares, 16 channels per thread for the codes) and keeps the codes in LDS:
+// bit-identical to the separate launch, which costs a launch boundary and a round trip through HBM more than the GEMM itself at
+// this size.
 template <int NW, int MBLK, int CNT, int OUT = 0, bool NT = false, int QOP = 0>
 __global__ __launch_bounds__(NW * 64) void gemm_w4a4_skinny_kernel(GemmParams p) {
   constexpr bool OUT32 = OUT == 1;
@@ -138,7 +139,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a4_skinny_kernel(GemmParams p)
   constexpr int TPT = QOP == 4 ? 3 : 2, XC = 3;             // slot tasks / row chunks per thread at most (checked by the launcher)
   const int H = 2 * K4h + kKeeper;
   const int q_nchunks = H >> 3, q_nslots = H >> 4;
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   v4u q_ri[QOP ? TPT : 1][2], q_rb[QOP == 4 ? TPT : 1][2];
   h8 q_xr[QOP && QOP <= 3 ? XC : 1], q_rr[QOP == 3 ? XC : 1], q_wr[QOP == 2 || QOP == 3 ? 2 : 1];
   if constexpr (QOP != 0) {
@@ -259,21 +259,14 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a4_skinny_kernel(GemmParams p)
       const int m = tid >> 8, t8 = tid & 255;               // the stand-alone kernel's 4-wave tree, one per row
       if (m < p.M) {
         float ss = 0.f;
-        for (int c = t8; c < nchunks; c += 256) {            // chunk (i * 4 + wave) * 64 + lane, i ascending
-          const h8 v = *reinterpret_cast<const h8 *>(rowbuf + m * H * 2 + c * 16);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)v[k], (float)v[k], ss);
-        }
+        for (int c = t8; c < nchunks; c += 256)              // chunk (i * 4 + wave) * 64 + lane, i ascending
+          ss = sumsq8(*reinterpret_cast<const h8 *>(rowbuf + m * H * 2 + c * 16), ss);
         ss = wave_sum_butterfly(ss);
         if (lane == 0) red[m * 4 + (wave & 3)] = ss;
       }
       lds_barrier();
 #pragma unroll
-      for (int m2 = 0; m2 < MQ; ++m2) {
-        const float tot = ((red[m2 * 4 + 0] + red[m2 * 4 + 1]) + red[m2 * 4 + 2]) + red[m2 * 4 + 3];
-        const float var = (H & (H - 1)) == 0 ? tot * (1.0f / (float)H) : tot / (float)H;
-        rinv[m2] = rinv_sqrt_exact(var + p.q_eps);
-      }
+      for (int m2 = 0; m2 < MQ; ++m2) rinv[m2] = rms_rinv(red + m2 * 4, H, p.q_eps);
     }
 #pragma unroll
     for (int t = 0; t < TPT; ++t) {
@@ -294,22 +287,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a4_skinny_kernel(GemmParams p)
           for (int k = 0; k < 16; ++k) {
             const int off = p.q_idx ? (int)iv[k] : e0 + k;
             const half_t xh = *reinterpret_cast<const half_t *>(rowbuf + m * H * 2 + off * 2);
-            if constexpr (QOP >= 2) {
-              const half_t wg = *reinterpret_cast<const half_t *>(wbuf + off * 2);
-              v[k] = round_h(((float)xh * (float)wg) * rv);                            // RMSNorm.cuh:145-151 (FP32 product, THEN half)
-            } else {
-              v[k] = (float)xh;
-            }
+            if constexpr (QOP >= 2) v[k] = rmsnorm_value<false>(xh, *reinterpret_cast<const half_t *>(wbuf + off * 2), rv);
+            else v[k] = (float)xh;
           }
         }
-        float amax = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-        amax = max8(amax);
-        const GroupScale gs = group_scale<false>(amax, keeper, p.q_clip);
         float tr[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tr[i] = group_code<false>(v[i], gs);
+        const GroupScale gs = group_codes<false, max8>(v, keeper, p.q_clip, tr);
         const v4u w = pack_codes16(tr, keeper);
         if (keeper) *reinterpret_cast<v4u *>(qa8 + m * kKeeper + j * 16) = w;
         else *reinterpret_cast<v2u *>(qa4 + m * K4h + g * 64 + j * 8) = v2u{w[0], w[1]};

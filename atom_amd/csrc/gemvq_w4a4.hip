@@ -25,8 +25,10 @@
 //     group exactly, the quad leader applies c = fma(idot, sA * sB, c), 64-lane butterfly, keeper last.
 // Output: bit-identical to the stand-alone quantiser launch followed by atom_gemm_w4a4_multi (which runs gemv1_w4a4_kernel for these
 // token counts) -- atom_gemm_w4a4_packed_order() = 64 on both sides.
-// Quantiser arithmetic: the kernel-flavoured mode of quant_kernels.hip slot by slot (Reorder.cuh:137-178, RMSNorm.cuh:112-151,
-// Activate.cuh:112-167), the sum of squares as the same fixed-shape FP32 tree (256 threads per row).
+// Quantiser arithmetic: the functions of quant_math.h in their kernel-flavoured mode (Reorder.cuh:137-178, RMSNorm.cuh:112-151,
+// Activate.cuh:112-167) -- the ones the stand-alone kernels of quant_kernels.hip call.  This file only decides how a row's values reach
+// them (staged rows and norm weights in LDS, 8 channels per thread, the sum of squares over 256 threads per row) and where the codes go
+// (the LDS operand).
 #include <type_traits>
 #include "common.h"
 #include "quant_math.h"
@@ -43,13 +45,6 @@ __device__ __forceinline__ int quad_sum(int d) {
   d += __builtin_amdgcn_mov_dpp(d, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
   d += __builtin_amdgcn_mov_dpp(d, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
   return d;
-}
-
-// max over the aligned 16 lanes this lane belongs to (a quantisation group of 8-channel tasks = one DPP row): exact, order-free
-__device__ __forceinline__ float max16(float a) {
-  a = max8(a);
-  a = fmaxf(a, dpp_f<0x140>(a));                      // row_mirror: lanes 8-15 <-> 7-0 of the row
-  return a;
 }
 
 // LDS: the packed operand [MQ][K4h] codes, [MQ][128] keeper, [G][MQ] + [MQ] fp16 scales; then (16-byte aligned) the reduction scratch,
@@ -180,7 +175,6 @@ __global__ __launch_bounds__(NTH) void gemvq_w4a4_kernel(GemmParams p) {
   const int tpr = H / CPT;                                   // tasks per row: 8 channels each, 16 per quantisation group
   const int ntask = p.M * tpr;
   const int wbase = tid & ~63;                               // this wave's first thread
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   constexpr int TPT = TPT1 * MT;
   v4u q_ri[TPT], q_rb[QOP == 4 ? TPT : 1];                  // per task: 8 reorder indices (ops 1-3) / 8 gate and 8 up values (op 4)
   h8 q_xr[ROWS ? XC : 1], q_rr[QOP == 3 ? XC : 1], q_wr[NORM ? XC : 1];
@@ -419,16 +413,10 @@ __global__ __launch_bounds__(NTH) void gemvq_w4a4_kernel(GemmParams p) {
         if (regsum) {                                        // (one token: thread t8 holds chunks t8 and t8 + 256 = the tree's own)
 #pragma unroll
           for (int i = 0; i < XC; ++i)
-            if (t8 + i * 256 < q_nchunks) {
-#pragma unroll
-              for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)q_xr[i][k], (float)q_xr[i][k], ss);
-            }
+            if (t8 + i * 256 < q_nchunks) ss = sumsq8(q_xr[i], ss);
         } else {
-          for (int c = t8; c < q_nchunks; c += 256) {        // chunk (i * 4 + wave) * 64 + lane, i ascending
-            const h8 v = *reinterpret_cast<const h8 *>(rowbuf + m * H * 2 + c * 16);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)v[k], (float)v[k], ss);
-          }
+          for (int c = t8; c < q_nchunks; c += 256)          // chunk (i * 4 + wave) * 64 + lane, i ascending
+            ss = sumsq8(*reinterpret_cast<const h8 *>(rowbuf + m * H * 2 + c * 16), ss);
         }
         ss = wave_sum_butterfly(ss);
         if (lane == 0) red[m * 4 + (wave & 3)] = ss;
@@ -437,11 +425,7 @@ __global__ __launch_bounds__(NTH) void gemvq_w4a4_kernel(GemmParams p) {
       GQ_STAMP(4);                                             // sum of squares done
       if (!roles && sumsq_wave) issue_ring();
 #pragma unroll
-      for (int m2 = 0; m2 < MT; ++m2) {                      // (every thread: ~110 instructions per row)
-        const float tot = ((red[m2 * 4 + 0] + red[m2 * 4 + 1]) + red[m2 * 4 + 2]) + red[m2 * 4 + 3];
-        const float var = (H & (H - 1)) == 0 ? tot * (1.0f / (float)H) : tot / (float)H;
-        rinv[m2] = rinv_sqrt_exact(var + p.q_eps);
-      }
+      for (int m2 = 0; m2 < MT; ++m2) rinv[m2] = rms_rinv(red + m2 * 4, H, p.q_eps);   // (every thread: ~110 instructions per row)
     }
     GQ_STAMP(12);                                              // 1 / sqrt done
     // the codes: 8 channels per thread, a 128-channel group = 16 adjacent lanes (the stand-alone kernels take 16 per thread: the same
@@ -466,43 +450,15 @@ __global__ __launch_bounds__(NTH) void gemvq_w4a4_kernel(GemmParams p) {
           for (int k = 0; k < CPT; ++k) {
             const int off = p.q_idx ? (int)iv[k] : e0 + k;
             const half_t xh = *reinterpret_cast<const half_t *>(rowbuf + m * H * 2 + off * 2);
-            if constexpr (NORM) {
-              const half_t wg = *reinterpret_cast<const half_t *>(wbuf + off * 2);
-              v[k] = round_h(((float)xh * (float)wg) * rv);                            // RMSNorm.cuh:145-151 (FP32 product, THEN half)
-            } else {
-              v[k] = (float)xh;
-            }
+            if constexpr (NORM) v[k] = rmsnorm_value<false>(xh, *reinterpret_cast<const half_t *>(wbuf + off * 2), rv);
+            else v[k] = (float)xh;
           }
         }
-        float amax = 0.f;
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) amax = fmaxf(amax, fabsf(v[i]));
-        amax = max16(amax);
-        const GroupScale gs = group_scale<false>(amax, keeper, p.q_clip);
         float tr[CPT];
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) tr[i] = group_code<false>(v[i], gs);
+        const GroupScale gs = group_codes<false, max16>(v, keeper, p.q_clip, tr);
         if (tid + t * PT < ntask) {
-          if (keeper) {                                        // 8 INT8 codes: two words of pack_codes16's keeper form
-            unsigned w2[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-              const float lo = __builtin_fmaf(tr[4 * k + 1], 256.f, tr[4 * k] + 32896.f), hi = __builtin_fmaf(tr[4 * k + 3], 256.f, tr[4 * k + 2] + 32896.f);
-              w2[k] = ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x80808080u;
-            }
-            *reinterpret_cast<v2u *>(qa8 + m * kKeeper + j * 8) = v2u{w2[0], w2[1]};
-          } else {                                             // 8 INT4 codes: one word of its nibble form
-            float lo = 34952.f, hi = 34952.f;
-            lo = __builtin_fmaf(tr[0], 1.f, lo);
-            lo = __builtin_fmaf(tr[1], 16.f, lo);
-            lo = __builtin_fmaf(tr[2], 256.f, lo);
-            lo = __builtin_fmaf(tr[3], 4096.f, lo);
-            hi = __builtin_fmaf(tr[4], 1.f, hi);
-            hi = __builtin_fmaf(tr[5], 16.f, hi);
-            hi = __builtin_fmaf(tr[6], 256.f, hi);
-            hi = __builtin_fmaf(tr[7], 4096.f, hi);
-            *reinterpret_cast<unsigned *>(qa4 + m * K4h + g * 64 + j * 4) = ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x88888888u;
-          }
+          if (keeper) *reinterpret_cast<v2u *>(qa8 + m * kKeeper + j * 8) = pack_codes8(tr, true);
+          else *reinterpret_cast<unsigned *>(qa4 + m * K4h + g * 64 + j * 4) = pack_codes8(tr, false)[0];
           if (j == 0) {
             if (keeper) qsa8[m] = f2h(gs.s_store);
             else qsa[g * MQ + m] = f2h(gs.s_store);

@@ -80,10 +80,7 @@ __device__ __forceinline__ void slot_store(const SlotOut<DQ> &q, const ActQuantP
     if constexpr (FMT == 2) {
       uint8_t *dst = p.o4 + ((int64_t)g * p.f6_rows + r) * 104;
       *reinterpret_cast<v3u *>(dst + 12 * j) = v3u{q.w[0], q.w[1], q.w[2]};
-      if (j == 0) {                                       // the GEMM reads the token scale from the row itself: fp16 at byte 96,
-        const float sf = (float)__builtin_bit_cast(half_t, (unsigned short)q.sh);   // the same value as fp32 at byte 100
-        *reinterpret_cast<v2u *>(dst + 96) = v2u{q.sh, __builtin_bit_cast(unsigned, sf)};
-      }
+      if (j == 0) *reinterpret_cast<v2u *>(dst + 96) = f6_scale_words(q.sh);
     } else if constexpr (FMT == 1) {
       // my 16 channels are half `j & 1` of 32-channel block g*4 + j/2: even channels -> chunk 0, odd -> chunk 1
       uint8_t *dst = p.o4 + r * (int64_t)(2 * K4h) + g * 128 + (j >> 1) * 32 + (j & 1) * 8;
@@ -93,17 +90,8 @@ __device__ __forceinline__ void slot_store(const SlotOut<DQ> &q, const ActQuantP
       *reinterpret_cast<v2u *>(p.o4 + r * (int64_t)K4h + g * 64 + j * 8) = v2u{q.w[0], q.w[1]};
     }
   }
-  if (j == 0) {
-    half_t *dst = keeper ? p.s8 : (p.s4 + (int64_t)g * p.ld);
-    const half_t sh = __builtin_bit_cast(half_t, (unsigned short)q.sh);
-    if (p.ref_layout) {
-      const int base = ref_scale_index((int)r);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) dst[base + 2 * k] = sh;
-    } else {
-      dst[r] = sh;
-    }
-  }
+  if (j == 0)
+    store_token_scale(keeper ? p.s8 : (p.s4 + (int64_t)g * p.ld), r, __builtin_bit_cast(half_t, (unsigned short)q.sh), p.ref_layout);
   if constexpr (DQ) {
     v4u *dst = reinterpret_cast<v4u *>(p.xq + r * (int64_t)p.H + e0);
     dst[0] = q.o[0];
@@ -115,40 +103,20 @@ __device__ __forceinline__ void slot_store(const SlotOut<DQ> &q, const ActQuantP
 template <bool SIM, bool DQ, int FMT>
 __device__ __forceinline__ SlotOut<DQ> slot_codes(const float (&v)[16], const ActQuantParams &p, bool keeper) {
   SlotOut<DQ> q;
-  float amax = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-  amax = max8(amax);
-  const GroupScale gs = group_scale<SIM>(amax, keeper, p.clip);
   float tr[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) tr[i] = group_code<SIM>(v[i], gs);
+  const GroupScale gs = group_codes<SIM, max8>(v, keeper, p.clip, tr);
   q.sh = (unsigned)__builtin_bit_cast(unsigned short, f2h(gs.s_store));
   q.w = pack_codes16(tr, keeper);
   if constexpr (FMT == 2) {
     if (!keeper) {
-      // BF6 (E3M2) holds every INT4 code exactly; v_cvt_scalef32_2xpk16_bf6_f32 converts AND packs 32 floats into 6-bit
-      // fields, interleaving its two sources (field 2i = a[i], 2i+1 = b[i]; tools/probes): my 16 codes are fields 0..15
-      typedef float v16f __attribute__((ext_vector_type(16)));
-      typedef unsigned v6u __attribute__((ext_vector_type(6)));
-      v16f ea, eb;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        ea[i] = tr[2 * i];
-        eb[i] = tr[2 * i + 1];
-        ea[8 + i] = 0.f;
-        eb[8 + i] = 0.f;
-      }
-      const v6u f = cvt_2xpk16_bf6(ea, eb);
+      const v6u_t f = bf6_fields(tr);                       // my 16 codes are fields 0..15
       q.w = v4u{f[0], f[1], f[2], 0u};
     }
   }
   if constexpr (DQ) {
-    // code * scale is exact in FP32 (8 x 11 significant bits), so one rounding to half == the reference's half
-    // multiply; "+ 0" turns the -0 of a negative value that rounded to code 0 into the reference's +0
     half_t *ov = reinterpret_cast<half_t *>(q.o);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) ov[i] = (half_t)__builtin_fmaf(tr[i], gs.s_dq, 0.0f);
+    for (int i = 0; i < 16; ++i) ov[i] = dequant_half(tr[i], gs);
   }
   return q;
 }
@@ -184,9 +152,11 @@ __device__ __forceinline__ SlotOut<DQ> slot_codes_h(const unsigned (&z)[8], cons
     }
     q.w = v4u{w[0], w[1], w[2], w[3]};
   } else if constexpr (FMT == 2) {
-    typedef float v16f __attribute__((ext_vector_type(16)));
-    typedef unsigned v6u __attribute__((ext_vector_type(6)));
-    v16f ea, eb;                                          // field 2i = ea[i], 2i + 1 = eb[i]: channel 2i -> ea[i], 2i + 1 -> eb[i]
+    // The half pairs go straight into the two sources of the conversion (bf6_fields's layout: field 2i = ea[i], 2i + 1 = eb[i], the upper
+    // halves zero), not through bf6_fields: two instances compile at exactly 128 VGPRs = 4 waves per SIMD in this form (add + RMSNorm at
+    // hidden 4096 without, and add + RMSNorm with de-quantised output), and at 132 / 129 = 3 waves with the codes unpacked into a float
+    // array first (profiles/quant_shared/isa.txt)
+    v16f_t ea, eb;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const h2v c = __builtin_bit_cast(h2v, t[i]) - h2v{(_Float16)1536.0f, (_Float16)1536.0f};
@@ -196,7 +166,7 @@ __device__ __forceinline__ SlotOut<DQ> slot_codes_h(const unsigned (&z)[8], cons
     }
 #pragma unroll
     for (int i = 8; i < 16; ++i) { ea[i] = 0.f; eb[i] = 0.f; }
-    const v6u f = cvt_2xpk16_bf6(ea, eb);
+    const v6u_t f = cvt_2xpk16_bf6(ea, eb);
     q.w = v4u{f[0], f[1], f[2], 0u};
   } else {
     unsigned w[2];
@@ -231,6 +201,14 @@ __device__ __forceinline__ void quant_slot_h(const unsigned (&z)[8], const ActQu
   slot_store<DQ, FMT>(slot_codes_h<DQ, FMT>(z, p, keeper), p, r, g, j, e0, keeper, K4h);
 }
 
+// The kernel arguments in ONE batch of scalar loads (round 6: hipcc fetched them in two or three, a scalar-cache round trip apart; at
+// decode batches these kernels are a chain of such trips)
+__device__ __forceinline__ void batch_kernel_args(const ActQuantParams &p) {
+  const void *a0 = p.x, *a1 = p.b, *a2 = p.res, *a3 = p.res_out, *a4 = p.idx, *a5 = p.o8, *a6 = p.o4, *a7 = p.s8, *a8_ = p.s4, *a9 = p.xq;
+  const int i0 = (int)p.M, i1 = p.H, i2 = p.ref_layout, i3 = p.w_lds, i4 = (int)gridDim.x, i5 = (int)p.f6_rows, i6 = (int)p.ld;
+  asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(a5), "s"(a6), "s"(a7), "s"(a8_), "s"(a9), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(i4), "s"(i5), "s"(i6));
+}
+
 // reorder / rmsnorm: persistent workgroups, LDS-DMA double buffer.  NP = slots (16 channels) per thread per row.
 // HC != 0: an instance for ONE hidden size (the launcher picks it when p.H == HC).  Everything derived from H folds, and -- what pays --
 // the two row buffers sit at compile-time LDS offsets: the row loop is unrolled by two and a gathered channel's address is its
@@ -239,12 +217,7 @@ __device__ __forceinline__ void quant_slot_h(const unsigned (&z)[8], const ActQu
 template <int OP, bool SIM, bool DQ, int NP, int FMT, int HC = 0>
 __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  {  // the kernel arguments in ONE batch of scalar loads (round 6: hipcc fetched them in two or three, a scalar-cache round trip apart;
-     // at decode batches this kernel is a chain of such trips)
-    const void *a0 = p.x, *a1 = p.b, *a2 = p.res, *a3 = p.res_out, *a4 = p.idx, *a5 = p.o8, *a6 = p.o4, *a7 = p.s8, *a8_ = p.s4, *a9 = p.xq;
-    const int i0 = (int)p.M, i1 = p.H, i2 = p.ref_layout, i3 = p.w_lds, i4 = (int)gridDim.x, i5 = (int)p.f6_rows, i6 = (int)p.ld;
-    asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(a5), "s"(a6), "s"(a7), "s"(a8_), "s"(a9), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(i4), "s"(i5), "s"(i6));
-  }
+  batch_kernel_args(p);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = HC ? HC : p.H;
@@ -377,53 +350,28 @@ __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
     if (rn < rend) issue_row(rn, b ^ 1);
     char *row = smem + b * stage;
 
-    // Sum of squares: a FIXED-SHAPE FP32 tree over the row in memory order (not over the gathered channels, so the reorder index
-    // does not enter): 16-byte chunk c belongs to thread (wave (c / 64) % 4, lane c % 64); a thread folds its chunks in order with
-    // s = fma(x, x, s); lanes combine by the butterfly xor 32, 16, .., 1; the four waves as ((w0 + w1) + w2) + w3.  Deterministic,
-    // restated step by step in oracle/ (r01 used an FP64 sum rounded once: two half-rate instructions per element).
-    float ss = 0.f;
-    if constexpr (ADD) {
-      // x + residual (one fp16 add per element, as torch's half add), written back to the residual stream and kept in
-      // LDS for the gather; the sum of squares is taken here, on the linear data
-      typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-      for (int i = 0; i < 2 * NP; ++i) {
-        const int c = (i * 4 + wave) * 64 + lane;
-        if (c < nchunks) {
-          const h8 a = *reinterpret_cast<const h8 *>(row + c * 16);
-          const h8 rr = *reinterpret_cast<const h8 *>(row + bufbytes + c * 16);
-          const h8 sum = a + rr;
-          *reinterpret_cast<h8 *>(row + c * 16) = sum;
-          *reinterpret_cast<h8 *>(reinterpret_cast<char *>(p.res_out + r * (int64_t)H) + c * 16) = sum;
-#pragma unroll
-          for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)sum[k], (float)sum[k], ss);
-        }
-      }
-      ss = wave_sum_butterfly(ss);
-      if (lane == 0) red[b * 4 + wave] = ss;
-      __syncthreads();                                      // sums visible to the gather, partial sums to everyone
-    } else if constexpr (NORM) {
-      typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-      for (int i = 0; i < 2 * NP; ++i) {
-        const int c = (i * 4 + wave) * 64 + lane;
-        if (c < nchunks) {
-          const h8 a = *reinterpret_cast<const h8 *>(row + c * 16);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)a[k], (float)a[k], ss);
-        }
-      }
-      ss = wave_sum_butterfly(ss);
-      if (lane == 0) red[b * 4 + wave] = ss;
-      __syncthreads();
-    }
-
+    // the sum of squares (quant_math.h) is taken here, on the linear data.  ADD: x + residual first (one fp16 add per element, as
+    // torch's half add), written back to the residual stream and kept in LDS for the gather
     float rinv = 0.f;
     if constexpr (NORM) {
-      const float tot = ((red[b * 4 + 0] + red[b * 4 + 1]) + red[b * 4 + 2]) + red[b * 4 + 3];
-      // correctly rounded divide, sqrt and divide (hipcc default); a power-of-two H divides exactly by multiplying
-      const float var = (H & (H - 1)) == 0 ? tot * (1.0f / (float)H) : tot / (float)H;
-      rinv = rinv_sqrt_exact(var + p.eps);
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < 2 * NP; ++i) {
+        const int c = (i * 4 + wave) * 64 + lane;
+        if (c < nchunks) {
+          h8 a = *reinterpret_cast<const h8 *>(row + c * 16);
+          if constexpr (ADD) {
+            a = a + *reinterpret_cast<const h8 *>(row + bufbytes + c * 16);
+            *reinterpret_cast<h8 *>(row + c * 16) = a;
+            *reinterpret_cast<h8 *>(reinterpret_cast<char *>(p.res_out + r * (int64_t)H) + c * 16) = a;
+          }
+          ss = sumsq8(a, ss);
+        }
+      }
+      ss = wave_sum_butterfly(ss);
+      if (lane == 0) red[b * 4 + wave] = ss;
+      __syncthreads();                                      // (ADD: sums visible to the gather;) partial sums to everyone
+      rinv = rms_rinv(red + b * 4, H, p.eps);
     }
     if constexpr (SIM) {
       // the simulated path in the FP16 domain (quant_math.h): a slot as 8 half pairs, pair i = channels (pair_lo(i), pair_lo(i) + 4)
@@ -436,7 +384,6 @@ __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) xs[k] = *reinterpret_cast<const unsigned short *>(row + off[ps][k]);
             if constexpr (NORM) {
-              // HF LlamaRMSNorm, half opmath: half(x * rinv) from the FP32 product, then a half multiply by the weight
               sim_scale4<0, 0, 0, 0>(xs[0], xs[1], xs[2], xs[3], xs[4], xs[5], xs[6], xs[7], rinv, z[0], z[1], z[2], z[3]);
               sim_scale4<0, 0, 0, 0>(xs[8], xs[9], xs[10], xs[11], xs[12], xs[13], xs[14], xs[15], rinv, z[4], z[5], z[6], z[7]);
             } else {
@@ -496,19 +443,9 @@ __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
     }
     if constexpr (NORM) {
 #pragma unroll
-      for (int ps = 0; ps < NP; ++ps) {
+      for (int ps = 0; ps < NP; ++ps)
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          if constexpr (SIM) {
-            // HF LlamaRMSNorm, half opmath: half(x * rinv) from the FP32 product, then a half multiply by the weight (the exact
-            // product of two halves rounded once: what round_h(w * y) in FP32 gives)
-            const half_t y = f2h((float)xh[ps][k] * rinv);                      // (f2h: the FP32 product is rounded BEFORE the half rounding)
-            x[ps][k] = (float)(half_t)(wg[ps][k] * y);
-          } else {
-            x[ps][k] = round_h(((float)xh[ps][k] * (float)wg[ps][k]) * rinv);           // RMSNorm.cuh:145-151 (two roundings: FP32, then half)
-          }
-        }
-      }
+        for (int k = 0; k < 16; ++k) x[ps][k] = rmsnorm_value<SIM>(xh[ps][k], wg[ps][k], rinv);
     } else {
 #pragma unroll
       for (int ps = 0; ps < NP; ++ps)
@@ -543,12 +480,7 @@ __global__ __launch_bounds__(256) void act_quant2_kernel(ActQuantParams p) {
 template <bool SIM, bool DQ, int FMT>
 __global__ __launch_bounds__(256) void silu_quant2_kernel(ActQuantParams p) {
   const int tid = threadIdx.x;
-  {  // the kernel arguments in ONE batch of scalar loads (round 6: hipcc fetched them in two or three, a scalar-cache round trip apart;
-     // at decode batches this kernel is a chain of such trips)
-    const void *a0 = p.x, *a1 = p.b, *a2 = p.res, *a3 = p.res_out, *a4 = p.idx, *a5 = p.o8, *a6 = p.o4, *a7 = p.s8, *a8_ = p.s4, *a9 = p.xq;
-    const int i0 = (int)p.M, i1 = p.H, i2 = p.ref_layout, i3 = p.w_lds, i4 = (int)gridDim.x, i5 = (int)p.f6_rows, i6 = (int)p.ld;
-    asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(a5), "s"(a6), "s"(a7), "s"(a8_), "s"(a9), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(i4), "s"(i5), "s"(i6));
-  }
+  batch_kernel_args(p);
   // rows by XCD (see act_quant2_kernel): the grid is 8 * ceil(M / 8); XCD x takes rows [x * cm, (x + 1) * cm)
   const int64_t cm = (p.M + 7) >> 3;
   const int64_t r = (blockIdx.x & 7) * cm + (blockIdx.x >> 3);
@@ -636,31 +568,46 @@ static int launch_act_quant2_np(const ActQuantParams &p0, hipStream_t s) {
   return ATOM_OK;
 }
 
-template <int OP, bool SIM, bool DQ, int FMT>
-static int launch_act_quant2_fmt(const ActQuantParams &p, hipStream_t s) {
-  if constexpr (OP == OP_SILU_MUL) {
-    const unsigned parts = p.M <= 1024 ? (unsigned)(((p.H >> 4) + 255) >> 8) : 1u;
-    hipLaunchKernelGGL((silu_quant2_kernel<SIM, DQ, FMT>), dim3((unsigned)(((p.M + 7) >> 3) << 3), parts), dim3(256), 0, s, p);
-    return ATOM_OK;
-  } else {
-    const int np = ((p.H >> 4) + 255) >> 8;
-    // the hidden size of Llama-7B has its own instances of the RMSNorm kernels (same box, 4096 / 65,536 rows: RMSNorm-quant 14.2-14.7 ->
-    // 13.7-13.8 / 160-162 -> 153-156 us, kernel-flavoured 15.0-15.8 -> 14.1-14.2 / 166 -> 158; the plain reorder gains nothing at
-    // 4,096 rows and loses 9 % at 65,536 in the kernel-flavoured mode: it keeps the generic form; profiles/r05/quant_valu.txt)
-    if constexpr (OP != OP_REORDER) {
-      if (np == 1 && p.H == 4096) return launch_act_quant2_np<OP, SIM, DQ, 1, FMT, 4096>(p, s);
-    }
-    if (np == 1) return launch_act_quant2_np<OP, SIM, DQ, 1, FMT>(p, s);
-    if (np == 2) return launch_act_quant2_np<OP, SIM, DQ, 2, FMT>(p, s);
-    if (np == 3) return launch_act_quant2_np<OP, SIM, DQ, 3, FMT>(p, s);
-    return launch_act_quant2_np<OP, SIM, DQ, 4, FMT>(p, s);
-  }
+// f(std::integral_constant<int, v>()) for v in 0 .. N - 1: a run-time choice as a template argument (any other v is an error)
+template <int N, class F>
+static int with_constant(int v, F f) {
+  if constexpr (N == 0) return ATOM_ERR_INVALID_ARG;
+  else return v == N - 1 ? f(std::integral_constant<int, N - 1>()) : with_constant<N - 1>(v, f);
 }
-template <int OP, bool SIM, bool DQ>
-static int launch_act_quant2(const ActQuantParams &p, hipStream_t s) {
-  if (p.f6_rows) return launch_act_quant2_fmt<OP, SIM, DQ, 2>(p, s);
-  if (p.wide) return launch_act_quant2_fmt<OP, SIM, DQ, 1>(p, s);
-  return launch_act_quant2_fmt<OP, SIM, DQ, 0>(p, s);
+
+// the kernel instance of (op, mode, de-quantised output, code format) -- one index over the 4 x 2 x 2 x 3 of them -- and, for the row
+// kernels, of the slots per thread
+static int launch_act_quant2(int op, const ActQuantParams &p, hipStream_t s) {
+  if (op < OP_REORDER || op > OP_ADD_RMSNORM) return ATOM_ERR_INVALID_ARG;
+  const int fmt = p.f6_rows ? 2 : (p.wide ? 1 : 0);
+  return with_constant<48>(((op * 2 + (p.sim != 0)) * 2 + (p.xq != nullptr)) * 3 + fmt, [&](auto inst) {
+    constexpr int I = decltype(inst)::value, OP = I / 12, FMT = I % 3;
+    constexpr bool SIM = (I / 6) % 2 != 0, DQ = (I / 3) % 2 != 0;
+    if constexpr (OP == OP_SILU_MUL) {
+      const unsigned parts = p.M <= 1024 ? (unsigned)(((p.H >> 4) + 255) >> 8) : 1u;
+      hipLaunchKernelGGL((silu_quant2_kernel<SIM, DQ, FMT>), dim3((unsigned)(((p.M + 7) >> 3) << 3), parts), dim3(256), 0, s, p);
+      return (int)ATOM_OK;
+    } else {
+      // the hidden size of Llama-7B has its own instances of the RMSNorm kernels (same box, 4096 / 65,536 rows: RMSNorm-quant 14.2-14.7 ->
+      // 13.7-13.8 / 160-162 -> 153-156 us, kernel-flavoured 15.0-15.8 -> 14.1-14.2 / 166 -> 158; the plain reorder gains nothing at
+      // 4,096 rows and loses 9 % at 65,536 in the kernel-flavoured mode: it keeps the generic form; profiles/r05/quant_valu.txt)
+      if constexpr (OP != OP_REORDER) {
+        if (p.H == 4096) return launch_act_quant2_np<OP, SIM, DQ, 1, FMT, 4096>(p, s);
+      }
+      const int np = ((p.H >> 4) + 255) >> 8;             // slots per thread: 1 .. 4 (H <= 16384)
+      return with_constant<4>(np - 1, [&](auto np1) { return launch_act_quant2_np<OP, SIM, DQ, decltype(np1)::value + 1, FMT>(p, s); });
+    }
+  });
+}
+
+// the fields every op shares: the shape, the clip and the outputs
+static ActQuantParams act_quant_params(const void *x, int64_t M, int hidden, float clip, void *o_outliers, void *o_norms,
+                                       void *outlier_scales, void *norm_scales, void *xq_f16) {
+  ActQuantParams p{};
+  p.x = (const half_t *)x; p.M = M; p.H = hidden; p.clip = clip;
+  p.o8 = (int8_t *)o_outliers; p.o4 = (uint8_t *)o_norms; p.s8 = (half_t *)outlier_scales;
+  p.s4 = (half_t *)norm_scales; p.xq = (half_t *)xq_f16;
+  return p;
 }
 
 static int launch_act_quant(int op, ActQuantParams p, int quant_mode, int scale_layout, void *stream) {
@@ -682,20 +629,7 @@ static int launch_act_quant(int op, ActQuantParams p, int quant_mode, int scale_
   p.sim = quant_mode == ATOM_QUANT_SIM;
   p.ref_layout = scale_layout == ATOM_SCALE_LAYOUT_REF;
   p.ld = (int64_t)atom_scale_size(p.M, scale_layout);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int st = ATOM_OK;
-#define ATOM_LAUNCH2(OPV)                                                  \
-  if (p.sim && p.xq) st = launch_act_quant2<OPV, true, true>(p, s);        \
-  else if (p.sim) st = launch_act_quant2<OPV, true, false>(p, s);          \
-  else if (p.xq) st = launch_act_quant2<OPV, false, true>(p, s);           \
-  else st = launch_act_quant2<OPV, false, false>(p, s);
-  switch (op) {
-    case OP_REORDER: ATOM_LAUNCH2(OP_REORDER) break;
-    case OP_RMSNORM: ATOM_LAUNCH2(OP_RMSNORM) break;
-    case OP_ADD_RMSNORM: ATOM_LAUNCH2(OP_ADD_RMSNORM) break;
-    default: ATOM_LAUNCH2(OP_SILU_MUL) break;
-  }
-#undef ATOM_LAUNCH2
+  const int st = launch_act_quant2(op, p, reinterpret_cast<hipStream_t>(stream));
   return st != ATOM_OK ? st : check_launch();
 }
 
@@ -990,8 +924,6 @@ struct RepackF6Pair { RepackF6Params op[2]; };
 __global__ __launch_bounds__(256) void repack_f6_kernel(RepackF6Pair pp) {
   const RepackF6Params &p = pp.op[blockIdx.z];
   if ((int64_t)blockIdx.x * 256 >= p.rows_pad) return;
-  typedef float v16f __attribute__((ext_vector_type(16)));
-  typedef unsigned v6u __attribute__((ext_vector_type(6)));
   __shared__ __attribute__((aligned(16))) unsigned char rec[256 * 104];
   const int g = blockIdx.y;
   const int64_t n0 = (int64_t)blockIdx.x * 256;
@@ -1002,24 +934,19 @@ __global__ __launch_bounds__(256) void repack_f6_kernel(RepackF6Pair pp) {
     const uint8_t *src = p.B4 + n * p.K4h + g * 64;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                          // 32 codes = 16 packed bytes -> 24 bytes
-      const v4u raw = *reinterpret_cast<const v4u *>(src + 16 * q);
-      v16f ea, eb;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const unsigned byte = (raw[i >> 2] >> (8 * (i & 3))) & 0xFF;
-        ea[i] = (float)((int)(byte << 28) >> 28);          // element 2i: low nibble, sign-extended
-        eb[i] = (float)((int)(byte << 24) >> 28);          // element 2i+1: high nibble
-      }
+      v16f_t ea, eb;
+      nibbles16_to_f32x32(*reinterpret_cast<const v4u *>(src + 16 * q), ea, eb);
       // (the builtin, not cvt_2xpk16_bf6: see common.h -- guarded by the disassembly check in tests/test_abi_cpu.py)
-      const v6u f = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(ea, eb, 1.0f);
+      const v6u_t f = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(ea, eb, 1.0f);
 #pragma unroll
       for (int k = 0; k < 6; ++k) dst[6 * q + k] = f[k];
     }
     unsigned sc = 0u, sc32 = 0u;
     if (p.scale) {
       const half_t sv = p.scale[(int64_t)g * p.ld + (p.ref_layout ? ref_scale_index((int)n) : (int)n)];
-      sc = (unsigned)__builtin_bit_cast(unsigned short, sv);
-      sc32 = __builtin_bit_cast(unsigned, (float)sv);
+      const v2u w = f6_scale_words(__builtin_bit_cast(unsigned short, sv));
+      sc = w[0];
+      sc32 = w[1];
     }
     dst[24] = sc;
     dst[25] = sc32;
@@ -1039,8 +966,6 @@ __global__ __launch_bounds__(256) void repack_f6_kernel(RepackF6Pair pp) {
 // (rows / 256) x G workgroups of one row per thread, which is 31 workgroups on a 256-CU chip at 256 x 4096.  Rows [rows, 64-row block
 // end) are zero records, rows beyond are not written (pad rows of an F6 operand may hold any bytes, include/atom_hip.h).
 __global__ __launch_bounds__(256) void repack_f6_rows64_kernel(RepackF6Params p) {
-  typedef float v16f __attribute__((ext_vector_type(16)));
-  typedef unsigned v6u __attribute__((ext_vector_type(6)));
   __shared__ __attribute__((aligned(16))) unsigned char rec[64 * 104];
   const int g = blockIdx.y;
   const int64_t n0 = (int64_t)blockIdx.x * 64;
@@ -1048,21 +973,16 @@ __global__ __launch_bounds__(256) void repack_f6_rows64_kernel(RepackF6Params p)
   const int64_t n = n0 + r;
   unsigned *dst = reinterpret_cast<unsigned *>(rec + r * 104);
   if (n < p.N) {
-    const v4u raw = *reinterpret_cast<const v4u *>(p.B4 + n * p.K4h + g * 64 + 16 * q);
-    v16f ea, eb;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const unsigned byte = (raw[i >> 2] >> (8 * (i & 3))) & 0xFF;
-      ea[i] = (float)((int)(byte << 28) >> 28);
-      eb[i] = (float)((int)(byte << 24) >> 28);
-    }
-    const v6u f = cvt_2xpk16_bf6(ea, eb);
+    v16f_t ea, eb;
+    nibbles16_to_f32x32(*reinterpret_cast<const v4u *>(p.B4 + n * p.K4h + g * 64 + 16 * q), ea, eb);
+    const v6u_t f = cvt_2xpk16_bf6(ea, eb);
 #pragma unroll
     for (int k = 0; k < 6; ++k) dst[6 * q + k] = f[k];
     if (q == 0) {
       const half_t sv = p.scale[(int64_t)g * p.ld + (p.ref_layout ? ref_scale_index((int)n) : (int)n)];
-      dst[24] = (unsigned)__builtin_bit_cast(unsigned short, sv);
-      dst[25] = __builtin_bit_cast(unsigned, (float)sv);
+      const v2u sc = f6_scale_words(__builtin_bit_cast(unsigned short, sv));
+      dst[24] = sc[0];
+      dst[25] = sc[1];
     }
   } else {
 #pragma unroll
@@ -1118,8 +1038,6 @@ __global__ __launch_bounds__(256) void check_scale_pairs_kernel(const half_t *sB
 // the F6 weight form [G][rows_pad][104] (+ float32 scales [G][rows_pad] behind it) against what atom_repack_weight_f6s makes of the
 // packed weight: one thread per (row < N, group) re-codes its 128 codes and compares the record and the scale (pad rows: not compared)
 __global__ __launch_bounds__(256) void verify_weight_f6s_kernel(RepackF6Params p, const uint8_t *have, int32_t *n_bad) {
-  typedef float v16f __attribute__((ext_vector_type(16)));
-  typedef unsigned v6u __attribute__((ext_vector_type(6)));
   const int g = blockIdx.y;
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= p.N) return;
@@ -1128,15 +1046,9 @@ __global__ __launch_bounds__(256) void verify_weight_f6s_kernel(RepackF6Params p
   int bad = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const v4u raw = *reinterpret_cast<const v4u *>(src + 16 * q);
-    v16f ea, eb;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const unsigned byte = (raw[i >> 2] >> (8 * (i & 3))) & 0xFF;
-      ea[i] = (float)((int)(byte << 28) >> 28);
-      eb[i] = (float)((int)(byte << 24) >> 28);
-    }
-    const v6u f = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(ea, eb, 1.0f);
+    v16f_t ea, eb;
+    nibbles16_to_f32x32(*reinterpret_cast<const v4u *>(src + 16 * q), ea, eb);
+    const v6u_t f = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(ea, eb, 1.0f);
 #pragma unroll
     for (int k = 0; k < 6; ++k) bad |= rec[6 * q + k] != f[k];
   }
@@ -1174,10 +1086,8 @@ size_t atom_scale_size(int64_t rows, int scale_layout) {
 int atom_reorder_quant_f16(const void *x, const int16_t *reorder_index, int64_t M, int hidden, int quant_mode,
                            float clip, int scale_layout, void *o_outliers, void *o_norms, void *outlier_scales,
                            void *norm_scales, void *xq_f16, void *stream) {
-  ActQuantParams p{};
-  p.x = (const half_t *)x; p.idx = reorder_index; p.M = M; p.H = hidden; p.clip = clip;
-  p.o8 = (int8_t *)o_outliers; p.o4 = (uint8_t *)o_norms; p.s8 = (half_t *)outlier_scales;
-  p.s4 = (half_t *)norm_scales; p.xq = (half_t *)xq_f16;
+  ActQuantParams p = act_quant_params(x, M, hidden, clip, o_outliers, o_norms, outlier_scales, norm_scales, xq_f16);
+  p.idx = reorder_index;
   return launch_act_quant(OP_REORDER, p, quant_mode, scale_layout, stream);
 }
 
@@ -1185,11 +1095,8 @@ int atom_rmsnorm_reorder_quant_f16(const void *x, const void *weight, float eps,
                                    int64_t M, int hidden, int quant_mode, float clip, int scale_layout,
                                    void *o_outliers, void *o_norms, void *outlier_scales, void *norm_scales,
                                    void *xq_f16, void *stream) {
-  ActQuantParams p{};
-  p.x = (const half_t *)x; p.b = (const half_t *)weight; p.eps = eps; p.idx = reorder_index; p.M = M;
-  p.H = hidden; p.clip = clip;
-  p.o8 = (int8_t *)o_outliers; p.o4 = (uint8_t *)o_norms; p.s8 = (half_t *)outlier_scales;
-  p.s4 = (half_t *)norm_scales; p.xq = (half_t *)xq_f16;
+  ActQuantParams p = act_quant_params(x, M, hidden, clip, o_outliers, o_norms, outlier_scales, norm_scales, xq_f16);
+  p.b = (const half_t *)weight; p.eps = eps; p.idx = reorder_index;
   return launch_act_quant(OP_RMSNORM, p, quant_mode, scale_layout, stream);
 }
 
@@ -1197,22 +1104,17 @@ int atom_add_rmsnorm_reorder_quant_f16(const void *x, const void *residual, void
                                        float eps, const int16_t *reorder_index, int64_t M, int hidden, int quant_mode, float clip,
                                        int scale_layout, void *o_outliers, void *o_norms, void *outlier_scales,
                                        void *norm_scales, void *xq_f16, void *stream) {
-  ActQuantParams p{};
-  p.x = (const half_t *)x; p.res = (const half_t *)residual; p.res_out = (half_t *)residual_out;
-  p.b = (const half_t *)weight; p.eps = eps;
-  p.idx = reorder_index; p.M = M; p.H = hidden; p.clip = clip;
-  p.o8 = (int8_t *)o_outliers; p.o4 = (uint8_t *)o_norms; p.s8 = (half_t *)outlier_scales;
-  p.s4 = (half_t *)norm_scales; p.xq = (half_t *)xq_f16;
+  ActQuantParams p = act_quant_params(x, M, hidden, clip, o_outliers, o_norms, outlier_scales, norm_scales, xq_f16);
+  p.res = (const half_t *)residual; p.res_out = (half_t *)residual_out;
+  p.b = (const half_t *)weight; p.eps = eps; p.idx = reorder_index;
   return launch_act_quant(OP_ADD_RMSNORM, p, quant_mode, scale_layout, stream);
 }
 
 int atom_silu_mul_quant_f16(const void *a, const void *b, int64_t M, int hidden, int quant_mode, float clip,
                             int scale_layout, void *o_outliers, void *o_norms, void *outlier_scales,
                             void *norm_scales, void *xq_f16, void *stream) {
-  ActQuantParams p{};
-  p.x = (const half_t *)a; p.b = (const half_t *)b; p.M = M; p.H = hidden; p.clip = clip;
-  p.o8 = (int8_t *)o_outliers; p.o4 = (uint8_t *)o_norms; p.s8 = (half_t *)outlier_scales;
-  p.s4 = (half_t *)norm_scales; p.xq = (half_t *)xq_f16;
+  ActQuantParams p = act_quant_params(a, M, hidden, clip, o_outliers, o_norms, outlier_scales, norm_scales, xq_f16);
+  p.b = (const half_t *)b;
   return launch_act_quant(OP_SILU_MUL, p, quant_mode, scale_layout, stream);
 }
 

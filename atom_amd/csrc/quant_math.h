@@ -1,5 +1,8 @@
-// The per-group quantisation arithmetic of the fused activation ops, shared by quant_kernels.hip and the GEMM epilogue that fuses
-// SiLU x up -> quant behind gate_proj / up_proj (gemm_w4a4_f6.hip).  Two modes, specified op by op and restated in oracle/:
+// THE statement of the activation quantisers' arithmetic: every step between a row of fp16 values and the codes, scales and records
+// that leave a quantiser is written here once, as a pure device function (the only memory traffic: the steps that ARE stores).  The
+// kernels that contain a quantiser -- quant_kernels.hip (stand-alone launches, re-coding), gemvq_w4a4.hip and gemm_w4a4_skinny.hip
+// (quantiser in front of a decode GEMM), gemm_w4a4_f6.hip (SiLU x up -> quant behind gate_proj / up_proj) -- differ only in how the
+// values reach these functions and where the codes go.  Two modes, specified op by op and restated in oracle/:
 //   SIM     the simulated path (model/quant.py:134-181): FP16 opmath -- amax.clamp(1e-5) * clip, scale = amax / qmax, every step
 //           rounded to half; code = clamp(round_half_even(x / scale))
 //   kernel  the CUDA kernels (Reorder.cuh:137-178 == Activate.cuh:112-167): FP32, scale = amax * clip / qmax,
@@ -67,33 +70,42 @@ __device__ __forceinline__ float group_code(float v, const GroupScale &g) {
   }
 }
 
-// 16 codes (integer-valued floats) of one slot -> packed words, exact integer arithmetic in FP32: INT4 two's-complement nibbles,
-// channel k of the slot at bits 4 (k % 8) of word k / 8 (2 words); INT8 keeper bytes, channel k at byte k % 4 of word k / 4 (4 words)
+// Codes (integer-valued floats) -> packed words, exact integer arithmetic in FP32 (bias folded into the initial value, two's complement
+// restored with one XOR per word): 4 codes -> one word of INT8 keeper bytes, code k at byte k; 8 codes -> one word of INT4 nibbles,
+// code k at bits 4 k
+__device__ __forceinline__ unsigned pack_bytes4(const float *tr) {
+  const float lo = __builtin_fmaf(tr[1], 256.f, tr[0] + 32896.f);                        // (c0+128) + (c1+128)*256
+  const float hi = __builtin_fmaf(tr[3], 256.f, tr[2] + 32896.f);
+  return ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x80808080u;
+}
+__device__ __forceinline__ unsigned pack_nibbles8(const float *tr) {
+  float lo = 34952.f, hi = 34952.f;                                                      // sum 8*16^i, i<4
+  lo = __builtin_fmaf(tr[0], 1.f, lo);
+  lo = __builtin_fmaf(tr[1], 16.f, lo);
+  lo = __builtin_fmaf(tr[2], 256.f, lo);
+  lo = __builtin_fmaf(tr[3], 4096.f, lo);
+  hi = __builtin_fmaf(tr[4], 1.f, hi);
+  hi = __builtin_fmaf(tr[5], 16.f, hi);
+  hi = __builtin_fmaf(tr[6], 256.f, hi);
+  hi = __builtin_fmaf(tr[7], 4096.f, hi);
+  return ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x88888888u;
+}
+// 8 codes: the nibble word (in [0]) or the two keeper words
+__device__ __forceinline__ v2u pack_codes8(const float *tr, bool keeper) {
+  if (keeper) return v2u{pack_bytes4(tr), pack_bytes4(tr + 4)};
+  return v2u{pack_nibbles8(tr), 0u};
+}
+// the 16 codes of one slot: channel k at nibble k % 8 of word k / 8 (2 words), or at keeper byte k % 4 of word k / 4 (4 words)
 __device__ __forceinline__ v4u pack_codes16(const float (&tr)[16], bool keeper) {
   if (keeper) {
     unsigned w[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float lo = __builtin_fmaf(tr[4 * k + 1], 256.f, tr[4 * k] + 32896.f);        // (c0+128) + (c1+128)*256
-      const float hi = __builtin_fmaf(tr[4 * k + 3], 256.f, tr[4 * k + 2] + 32896.f);
-      w[k] = ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x80808080u;
-    }
+    for (int k = 0; k < 4; ++k) w[k] = pack_bytes4(tr + 4 * k);
     return v4u{w[0], w[1], w[2], w[3]};
   }
   unsigned w[2];
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    float lo = 34952.f, hi = 34952.f;                                                    // sum 8*16^i, i<4
-    lo = __builtin_fmaf(tr[8 * k + 0], 1.f, lo);
-    lo = __builtin_fmaf(tr[8 * k + 1], 16.f, lo);
-    lo = __builtin_fmaf(tr[8 * k + 2], 256.f, lo);
-    lo = __builtin_fmaf(tr[8 * k + 3], 4096.f, lo);
-    hi = __builtin_fmaf(tr[8 * k + 4], 1.f, hi);
-    hi = __builtin_fmaf(tr[8 * k + 5], 16.f, hi);
-    hi = __builtin_fmaf(tr[8 * k + 6], 256.f, hi);
-    hi = __builtin_fmaf(tr[8 * k + 7], 4096.f, hi);
-    w[k] = ((unsigned)lo | ((unsigned)hi << 16)) ^ 0x88888888u;
-  }
+  for (int k = 0; k < 2; ++k) w[k] = pack_nibbles8(tr + 8 * k);
   return v4u{w[0], w[1], 0u, 0u};
 }
 
@@ -108,6 +120,79 @@ __device__ __forceinline__ float max8(float a) {   // max over the aligned 8 lan
   return a;
 }
 
+// ... and over the aligned 16 lanes (one DPP row): exact, order-free
+__device__ __forceinline__ float max16(float a) {
+  a = max8(a);
+  a = fmaxf(a, dpp_f<0x140>(a));                      // row_mirror: lanes 8-15 <-> 7-0 of the row
+  return a;
+}
+
+// One thread's N values of a quantisation group -> their codes tr (integer-valued floats) and the group's scale: amax over the values,
+// `reduce` over the lanes that share the group (max8: 16 values per lane, max16: 8), group_scale, group_code
+template <bool SIM, float (&reduce)(float), int N>
+__device__ __forceinline__ GroupScale group_codes(const float (&v)[N], bool keeper, float clip, float (&tr)[N]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  amax = reduce(amax);
+  const GroupScale gs = group_scale<SIM>(amax, keeper, clip);
+#pragma unroll
+  for (int i = 0; i < N; ++i) tr[i] = group_code<SIM>(v[i], gs);
+  return gs;
+}
+
+// The de-quantised value of a code: code * scale is exact in FP32 (8 x 11 significant bits), so one rounding to half == the reference's
+// half multiply; "+ 0" turns the -0 of a negative value that rounded to code 0 into the reference's +0
+__device__ __forceinline__ half_t dequant_half(float code, const GroupScale &gs) { return (half_t)__builtin_fmaf(code, gs.s_dq, 0.0f); }
+
+// N <= 32 codes -> the first N 6-bit fields of one BF6 conversion (the rest zero).  BF6 (E3M2) holds every INT4 code exactly;
+// v_cvt_scalef32_2xpk16_bf6_f32 converts AND packs 32 floats, interleaving its two sources (field 2i = a[i], 2i+1 = b[i]; tools/probes)
+template <int N>
+__device__ __forceinline__ v6u_t bf6_fields(const float (&tr)[N]) {
+  v16f_t ea, eb;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    ea[i] = 2 * i < N ? tr[2 * i] : 0.f;
+    eb[i] = 2 * i < N ? tr[2 * i + 1] : 0.f;
+  }
+  return cvt_2xpk16_bf6(ea, eb);
+}
+// 16 packed bytes = 32 INT4 codes -> the two sources of that conversion: byte i = fields 2i (low nibble) and 2i+1, sign-extended
+__device__ __forceinline__ void nibbles16_to_f32x32(v4u raw, v16f_t &ea, v16f_t &eb) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const unsigned byte = (raw[i >> 2] >> (8 * (i & 3))) & 0xFF;
+    ea[i] = (float)((int)(byte << 28) >> 28);
+    eb[i] = (float)((int)(byte << 24) >> 28);
+  }
+}
+// the scale words of a BF6 record: the GEMM reads the token scale from the row itself, fp16 at byte 96, the same value as fp32 at byte 100
+__device__ __forceinline__ v2u f6_scale_words(unsigned sh) {
+  return v2u{sh, __builtin_bit_cast(unsigned, (float)__builtin_bit_cast(half_t, (unsigned short)sh))};
+}
+// a token's scale into a per-group scale vector: plain [rows], or the reference layout's four replicas (Reorder.cuh:39-44)
+__device__ __forceinline__ void store_token_scale(half_t *dst, int64_t row, half_t s, int ref_layout) {
+  if (ref_layout) {
+    const int base = ref_scale_index((int)row);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[base + 2 * k] = s;
+  } else {
+    dst[row] = s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// RMSNorm in front of the codes.  Sum of squares: a FIXED-SHAPE FP32 tree over the row in memory order (not over the gathered channels,
+// so the reorder index does not enter): 16-byte chunk c belongs to thread (wave (c / 64) % 4, lane c % 64) of 256; a thread folds its
+// chunks in order with s = fma(x, x, s); lanes combine by the butterfly xor 32, 16, .., 1 (wave_sum_butterfly); the four waves as
+// ((w0 + w1) + w2) + w3.  Deterministic, restated step by step in oracle/ (r01 used an FP64 sum rounded once: two half-rate
+// instructions per element).
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ float sumsq8(h8 v, float ss) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) ss = __builtin_fmaf((float)v[k], (float)v[k], ss);
+  return ss;
+}
 // 1.0f / sqrtf(x), BOTH operations correctly rounded (what hipcc's default expansion delivers and the oracle restates), without the
 // range handling of that expansion: for 2^-64 <= x <= 2^64 -- every RMSNorm statistic `mean(x^2) + eps` of fp16 data with a sane eps --
 // v_sqrt_f32's result is off by at most one ulp and the two residual tests below pick the correctly rounded neighbour (the compiler's
@@ -127,6 +212,28 @@ __device__ __forceinline__ float rinv_sqrt_exact(float x) {
   float q = r;                                              // 1.0f * r
   q = __builtin_fmaf(__builtin_fmaf(-y, q, 1.0f), r, q);
   return __builtin_fmaf(__builtin_fmaf(-y, q, 1.0f), r, q);
+}
+
+// the four waves' partial sums -> 1 / sqrt(mean + eps): correctly rounded divide, sqrt and divide (hipcc default); a power-of-two H
+// divides exactly by multiplying
+__device__ __forceinline__ float rms_rinv(const float *red4, int H, float eps) {
+  const float tot = ((red4[0] + red4[1]) + red4[2]) + red4[3];
+  const float var = (H & (H - 1)) == 0 ? tot * (1.0f / (float)H) : tot / (float)H;
+  return rinv_sqrt_exact(var + eps);
+}
+// One normalised value.  kernel: RMSNorm.cuh:145-151, (x * w) * rinv in FP32, then half -- TWO roundings.  SIM: HF LlamaRMSNorm in
+// half opmath, half(x * rinv) from the FP32 product (two roundings again), then a half multiply by the weight (the exact product of
+// two halves rounded once).  round_h / f2h keep hipcc from fusing product and conversion into v_fma_mixlo_f16, which rounds the exact
+// product ONCE: a different half wherever the FP32 rounding lands on the midpoint of two halves, ~6e-5 of all values, one code or scale
+// in a million (rounds 4-6 had it; found by the row-loop tests at 6181 rows).  sim_scale1 below is the SIM form on half pairs.
+template <bool SIM>
+__device__ __forceinline__ float rmsnorm_value(half_t x, half_t w, float rinv) {
+  if constexpr (SIM) {
+    const half_t y = f2h((float)x * rinv);
+    return (float)(half_t)(w * y);
+  } else {
+    return round_h(((float)x * (float)w) * rinv);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -214,11 +321,8 @@ __device__ __forceinline__ float max8_dpp(float a) {
   return a;
 }
 
-// y = half(float(x) * rinv) for four pairs: pair i takes the low (HI = 0) or high (HI = 1) halves of xl[i] and xh[i].  TWO roundings, as
-// torch's half opmath has them (HF LlamaRMSNorm: the FP32 product, then .to(half)): the product is rounded to FP32 and that value to
-// half.  v_fma_mixlo/hi_f16 -- one instruction, and what hipcc makes of (half)(x * r) unasked -- rounds the exact 35-bit product ONCE:
-// a different half wherever the FP32 rounding lands on the midpoint of two halves, ~6e-5 of all values, one code or scale in a million
-// (rounds 4-6 had it; found by the row-loop tests at 6181 rows).  opaque() keeps the compiler from fusing the two.
+// y = half(float(x) * rinv) for four pairs: pair i takes the low (HI = 0) or high (HI = 1) halves of xl[i] and xh[i].  Two roundings,
+// as in rmsnorm_value<true>: opaque() keeps the compiler from fusing the FP32 product and the conversion.
 template <int HI>
 __device__ __forceinline__ unsigned sim_scale1(unsigned xl, unsigned xh, float rinv) {
   const h2v a = __builtin_bit_cast(h2v, xl), b = __builtin_bit_cast(h2v, xh);

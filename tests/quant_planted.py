@@ -44,6 +44,12 @@ TAIL_H = 1024
 NORM_HS = [1024, 4096]
 # dense_layer_gemm_i4_multi_q: (q_op, N, K, nseg) -- the small shapes of test_quantiser_inside_the_gemm_launch_equals_quantiser_then_gemm
 MULTI_Q_CASES = [("reorder", 64, 256, 1), ("rmsnorm", 1408, 640, 2), ("silu_mul", 512, 1408, 1), ("add_rmsnorm", 256, 5120, 3)]
+# ... and every op on the other side of MULTI_Q_DOT_K.  One token runs the quantiser inside the dot-product kernel; two tokens run the one
+# inside the decode-batch kernel up to K = MULTI_Q_DOT_K and the dot-product kernel's beyond: with these, every op's planted rows reach
+# both quantisers at two tokens (the GPU test asserts the route).  The tie rows and the searched rows are built per group and hold at
+# any H; the CPU tests keep their hidden sizes (of the random edge rows fewer survive SiLU's division by 32 unchanged at H = 4352).
+MULTI_Q_DOT_K = 4096
+MULTI_Q_ROUTE_CASES = [("add_rmsnorm", 256, 1024, 1), ("reorder", 64, 4352, 1), ("rmsnorm", 64, 4352, 1), ("silu_mul", 64, 4352, 1)]
 
 
 def applies(mutant, op, mode, clip, dequant=True):

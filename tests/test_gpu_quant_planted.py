@@ -98,7 +98,7 @@ def _fused(N, K, nseg):
 
 @pytest.mark.parametrize("M", [1, 2])
 @pytest.mark.parametrize("clip", [1.0, 0.9])
-@pytest.mark.parametrize("op,N,K,nseg", P.MULTI_Q_CASES)
+@pytest.mark.parametrize("op,N,K,nseg", P.MULTI_Q_CASES + P.MULTI_Q_ROUTE_CASES)
 def test_quantisers_inside_the_gemm_launch_on_planted_rows(op, N, K, nseg, clip, M):
     """atom_gemm_w4a4_multi_q: the planted rows, M at a time, against the separate quantiser op followed by atom_gemm_w4a4_multi, bit
     for bit (in the summation order the separate entry points take for the token count: see
@@ -142,6 +142,7 @@ def test_quantisers_inside_the_gemm_launch_on_planted_rows(op, N, K, nseg, clip,
     qt, _ = separate(every)
     assert_quant_equal(qt, ref, R, layout="ref", what=f"{op} (separate op) clip={clip} K={K}")
     dot = ops.L.lib().atom_gemm_w4a4_packed_order(M, N * nseg, K, 0) == 64
+    assert dot == (M == 1 or K > P.MULTI_Q_DOT_K), "the planted rows no longer reach the quantiser of the kernel this case is here for"
     rep = 1 if dot else 2                                      # the decode-batch kernel needs two rows more: the tokens twice over
     for r0 in range(0, R - M + 1, M):
         rows = every[r0:r0 + M]
