@@ -69,5 +69,46 @@ def exact_inputs(rows, h1, h2, rank, capacity, layers, seed, guard=0):
     return ri(-8, 8, rows + guard, h2), ri(-2, 2, rows + guard, h1), ri(-1, 1, capacity, layers, rank, h1), ri(-1, 1, capacity, layers, h2, rank)
 
 
+LONG_S, LONG_FIRST, LONG_GUARD, LONG_CAP, LONG_LAYERS, LONG_LAYER = 200, 5, 8, 3, 2, 1
+LONG_SENTINEL = 0x7BFF                       # fp16 65504 in the guard rows: survives only if they are never written
+_LONG_LENS = (0, 1, 2, 3, 5, 15, 16, 17, 33)
+_LONG_IDS = (2, 0, -1, 1, 3, 0, 1, -1, 2, 7, 1, 0)          # cyclically, no two neighbours name the same adapter (-1, 3 and 7: none)
+
+
+def long_table():
+    """(seg_indptr [S + 1], ids [S]) of a table longer than the 64 segments the kernels search at a time: S = 200; segments 0 .. 63
+    and 128 .. 199 of 0, 1, 2, 3, 5, 15, 16, 17 and 33 rows in turn, 64 .. 127 all empty; the first segment starts at row 5 (and is
+    empty itself); ids in no order, with -1 and ids at and above the capacity of 3.  The caller adds LONG_GUARD rows behind
+    seg_indptr[S]"""
+    lens = [0 if 64 <= s < 128 else _LONG_LENS[s % len(_LONG_LENS)] for s in range(LONG_S)]
+    ids = [_LONG_IDS[s % len(_LONG_IDS)] for s in range(LONG_S)]
+    ptr = [LONG_FIRST]
+    for n in lens:
+        ptr.append(ptr[-1] + n)
+    assert ptr[-1] >= LONG_S and min(ids) < 0 and max(ids) >= LONG_CAP and sorted(ids) != ids
+    assert set(lens[:64]) == set(lens[128:]) == set(_LONG_LENS) and lens[0] == 0
+    return ptr, ids
+
+
+def long_ids_shifted(ids):
+    """the ids a search that loses its carried tile count would honour in the third block of 64 segments (128 .. 199): each segment
+    there gets its neighbour's adapter"""
+    n = LONG_S - 128
+    return ids[:128] + [ids[128 + (s + 1) % n] for s in range(n)]
+
+
+def long_case(rank, h1=320, h2=192):
+    """exact inputs on the rows of ``long_table`` + the guard rows: (y, x, wa, wb) of add_lora h1 -> rank -> h2, and (y_s [rows, rank],
+    x_e [rows, rank]) to run the two passes alone (shrink: y_s += x wa^T; expand: y += x_e wb^T); guard rows of y and y_s hold
+    LONG_SENTINEL"""
+    ptr, _ = long_table()
+    y, x, wa, wb = exact_inputs(ptr[-1], h1, h2, rank, LONG_CAP, LONG_LAYERS, seed=700 + rank, guard=LONG_GUARD)
+    g = torch.Generator().manual_seed(800 + rank)
+    y_s = torch.randint(-8, 9, (y.size(0), rank), generator=g).half()
+    x_e = torch.randint(-2, 3, (y.size(0), rank), generator=g).half()
+    y[ptr[-1]:] = y_s[ptr[-1]:] = torch.tensor([LONG_SENTINEL], dtype=torch.int16).view(torch.float16)
+    return y, x, wa, wb, y_s, x_e
+
+
 def bits(t):
     return t.contiguous().view(torch.int16)

@@ -1,5 +1,5 @@
-"""Torch-CPU restatement of the sparse mixture-of-experts block (checker side only): float softmax over the router logits, topk,
-renormalise, ``.half()``; rows grouped by expert in ascending token order; every expert output times its fp16 routing weight, added
+"""Torch-CPU restatement of the sparse mixture-of-experts block (checker side only): float softmax over the router logits, the top_k
+largest (the lower index of equal ones), renormalise, ``.half()``; rows grouped by expert in ascending token order; every expert output times its fp16 routing weight, added
 into an fp16 zero accumulator in expert order; the residual last.  Written from the block's definition, once with the routing tables
 the kernels use (``tables`` / ``combine`` / ``block``) and once without any table (``block_direct``)."""
 import torch
@@ -17,18 +17,106 @@ def distinct_logits(T, E, seed):
     return out
 
 
-def route(logits, top_k):
-    """(ids int64 [T, top_k], w fp16 [T, top_k]): softmax in float, the top_k largest first, renormalised, rounded to half"""
-    p = torch.softmax(logits.float(), dim=-1)
-    w, ids = torch.topk(p, top_k, dim=-1)
+def planted_logits(T, E, K, seed):
+    """(fp16 [T, E], exact-weight row indices): rows on which equal logits decide the routing.  Seven kinds of row, eight of each with
+    their own positions (rows 0 .. 55, kind = row % 7 in the order below), then T // 8 exact-weight rows; the rest, at least 64, are
+    coarse-grid rows: multiples of 1/8 in [-1/4, 1/4].
+      zeros      all +0
+      signed     +0 / -0 alternating: they compare equal, so the whole row is one tie
+      top, low   all 65504, all -65504
+      straddle   K - 1 distinct larger values, then min(3, E - K + 1) equal ones (pairwise non-adjacent where E >= 5), the rest
+                 smaller: the top_k boundary cuts through the tie.  (E == K has no boundary: an "inside" row stands in.)
+      inside     K >= 2: a tie inside the top K and none at its boundary -- K - 2 distinct larger values, two equal ones, the rest
+                 smaller; the order inside topk_ids tells the lower index first from the opposite.  (K == 1: a tie for the maximum.)
+      maximum    1/4 twice (non-adjacent where E >= 3) over coarse-grid values up to 1/8: lmax is reached twice
+      exact      values from {0, -128, -256} with 1 .. K zeros: two selected logits are equal or at least 128 apart, so every exp is
+                 exactly 1 or exactly 0 in float (e^-128 is below the smallest float denormal, flushed or not) and each weight is
+                 half(1 / m) on the m tied maxima and 0 on the other selected experts"""
+    assert 2 <= E <= 64 and 1 <= K <= E
+    g = torch.Generator().manual_seed(seed)
+    ri = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g)
+    coarse = lambda *shape: ri(-2, 2, *shape).float() / 8
+
+    def spread(n):
+        """n ascending positions of 0 .. E - 1 in random places, pairwise non-adjacent where E >= 2 n - 1 has the room"""
+        if E >= 2 * n - 1:                                    # n - 1 gaps of at least one other position each
+            free = E - n - (n - 1)
+            cuts = sorted(ri(0, free, n).tolist())            # extra room before each of the n positions
+            pos = [cuts[i] + 2 * i for i in range(n)]
+            assert all(b - a >= 2 for a, b in zip(pos, pos[1:])) and pos[-1] < E
+            return pos
+        return torch.randperm(E, generator=g)[:n].sort().values.tolist()
+
+    def place(tied, n_larger, tie_value=1.0):
+        """a row with ``tied`` equal values, ``n_larger`` distinct larger ones and the rest distinct and smaller"""
+        row = torch.empty(E)
+        tie_pos = spread(tied)
+        others = [i for i in torch.randperm(E, generator=g).tolist() if i not in tie_pos]
+        row[tie_pos] = tie_value
+        for j, i in enumerate(others[:n_larger]):
+            row[i] = tie_value + 1 + j
+        for j, i in enumerate(others[n_larger:]):
+            row[i] = tie_value - 1 - j / 8
+        return row
+
+    reps, n_exact = 8, T // 8
+    out = coarse(T, E)
+    exact_rows = []
+    r = 0
+    for _ in range(reps):
+        out[r] = 0.0
+        out[r + 1] = torch.where(torch.arange(E) % 2 == 0, 0.0, -0.0)
+        out[r + 2], out[r + 3] = 65504.0, -65504.0
+        tied = min(3, E - K + 1)
+        out[r + 4] = place(tied, K - 1) if tied >= 2 else place(2, K - 2)
+        out[r + 5] = place(2, K - 2) if K >= 2 else place(min(3, E), 0)
+        out[r + 6] = coarse(E).clamp(max=0.125)
+        out[r + 6][spread(2)] = 0.25
+        r += 7
+    for _ in range(n_exact):
+        m = int(ri(1, K, 1))
+        row = -128.0 * ri(1, 2, E).float()
+        row[torch.randperm(E, generator=g)[:m]] = 0.0
+        out[r] = row
+        exact_rows.append(r)
+        r += 1
+    assert r <= T - 64                                       # at least 64 coarse-grid rows
+    h = out.half()
+    assert torch.equal(h.float(), out)                       # every planted value is an fp16 value
+    assert torch.equal(h[1].view(torch.int16)[:2], torch.tensor([0, -32768], dtype=torch.int16))          # the -0 survived
+    ex = h[exact_rows].float()
+    assert bool(((ex == 0) | (ex == -128) | (ex == -256)).all()) and bool((((ex == 0).sum(-1) >= 1) & ((ex == 0).sum(-1) <= K)).all())
+    assert bool((h[r:].float().abs() <= 0.25).all()) and torch.equal(h[r:].float() * 8, (h[r:].float() * 8).round())
+    if E > K:                                                # the straddling rows: value K and value K + 1 of the ordered row are equal
+        v = h[4:7 * reps:7].float().sort(-1, descending=True).values
+        assert bool((v[:, K - 1] == v[:, K]).all()) and (K == 1 or bool((v[:, :K - 1].diff(dim=-1) < 0).all()))
+    return h, exact_rows
+
+
+def _top_ids(l, top_k, tie):
+    """the first top_k of a stable descending sort of float logits: of equal values the lower index comes first (``tie="high"``: the
+    mutant in which the higher index does, the same sort on the reversed row)"""
+    if tie == "low":
+        return torch.sort(l, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    assert tie == "high"
+    return l.shape[-1] - 1 - torch.sort(l.flip(-1), dim=-1, descending=True, stable=True).indices[:, :top_k]
+
+
+def route(logits, top_k, tie="low"):
+    """(ids int64 [T, top_k], w fp16 [T, top_k]): the top_k largest logits first, of equal logits the LOWER expert index first
+    (include/atom_hip.h; torch.topk promises no order among equal values and does not keep this one); softmax in float, gathered at
+    those experts, renormalised, rounded to half"""
+    ids = _top_ids(logits.float(), top_k, tie)
+    w = torch.gather(torch.softmax(logits.float(), dim=-1), 1, ids)
     w = w / w.sum(dim=-1, keepdim=True)
     return ids, w.half()
 
 
-def route_formula(logits, top_k):
+def route_formula(logits, top_k, tie="low"):
     """the same weights by w_k = exp(l_k - l_max) / sum_{j selected} exp(l_j - l_max) in float: the full softmax's denominator cancels"""
     l = logits.float()
-    top, ids = torch.topk(l, top_k, dim=-1)
+    ids = _top_ids(l, top_k, tie)
+    top = torch.gather(l, 1, ids)
     ex = torch.exp(top - top[:, :1])
     return ids, (ex / ex.sum(dim=-1, keepdim=True)).half()
 
@@ -51,11 +139,12 @@ def tables(ids, E):
     slot_row [T][top_k], tile_expert, tile_row0"""
     T, K = ids.shape
     row_token, slot_row, counts = [], [[-1] * K for _ in range(T)], []
+    ids = ids.tolist()
     for e in range(E):
         n = 0
         for t in range(T):
             for k in range(K):
-                if int(ids[t, k]) == e:
+                if ids[t][k] == e:
                     slot_row[t][k] = len(row_token)
                     row_token.append(t)
                     n += 1

@@ -43,7 +43,7 @@ def _case(rank):
 
 
 @pytest.mark.parametrize("id_dtype", [torch.int64, torch.int32])
-@pytest.mark.parametrize("rank", [8, 24, 64])
+@pytest.mark.parametrize("rank", [8, 16, 24, 32, 64])
 @pytest.mark.parametrize("rows", [1, 3, 17, 70])
 def test_add_lora_one_row_segments(rows, rank, id_dtype):
     from atom_amd import ops
@@ -58,7 +58,7 @@ def test_add_lora_one_row_segments(rows, rank, id_dtype):
     assert torch.equal(bits(got[none].cpu()), bits(y[none]))
 
 
-@pytest.mark.parametrize("rank", [8, 24, 64])
+@pytest.mark.parametrize("rank", [8, 16, 24, 32, 64])
 def test_add_lora_segments(rank):
     from atom_amd import ops
     y, x, wa, wb, xd, wad, wbd = _case(rank)
@@ -72,6 +72,38 @@ def test_add_lora_segments(rank):
     assert torch.equal(bits(got[1:16]), bits(y[1:16]))                                           # the -1 segment, as bits
     assert bool((bits(got[rows:]) == SENTINEL).all())                                            # the guard rows behind seg_indptr[S]
     assert not torch.equal(got[16:32], y[16:32]) and not torch.equal(got[49:82], y[49:82])
+
+
+@pytest.mark.parametrize("rank", [8, 64])
+def test_segment_table_longer_than_one_search_pass(rank):
+    """lora_ref.long_table: 200 segments, so the kernels' search of 64 segments at a time runs four passes and carries its tile
+    count over a block of 64 empty segments into the third; the first segment starts at row 5.  add_lora 320 -> rank -> 192 and
+    each pass alone, bit for bit on exact inputs (tests/test_lora_cpu.py: a lost count changes every non-empty segment behind 128)"""
+    from atom_amd import ops
+    ptr, ids = lora_ref.long_table()
+    y, x, wa, wb, y_s, x_e = lora_ref.long_case(rank)
+    rows, layer = ptr[-1], lora_ref.LONG_LAYER
+    assert y.size(0) == rows + lora_ref.LONG_GUARD >= lora_ref.LONG_S
+    idt = torch.tensor(ids, dtype=torch.int32, device="cuda")
+    ptrt = torch.tensor(ptr, dtype=torch.int32, device="cuda")
+    xd, wad, wbd = x.cuda(), wa.cuda(), wb.cuda()
+    runs = [(y, lora_ref.add_lora(y, x, wa, wb, ids, layer, 0.25, seg_indptr=ptr, exact=True),
+             lambda o: ops.add_lora(o, xd, wad, wbd, idt, layer, 0.25, seg_indptr=ptrt)),
+            (y_s, lora_ref.bgmv(y_s, x, wa, ids, layer, 0.25, seg_indptr=ptr, exact=True),
+             lambda o: ops.bgmv(o, xd, wad, idt, layer, 0.25, seg_indptr=ptrt)),
+            (y, lora_ref.bgmv(y, x_e, wb, ids, layer, 0.25, seg_indptr=ptr, exact=True),
+             lambda o: ops.bgmv(o, x_e.cuda(), wbd, idt, layer, 0.25, seg_indptr=ptrt))]
+    for y0, want, run in runs:
+        got = y0.cuda()
+        run(got)
+        got = got.cpu()
+        assert torch.equal(bits(got[:rows]), bits(want[:rows]))
+        assert torch.equal(bits(got[:ptr[0]]), bits(y0[:ptr[0]]))                                # the rows in front of the first segment
+        assert bool((bits(got[rows:]) == lora_ref.LONG_SENTINEL).all())                          # the guard rows behind seg_indptr[S]
+        for s, a in enumerate(ids):
+            if not 0 <= a < lora_ref.LONG_CAP:
+                assert torch.equal(bits(got[ptr[s]:ptr[s + 1]]), bits(y0[ptr[s]:ptr[s + 1]])), s  # segments without an adapter
+        assert not torch.equal(got[ptr[128]:rows], y0[ptr[128]:rows])
 
 
 def test_add_lora_ids_outside_the_pool_touch_nothing():
@@ -99,7 +131,7 @@ def test_add_lora_long_sums_rank_64(segmented):
 
 
 @pytest.mark.parametrize("segmented", [False, True])
-@pytest.mark.parametrize("rank", [8, 24, 40, 64])
+@pytest.mark.parametrize("rank", [8, 16, 24, 32, 40, 48, 56, 64])
 def test_bgmv_alone_in_both_shape_regimes(rank, segmented):
     """shrink (H2 = rank) and expand (H1 = rank), each on rows and on the segment table"""
     from atom_amd import ops

@@ -25,15 +25,21 @@ def _bits(t):
 
 
 # ------------------------------------------------------------------------------------------------ 1. router
-def _check_router(logits, T, E, K):
+def _check_router(logits, T, E, K, distinct=True, exact_rows=None):
+    """ids, tables and n_tiles bit for bit against moe_ref (the lower index of equal logits); the weights bit for bit on
+    ``exact_rows`` and within one fp16 ulp elsewhere"""
     from atom_amd import ops
     r = ops.moe_route_topk(logits.to(DEV), K)
     ids_ref, w_ref = moe_ref.route(logits, K)
-    assert torch.equal(torch.topk(logits.float(), K, dim=-1).indices, ids_ref)
+    if distinct:                                             # (among equal logits torch.topk keeps no rule: not a cross-check there)
+        assert torch.equal(torch.topk(logits.float(), K, dim=-1).indices, ids_ref)
     assert torch.equal(r.topk_ids.cpu().long(), ids_ref)
-    ulp = (_bits(r.topk_w).int() - _bits(w_ref).int()).abs().max().item()            # positive halves: the bit patterns are ordered
-    print(f"T {T} E {E} top_k {K}: topk_w within {ulp} fp16 ulp of the reference")
+    d = (_bits(r.topk_w).int() - _bits(w_ref).int()).abs()                               # positive halves: the bit patterns are ordered
+    ulp = d.max().item()
+    print(f"T {T} E {E} top_k {K}: topk_w within {ulp} fp16 ulp of the reference, {int((d != 0).sum())} of {d.numel()} elements differ")
     assert ulp <= 1
+    if exact_rows is not None:
+        assert len(exact_rows) > 0 and torch.equal(_bits(r.topk_w)[exact_rows], _bits(w_ref)[exact_rows])
     tb = moe_ref.tables(ids_ref, E)
     n = tb["n_tiles"]
     assert r.n_tiles.item() == n and n <= ops.moe_max_tiles(T * K, E) == r.tile_expert.numel()
@@ -43,15 +49,33 @@ def _check_router(logits, T, E, K):
     assert r.tile_expert[:n].tolist() == tb["tile_expert"] and r.tile_row0[:n].tolist() == tb["tile_row0"]
 
 
-@pytest.mark.parametrize("T,E,K", [(1, 8, 2), (5, 8, 2), (257, 8, 2), (300, 16, 4), (300, 64, 8), (300, 3, 1)])
+@pytest.mark.parametrize("T,E,K", [(1, 8, 2), (5, 8, 2), (257, 8, 2), (300, 16, 4), (300, 64, 8), (300, 3, 1),
+                                   (256, 8, 2), (512, 8, 2), (1025, 8, 2)])              # pass B: one and two full chunks, five chunks
 def test_router_tables(T, E, K):
     _check_router(moe_ref.distinct_logits(T, E, 100 + T + E), T, E, K)
+
+
+@pytest.mark.parametrize("T,E,K", [(600, 8, 2), (600, 2, 2), (600, 3, 1), (600, 16, 4), (600, 64, 8), (600, 5, 5)])
+def test_router_on_equal_logits_takes_the_lower_index(T, E, K):
+    """planted ties (tests/test_moe_cpu.py: the opposite rule gives other topk_ids on 186 or more of the 600 rows of every case): all
+    zeros, +0 / -0, saturated rows, ties across and inside the top_k boundary and for the maximum; E = 2 and top_k = E included"""
+    logits, exact_rows = moe_ref.planted_logits(T, E, K, 500 + E + K)
+    _check_router(logits, T, E, K, distinct=False, exact_rows=exact_rows)
 
 
 def test_router_with_empty_experts():
     """every token picks experts 5 and 2: the other six have no row and no tile"""
     T, E, K = 70, 8, 2
     logits = moe_ref.distinct_logits(T, E, 7)
+    logits[:, 5], logits[:, 2] = 20.0, 19.0
+    _check_router(logits, T, E, K)
+
+
+def test_router_with_two_experts_fed_by_every_chunk():
+    """1000 tokens, all on experts 5 and 2: each gets 1000 rows (16 tiles) that arrive in all four chunks of pass B, so every row
+    behind the first chunk depends on the carried base[]"""
+    T, E, K = 1000, 8, 2
+    logits = moe_ref.distinct_logits(T, E, 8)
     logits[:, 5], logits[:, 2] = 20.0, 19.0
     _check_router(logits, T, E, K)
 
@@ -119,6 +143,31 @@ def test_routed_gemm_with_the_grid_far_above_the_tile_count():
     _routed_gemm_case([0, 2, 0, 0, 1, 0], 128, 2, 384, True, "ref", seed=5)
 
 
+@pytest.mark.parametrize("layout", ["ref", "plain"])
+@pytest.mark.parametrize("K", [256, 768, 896, 1024, 1152])
+def test_routed_gemm_ring_at_every_fill(K, layout):
+    """G = 1, 5, 6, 7, 8 int4 groups (+ 2 keeper stages) against the ring of 8: the prologue repeats its last stage, fills the ring
+    exactly, overfills it by one, and the keeper's two stages wrap around its end"""
+    _routed_gemm_case(COUNTS, 128, 2, K, True, layout, seed=3 * K)
+
+
+@pytest.mark.parametrize("layout", ["ref", "plain"])
+@pytest.mark.parametrize("nseg", [1, 2])
+def test_routed_gemm_64_feature_segments_one_tile(nseg, layout):
+    """n_seg = 64: the weight-scale piece clamps every lane above 31 (nseg 1) or the second feature block's (nseg 2); one expert,
+    one tile of 3 rows, so fewer live workgroups than XCDs"""
+    _routed_gemm_case([3], 64, nseg, 384, True, layout, seed=17 + nseg)
+
+
+def test_routed_gemm_64_feature_segments_with_empty_experts():
+    _routed_gemm_case([0, 200, 0, 1], 64, 2, 384, True, "ref", seed=23)
+
+
+def test_routed_gemm_64_experts_of_one_row():
+    """R = 64 over 64 experts: 64 tiles, 63 of 64 rows masked in each"""
+    _routed_gemm_case([1] * 64, 128, 2, 384, True, "ref", seed=29)
+
+
 # ------------------------------------------------------------------------------------------------ 3. combine
 @pytest.mark.parametrize("res", [False, True])
 @pytest.mark.parametrize("K", [1, 2, 4])
@@ -140,6 +189,29 @@ def test_combine_is_the_reference_fp16_arithmetic(T, K, res):
     if K == 4:                                                 # the order matters on these inputs: descending expert id gives other bits
         other = moe_ref.combine(y, E - 1 - ids, w, slot_row.tolist(), residual)
         assert not torch.equal(_bits(other), _bits(want))
+
+
+@pytest.mark.parametrize("res", [False, True])
+@pytest.mark.parametrize("K", [2, 8])
+@pytest.mark.parametrize("H", [2056, 4096])
+def test_combine_with_more_than_one_block_per_token(H, K, res):
+    """H / 8 = 257 and 512 sixteen-byte pieces: two blocks of 256 threads per token, the second with one live thread at H = 2056;
+    top_k = 8 (of 64 experts) fills every slot of the kernel's selection"""
+    from atom_amd import ops
+    T, E, R = 3, (64 if K == 8 else 8), 3 * K
+    g = torch.Generator().manual_seed(H + K)
+    ids = torch.rand((T, E), generator=g).argsort(-1)[:, :K]
+    w = (torch.rand((T, K), generator=g) * 2.0 ** torch.randint(-6, 1, (T, K), generator=g).float()).half()
+    y = (torch.randn((R, H), generator=g) * 2.0 ** torch.randint(-4, 7, (R, 1), generator=g).float()).half()
+    residual = torch.randn((T, H), generator=g).half() if res else None
+    slot_row = torch.randperm(R, generator=g).view(T, K)
+    route = ops.MoeRoute(T, E, K, topk_ids=_i32(ids), topk_w=w.to(DEV), slot_row=_i32(slot_row))
+    got = ops.moe_combine(y.to(DEV), route, None if residual is None else residual.to(DEV))
+    want = moe_ref.combine(y, ids, w, slot_row.tolist(), residual)
+    assert torch.equal(_bits(got), _bits(want))
+    if K == 8:                                               # descending expert id gives other bits, also in the second block's columns
+        other = moe_ref.combine(y, E - 1 - ids, w, slot_row.tolist(), residual)
+        assert not torch.equal(_bits(other[:, 2048:]), _bits(want[:, 2048:]))
 
 
 # ------------------------------------------------------------------------------------------------ 4. the block
@@ -207,6 +279,81 @@ def test_block_equals_the_chain_of_references(moe_block, T):
     # 5. combine
     want = moe_ref.combine(torch.from_numpy(y), ids, w, tb["slot_row"], residual.cpu())
     assert torch.equal(_bits(got), _bits(want))
+
+
+def _chain_of_references(moe, x_q, ids, w, residual):
+    """what the block computes from a given routing, reference by reference: the C oracle's GEMM per expert on the gathered codes,
+    the project's quantiser on gate / up, the oracle again for down, moe_ref.combine"""
+    from atom_amd import ops
+    T, K = ids.shape
+    E, F, H, R = moe.num_experts, moe.intermediate_size, moe.hidden_size, T * K
+    tb = moe_ref.tables(ids, E)
+    indptr, rt = tb["expert_indptr"], np.asarray(tb["row_token"])
+    o8, o4, s8, s4 = x_q
+    a4, a8 = t2n(o4).view(np.uint8), t2n(o8)
+    sa, sa8 = scales_plain(s4, T, "ref"), scales_plain(s8, T, "ref")
+    gu = np.empty((R, 2 * F), np.float16)
+    for e in range(E):
+        src = rt[indptr[e]:indptr[e + 1]]
+        if len(src):
+            gu[indptr[e]:indptr[e + 1]] = c_oracle.gemm(a4[src], t2n(moe.w13_int4[e]), sa[:, src], t2n(moe.w13_scale_int4[e]), a8[src],
+                                                        t2n(moe.w13_int8[e]), sa8[src], t2n(moe.w13_scale_int8[e]))
+    gate, up = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in (gu[:, :F], gu[:, F:])]
+    b8, b4, t8, t4 = ops.activate_fp16_i4(gate, up)
+    h4, h8, hs, hs8 = t2n(b4).view(np.uint8), t2n(b8), scales_plain(t4, R, "ref"), scales_plain(t8, R, "ref")
+    y = np.empty((R, H), np.float16)
+    for e in range(E):
+        lo, hi = indptr[e], indptr[e + 1]
+        if hi > lo:
+            y[lo:hi] = c_oracle.gemm(h4[lo:hi], t2n(moe.w2_int4[e]), hs[:, lo:hi], t2n(moe.w2_scale_int4[e]), h8[lo:hi], t2n(moe.w2_int8[e]),
+                                     hs8[lo:hi], t2n(moe.w2_scale_int8[e]))
+    return moe_ref.combine(torch.from_numpy(y), ids, w, tb["slot_row"], residual.cpu()), tb
+
+
+def test_block_equals_the_chain_of_references_on_tied_logits():
+    """80 tokens whose router logits are exact small integers (gate_in integers in [-2, 2], gate.weight in {-1, 0, 1} with two
+    non-zeros per expert: |logit| <= 4 whatever the order of the sum), so that many tokens have equal logits at the top_k boundary;
+    expert 6 gets + 9 on a column where gate_in is 1: logit 5 .. 13, chosen by every token -- 80 rows, a full tile and a second one.
+    The routing comes from moe_ref.route (the lower index of equal logits); the weights from the router kernel on the same logits,
+    after the ids are shown equal and the weights within the router's own 1 ulp, so that this test is about the block alone."""
+    from atom_amd import ops
+    from atom_amd.e2e import MixtralSparseMoeInt4
+    T, ALL = 80, 6
+    moe = MixtralSparseMoeInt4(_cfg()).cuda()
+    g = torch.Generator().manual_seed(61)
+    _load_moe(moe, g)
+    gw = torch.zeros((E_, H_))
+    for e in range(E_):
+        cols = 1 + torch.randperm(H_ - 1, generator=g)[:2]
+        gw[e, cols] = (torch.randint(0, 2, (2,), generator=g) * 2 - 1).float()
+    gw[ALL, 0] += 9
+    moe.gate.weight.data = gw.half().cuda()
+    x = torch.randn((T, H_), generator=g)
+    x[:, -128:] *= 10
+    gate_in = torch.randint(-2, 3, (T, H_), generator=g).float()
+    gate_in[:, 0] = 1
+    x, gate_in, residual = x.half().cuda(), gate_in.half().cuda(), torch.randn((T, H_), generator=g).half().cuda()
+    x_q = ops.reorder_fp16_i4(x, None)
+    got = moe(x_q, gate_in, residual)
+    logits = torch.nn.functional.linear(gate_in, moe.gate.weight).cpu()
+    assert torch.equal(logits.double(), gate_in.cpu().double() @ gw.double().t())      # exact integers
+    ids, w_ref = moe_ref.route(logits, K_)
+    srt = logits.float().sort(-1, descending=True).values
+    ties = int((srt[:, K_ - 1] == srt[:, K_]).sum())
+    print(f"{ties} of {T} tokens have equal logits at the top_k boundary")
+    assert ties >= 10 and bool((ids == ALL).any(-1).all())
+    r = ops.moe_route_topk(logits.cuda(), K_)
+    assert torch.equal(r.topk_ids.cpu().long(), ids)
+    assert (_bits(r.topk_w).int() - _bits(w_ref).int()).abs().max().item() <= 1
+    w = r.topk_w.cpu()
+    want, tb = _chain_of_references(moe, x_q, ids, w, residual)
+    assert tb["expert_indptr"][ALL + 1] - tb["expert_indptr"][ALL] == T and tb["n_tiles"] >= 3
+    assert torch.equal(_bits(got), _bits(want))
+    # the tie rule reaches the output: the chain from the opposite rule's routing gives other bits
+    ids_hi, w_hi = moe_ref.route(logits, K_, tie="high")
+    assert torch.equal(w_hi, w_ref) and not torch.equal(ids_hi, ids)                   # the same weights in the same slots: only ids differ
+    other, _ = _chain_of_references(moe, x_q, ids_hi, w, residual)
+    assert not torch.equal(_bits(other), _bits(want))
 
 
 # ------------------------------------------------------------------------------------------------ 5. generation

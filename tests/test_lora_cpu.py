@@ -108,6 +108,53 @@ def test_exact_inputs_are_exact_at_the_gpu_tests_shapes():
     lora_ref.add_lora(y, x, wa, wb, [i % 3 for i in range(82)], 1, 0.25, exact=True)
     y, x, wa, wb = lora_ref.exact_inputs(33, 4096, 1024, 64, 2, 1, seed=4)
     lora_ref.add_lora(y, x, wa, wb, [i % 2 for i in range(33)], 0, 0.125, exact=True)
+    for rank in (16, 32):                                                  # tests/test_gpu_lora.py::_case at its added ranks
+        y, x, wa, wb = lora_ref.exact_inputs(82, 320, 192, rank, 3, 2, seed=10 + rank, guard=8)
+        lora_ref.add_lora(y, x, wa, wb, [i % 3 for i in range(90)], 1, 0.25, exact=True)
+    for rank in (16, 32, 48, 56):                                          # ... and the operands of its bgmv test, both regimes
+        y, x, _, _ = lora_ref.exact_inputs(82, 320, 192, 8, 3, 2, seed=18, guard=8)
+        g = torch.Generator().manual_seed(rank)
+        w_s, y_s = torch.randint(-1, 2, (3, 2, rank, 320), generator=g).half(), torch.randint(-8, 9, (82, rank), generator=g).half()
+        lora_ref.bgmv(y_s, x[:82], w_s, [i % 3 for i in range(82)], 1, 0.25, exact=True)
+        w_e, x_e = torch.randint(-1, 2, (3, 2, 192, rank), generator=g).half(), torch.randint(-2, 3, (82, rank), generator=g).half()
+        lora_ref.bgmv(y[:82], x_e, w_e, [i % 3 for i in range(82)], 1, 0.25, exact=True)
+    ptr, ids = lora_ref.long_table()                                       # the long table: every segment on a real adapter
+    for rank in (8, 64):
+        y, x, wa, wb, y_s, x_e = lora_ref.long_case(rank)
+        every = [s % lora_ref.LONG_CAP for s in range(lora_ref.LONG_S)]
+        lora_ref.add_lora(y, x, wa, wb, every, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True)
+        lora_ref.bgmv(y_s, x, wa, every, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True)
+        lora_ref.bgmv(y, x_e, wb, every, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True)
+
+
+def test_long_table_meets_the_abi_and_tells_a_lost_tile_count():
+    """the table of the GPU test: within the ABI (ascending, inside the rows, rows >= S), more than 64 segments with a whole block
+    of 64 empty ones; and shifting the adapters of segments 128 .. 199 by one -- what a search that forgot the tiles of the first
+    two blocks would honour -- changes at least one row of EVERY non-empty segment there, for add_lora and for both single passes"""
+    ptr, ids = lora_ref.long_table()
+    S, rows = lora_ref.LONG_S, ptr[-1]
+    assert len(ptr) == S + 1 and len(ids) == S and S > 128 and ptr[0] == lora_ref.LONG_FIRST > 0
+    assert all(a <= b for a, b in zip(ptr, ptr[1:])) and rows + lora_ref.LONG_GUARD >= S
+    assert ptr[64] == ptr[128] and ptr[64] > ptr[0] and ptr[S] > ptr[128]
+    assert -1 in ids and any(a >= lora_ref.LONG_CAP for a in ids) and {0, 1, 2} <= set(ids)
+    shifted = lora_ref.long_ids_shifted(ids)
+    assert shifted[:128] == ids[:128]
+    none = lambda a: not 0 <= a < lora_ref.LONG_CAP
+    assert all(a != b and not (none(a) and none(b)) for a, b in zip(ids[128:], shifted[128:]))
+    live = [s for s in range(128, S) if ptr[s + 1] > ptr[s]]
+    for rank in (8, 64):
+        y, x, wa, wb, y_s, x_e = lora_ref.long_case(rank)
+        assert y.size(0) == rows + lora_ref.LONG_GUARD
+        for what, fn in (("add_lora", lambda i: lora_ref.add_lora(y, x, wa, wb, i, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True)),
+                         ("shrink", lambda i: lora_ref.bgmv(y_s, x, wa, i, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True)),
+                         ("expand", lambda i: lora_ref.bgmv(y, x_e, wb, i, lora_ref.LONG_LAYER, 0.25, seg_indptr=ptr, exact=True))):
+            want, other = fn(ids), fn(shifted)
+            told = [s for s in live if not torch.equal(lora_ref.bits(want[ptr[s]:ptr[s + 1]]), lora_ref.bits(other[ptr[s]:ptr[s + 1]]))]
+            print(f"rank {rank} {what}: the shifted adapters change {len(told)} of the {len(live)} non-empty segments 128 .. 199")
+            assert told == live
+            assert torch.equal(lora_ref.bits(want[:ptr[128]]), lora_ref.bits(other[:ptr[128]]))
+            assert torch.equal(lora_ref.bits(want[:ptr[0]]), lora_ref.bits((y_s if what == "shrink" else y)[:ptr[0]]))
+            assert bool((lora_ref.bits(want[rows:]) == lora_ref.LONG_SENTINEL).all())
 
 
 def test_pool_folds_alpha_into_b_and_permutes_the_intermediate_channels():
