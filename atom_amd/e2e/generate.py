@@ -1,29 +1,74 @@
-"""Greedy token generation by graph replay: ``DecodeGraph`` captures ONE decode step of a ``LlamaForCausalLM`` over a
-``StaticBatchedKvCacheInt4`` -- page tables stepped on the device (ops.kv_step_i4), the model's forward, argmax, the token written
-back as the next input -- and replays it for every following token; ``generate`` is the loop around it: eager prefill, then replays.
-Nothing between two steps touches the host: no page-table upload, no ``.item()``.
+"""Token generation by graph replay: ``DecodeGraph`` captures ONE decode step of a ``LlamaForCausalLM`` over a
+``StaticBatchedKvCacheInt4`` -- page tables stepped on the device (ops.kv_step_i4), the model's forward, argmax (or, with a
+``Sampler``, ops.sample: temperature / top-k / top-p, one launch), the token written back as the next input -- and replays it for
+every following token; ``generate`` is the loop around it: eager prefill, then replays.
+Nothing between two steps touches the host: no page-table upload, no ``.item()``, no logits on the host.
 """
 from __future__ import annotations
 
-from typing import Sequence
+import dataclasses
+from typing import Sequence, Union
 
 import torch
 
+from .. import ops
 from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, StaticBatchedKvCacheInt4
 
 
+@dataclasses.dataclass(frozen=True)
+class SamplingParams:
+    """How one sequence draws its tokens (ops.sample): ``temperature`` <= 0 is greedy, ``top_k`` outside 1 .. vocab - 1 and
+    ``top_p`` >= 1 are off, ``seed`` is any 64-bit integer.  Token i of a sequence is draw number i of its seed: the stream is a
+    function of the seed and the logits alone, whatever the batch around it."""
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+
+
+class Sampler:
+    """The per-sequence sampling parameters as four ``[batch]`` device buffers at FIXED addresses (``temperature`` float32, ``top_k``
+    int32, ``top_p`` float32, ``seeds`` int64), so a captured ``ops.sample`` follows ``set``."""
+
+    def __init__(self, batch: int, device, params: Union[SamplingParams, Sequence[SamplingParams]] = SamplingParams()):
+        self.batch = int(batch)
+        self.temperature = torch.empty(self.batch, dtype=torch.float32, device=device)
+        self.top_k = torch.empty(self.batch, dtype=torch.int32, device=device)
+        self.top_p = torch.empty(self.batch, dtype=torch.float32, device=device)
+        self.seeds = torch.empty(self.batch, dtype=torch.int64, device=device)
+        self.set(params)
+
+    def set(self, params: Union[SamplingParams, Sequence[SamplingParams]]):
+        """One ``SamplingParams`` for all sequences or one per sequence, copied into the buffers in place."""
+        ps = [params] * self.batch if isinstance(params, SamplingParams) else list(params)
+        if len(ps) != self.batch or not all(isinstance(q, SamplingParams) for q in ps):
+            raise ValueError(f"sampling: one SamplingParams, or one per sequence ({self.batch})")
+        seeds = [int(q.seed) & (2 ** 64 - 1) for q in ps]
+        self.temperature.copy_(torch.tensor([float(q.temperature) for q in ps], dtype=torch.float32))
+        self.top_k.copy_(torch.tensor([max(min(int(q.top_k), 2 ** 31 - 1), -1) for q in ps], dtype=torch.int32))
+        self.top_p.copy_(torch.tensor([float(q.top_p) for q in ps], dtype=torch.float32))
+        self.seeds.copy_(torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64))   # the same 64 bits
+
+    def sample(self, logits: torch.Tensor, step: torch.Tensor = None, step_offset: int = 0) -> torch.Tensor:
+        """Draw number ``step[0] + step_offset`` of every sequence from ``logits`` fp16 [batch, vocab]; int64 [batch]."""
+        return ops.sample(logits, self.temperature, self.top_k, self.top_p, self.seeds, step=step, step_offset=step_offset)
+
+
 class DecodeGraph:
-    """One greedy decode step over ``static_kv``, run up to ``max_steps`` times.
+    """One decode step over ``static_kv``, run up to ``max_steps`` times: greedy, or sampled with ``sampler`` (a ``Sampler``, or
+    ``SamplingParams`` -- one, or one per sequence -- to build ``self.sampler`` from).  Step i (from 0) takes draw number i + 1 of
+    every sequence; draw 0 belongs to the token the caller feeds in.  ``self.sampler.set(...)`` between steps changes the parameters
+    of the steps that follow, replayed ones included.
 
     Static buffers: ``input_ids`` int64 [batch] (the tokens the next step consumes), ``tokens`` int64 [max_steps, batch] (row i: the
     tokens step i produced) and, with ``keep_logits=True``, ``logits`` fp16 [max_steps, batch, vocab]; a device counter indexes the rows.
     A step is ``static_kv.step()`` (every sequence gains a slot, its page tables are rebuilt on the device), the model's forward for
-    one token per sequence, ``argmax``.  The first ``step()`` runs eagerly: it builds what a capture cannot -- the fused weight
-    operands, the weight-scale pair tags, the workspace.  The second is captured on torch's capture stream (one stream: a single
+    one token per sequence, ``argmax`` (``sampler=None``) or ``ops.sample`` reading the device counter as its step.  The first
+    ``step()`` runs eagerly: it builds what a capture cannot -- the fused weight operands, the weight-scale pair tags, the workspace.  The second is captured on torch's capture stream (one stream: a single
     chain of launches) and replayed; every later one is a replay.  ``steps_done`` counts on the host; the capacity check is the
     cache's status word (``static_kv.sync_host()``), read after the loop."""
 
-    def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False):
+    def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None):
         assert max_steps >= 1
         self.model, self.kv, self.max_steps = model, static_kv, int(max_steps)
         device = static_kv.data.device
@@ -34,6 +79,8 @@ class DecodeGraph:
                        if keep_logits else None)
         self._counter = torch.zeros(1, dtype=torch.int64, device=device)
         self._blen = BatchLenInfo([], batch, device)
+        self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
+        assert self.sampler is None or self.sampler.batch == batch
         self._graph = None
         self.steps_done = 0
 
@@ -41,7 +88,10 @@ class DecodeGraph:
     def _step(self):
         self.kv.step()
         logits, _ = self.model(self.input_ids, self._blen, None, self.kv)
-        nxt = logits.argmax(dim=-1)
+        if self.sampler is None:
+            nxt = logits.argmax(dim=-1)
+        else:
+            nxt = self.sampler.sample(logits, step=self._counter, step_offset=1)
         self.tokens.index_copy_(0, self._counter, nxt.unsqueeze(0))
         if self.logits is not None:
             self.logits.index_copy_(0, self._counter, logits.unsqueeze(0))
@@ -73,9 +123,13 @@ class DecodeGraph:
 
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, *, eos_token_id: int = None,
-             caches: Sequence[KvCacheInt4] = None, return_logits: bool = False):
-    """Greedy generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
-    ``eos_token_id``.  The prompts are prefilled eagerly in one forward; the first new token is the argmax of each prompt's last row;
+             caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
+             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None):
+    """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
+    ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
+    ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
+    on the prompts beside it (as far as its logits do not).
+    The prompts are prefilled eagerly in one forward; the first new token is the argmax of each prompt's last row (or draw 0);
     the other ``max_new_tokens - 1`` come from a ``DecodeGraph`` over a ``StaticBatchedKvCacheInt4`` with that many tokens reserved
     from ``pool``.  All sequences run all steps (stopping is a host-side cut afterwards).
     ``caches``: one ``KvCacheInt4`` of ``pool`` per prompt to generate into (tokens they already hold are a cached prefix of the
@@ -92,11 +146,15 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
     last = torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1).to(device)
     all_logits = logits.index_select(0, last).unsqueeze(0)
-    new = all_logits.argmax(dim=-1)                            # [1, batch]
+    sampler = None if sampling is None else Sampler(len(prompts), device, sampling)
+    if sampler is None:
+        new = all_logits.argmax(dim=-1)                        # [1, batch]
+    else:
+        new = sampler.sample(all_logits[0]).unsqueeze(0)
     if max_new_tokens > 1:
         static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
-            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits)
+            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler)
             new = torch.cat([new, dg.run(new[0])])
             if return_logits:
                 all_logits = torch.cat([all_logits, dg.logits])

@@ -1007,3 +1007,44 @@ def kv_quant_u4(k: torch.Tensor):
     st = L.lib().atom_kv_quant_u4_f16(k.data_ptr(), packed.data_ptr(), params.data_ptr(), t, heads, d, L.current_stream(k.device))
     L.check(st, "atom_kv_quant_u4_f16")
     return packed, params
+
+
+# ------------------------------------------------------------------------------------------------ sampling
+_SAMPLE_PARAMS = (("temperature", torch.float32), ("top_k", torch.int32), ("top_p", torch.float32), ("seeds", torch.int64))
+
+
+def sample(logits: torch.Tensor, temperature: torch.Tensor = None, top_k: torch.Tensor = None, top_p: torch.Tensor = None,
+           seeds: torch.Tensor = None, step: torch.Tensor = None, step_offset: int = 0, out: torch.Tensor = None) -> torch.Tensor:
+    """NEW: one token per row of ``logits`` (fp16 [batch, vocab], rows ``stride(0) >= vocab`` apart) under temperature, top-k and
+    top-p -- ``atom_sample_f16``, the contract of DESIGN.md 4.13: the token is an exact function of the row's bits, its parameters
+    and the draw number ``step[0] + step_offset``; it does not depend on the batch or on timing.  The parameters are DEVICE tensors of
+    ``[batch]`` that the launch reads (a captured call follows buffers changed in place): ``temperature`` float32 (<= 0: greedy, the
+    first index of the maximum), ``top_k`` int32 (outside 1 .. vocab - 1: off), ``top_p`` float32 (>= 1: off), ``seeds`` int64 (the 64
+    bits are the Philox key; uint64 is taken too), ``step`` int64 [1].  None: T = 1, off, off, seed 0, step 0.  Returns int64 [batch]
+    (``out`` if given).  One launch; nothing is read back, nothing synchronises."""
+    if not logits.is_cuda:
+        raise L.AtomHipError("logits must live on the GPU: the sampler has no CPU fallback")
+    if logits.dtype != torch.float16:
+        raise TypeError(f"logits must be float16, got {logits.dtype}")
+    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
+    batch, vocab = logits.shape
+    ld = logits.stride(0) if batch > 1 else max(logits.stride(0), vocab)
+    given = dict(temperature=temperature, top_k=top_k, top_p=top_p, seeds=seeds)
+    for name, dtype in _SAMPLE_PARAMS:
+        t = given[name]
+        if t is None:
+            continue
+        ok = t.dtype == dtype or (name == "seeds" and t.dtype == torch.uint64)
+        if not (t.is_cuda and ok and t.shape == (batch,) and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous {dtype} tensor of [{batch}] on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if step is not None and not (step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
+        raise TypeError("step must be an int64 tensor of one element on the GPU")
+    if out is None:
+        out = torch.empty(batch, dtype=torch.int64, device=logits.device)
+    elif not (out.is_cuda and out.dtype == torch.int64 and out.shape == (batch,) and out.is_contiguous()):
+        raise TypeError(f"out must be a contiguous int64 tensor of [{batch}] on the GPU")
+    st = L.lib().atom_sample_f16(logits.data_ptr(), ld, batch, vocab, L.ptr(temperature), L.ptr(top_k), L.ptr(top_p), L.ptr(seeds),
+                                 L.ptr(step), int(step_offset), out.data_ptr(), L.current_stream(logits.device))
+    L.check(st, "atom_sample_f16")
+    return out

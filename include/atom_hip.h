@@ -647,6 +647,33 @@ int atom_add_lora_f16(void *y, const void *x, const void *wa, const void *wb, co
                       int64_t layer_idx, float scale, void *stream);
 int atom_kv_quant_u4_f16(const void *k, void *packed, void *param, int64_t T, int kv_heads, int head_dim, void *stream);
 
+/*
+ * Sampling: one token per row of fp16 logits under temperature, top-k and top-p -- csrc/sample.hip, arithmetic in csrc/sample_math.h,
+ * the contract in DESIGN.md 4.13.  No reference counterpart (the reference's serving loop takes the argmax on the host).
+ *   logits fp16 [batch, vocab], row stride ld >= vocab elements; tokens int64 [batch]
+ *   temperature float [batch], top_k int32 [batch], top_p float [batch], seeds uint64 [batch], step int64 [1]: DEVICE arrays, read by
+ *   the launch (a captured launch follows buffers that are changed in place); each may be NULL: T = 1, k off, p off, seed 0, *step = 0.
+ * tokens[b] is a pure function of row b's bits, its four parameters and s = *step + step_offset -- not of the batch, the grid or the
+ * order of any atomic:
+ *   1. l_i = float(logit_i), NaN -> -inf, +inf -> 65504, -0 = +0; m = max l_i; m = -inf: token 0.
+ *   2. order: l_i descending, the lower index first among equal logits.
+ *   3. T <= 0 or NaN: the first token of the order (greedy).  Otherwise T is clamped to [2^-10, 2^10].
+ *   4. w_i, 2^40 fixed point, FP32 with one rounding per operation: r = 1 / T, x = ((l_i - m) * r) * 0x1.715476p+0f; x < -40: w_i = 0;
+ *      else n = floor(x), f = x - n, q = 2^f by the degree-5 Horner polynomial of sample_math.h, w_i = (uint64)(q * 2^23) << (17 + n)
+ *      (a right shift where 17 + n < 0).  The maximum's weight is exactly 2^40.
+ *   5. 0 < k < vocab: keep the first k of the order (else all); Z_k = their weight sum.
+ *   6. p < 1 (or NaN): P = (uint64)(p * 2^32) (0 for p <= 0 or NaN), thr = (Z_k * P) >> 32; keep the shortest non-empty prefix whose
+ *      weight sum is >= thr; Z = its sum.
+ *   7. R = word 0 of Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (s & 0xffffffff, s >> 32, 0, 0); target = (Z * R) >> 32;
+ *      the token is the first of the kept prefix whose cumulative weight is greater than target.
+ * One launch, no workspace, nothing read back: capturable.  An index outside 0 .. vocab - 1 is never produced.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null logits / tokens; ATOM_ERR_SHAPE for batch < 1, vocab < 1,
+ * vocab > 262144 or ld < vocab; ATOM_ERR_ALIGN for a pointer off its element size (2 bytes for logits, 4 for temperature / top_k /
+ * top_p, 8 for seeds / step / tokens).  Rows whose base is 16-byte aligned with ld % 8 == 0 are read with 16-byte loads.
+ */
+int atom_sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
+                    const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t step_offset, int64_t *tokens, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

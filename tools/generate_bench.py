@@ -3,8 +3,10 @@
     eager   the loop a user writes without atom_amd.e2e.generate: acquire_one on every sequence, a new BatchedKvCacheInt4 (three
             host-to-device copies), one forward, argmax -- per token
     replay  atom_amd.e2e.DecodeGraph: the page tables stepped on the device (atom_kv_step_i4) and the whole step replayed from one graph
+    sampled the same with a sampler (ops.sample in place of argmax: T = 0.8, top-k 50, top-p 0.95, one seed per sequence)
+    pair    replay and sampled, their repetitions alternating in one process (the fair comparison of the two)
 
-    python tools/generate_bench.py [--mode eager|replay|both] [--batches 1,16] [--ctx 1024] [--steps 64] [--reps 5] [--layers 8]
+    python tools/generate_bench.py [--mode eager|replay|sampled|pair|both] [--batches 1,16] [--ctx 1024] [--steps 64] [--reps 5] [--layers 8]
                                    [--tree DIR]
 
 Every repetition is `steps` tokens timed by the host clock around work that ends in a device synchronise; the context grows from
@@ -23,7 +25,7 @@ import types
 import torch
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=["eager", "replay", "both"], default="both")
+ap.add_argument("--mode", choices=["eager", "replay", "sampled", "pair", "both"], default="both")
 ap.add_argument("--batches", default="1,16")
 ap.add_argument("--ctx", type=int, default=1024)
 ap.add_argument("--steps", type=int, default=64)
@@ -85,16 +87,37 @@ def eager(model, batch):
     return [timed(step, args.steps) for _ in range(args.reps)]
 
 
-def replay(model, batch):
+def replay_graph(model, batch, sampled):
     from atom_amd.e2e import DecodeGraph
     from atom_amd.utils import StaticBatchedKvCacheInt4
     total = WARM + args.reps * args.steps
     pool, seqs = sequences(batch, total)
     skv = StaticBatchedKvCacheInt4(seqs, reserve=total)
-    dg = DecodeGraph(model, skv, total)
+    kw = {}
+    if sampled:
+        from atom_amd.e2e import SamplingParams
+        kw["sampler"] = [SamplingParams(0.8, 50, 0.95, seed=b + 1) for b in range(batch)]
+    dg = DecodeGraph(model, skv, total, **kw)
     timed(dg.step, WARM)                                      # the eager first step, the capture, six replays
+    return dg, skv
+
+
+def replay(model, batch, sampled=False):
+    dg, skv = replay_graph(model, batch, sampled)
     us = [timed(dg.step, args.steps) for _ in range(args.reps)]
     skv.close()
+    return us
+
+
+def pair(model, batch):
+    """greedy and sampled replay, one repetition of each in turn"""
+    graphs = [replay_graph(model, batch, sampled) for sampled in (False, True)]
+    us = ([], [])
+    for _ in range(args.reps):
+        for (dg, _), out in zip(graphs, us):
+            out.append(timed(dg.step, args.steps))
+    for _, skv in graphs:
+        skv.close()
     return us
 
 
@@ -102,9 +125,14 @@ def main():
     model = build_model()
     modes = ["eager", "replay"] if args.mode == "both" else [args.mode]
     for batch in (int(b) for b in args.batches.split(",")):
+        results = []
         for mode in modes:
             with torch.no_grad():
-                us = (eager if mode == "eager" else replay)(model, batch)
+                if mode == "pair":
+                    results += list(zip(("replay", "sampled"), pair(model, batch)))
+                else:
+                    results.append((mode, eager(model, batch) if mode == "eager" else replay(model, batch, mode == "sampled")))
+        for mode, us in results:
             print(json.dumps({"mode": mode, "batch": batch, "ctx": args.ctx, "layers": args.layers, "steps": args.steps,
                               "us_per_token": [round(u, 1) for u in us], "median": round(sorted(us)[len(us) // 2], 1),
                               "device": torch.cuda.get_device_name(0), "tree": os.path.abspath(args.tree)}), flush=True)
