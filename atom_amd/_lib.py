@@ -98,6 +98,7 @@ SIGNATURES = {
     "atom_add_lora_f16": (_int, [_vp] * 7 + [_i64] * 8 + [_f32, _vp]),
     "atom_kv_quant_u4_f16": (_int, [_vp] * 3 + [_i64, _int, _int, _vp]),
     "atom_sample_f16": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64, _vp, _vp]),
+    "atom_logprob_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 // fixed-point weight, the top-p threshold, the Philox draw.  Every function is a pure function of its arguments, the same on the host
 // and on the device; the library is built with -ffp-contract=off, so each FP32 operation below is rounded once, as written.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -61,6 +62,10 @@ ATOM_SAMPLE_HD uint64_t weight(float l, float m, float r) {
   const int sh = 17 + (int)n;
   return sh >= 0 ? mant << sh : mant >> -sh;
 }
+
+// atom_logprob_f16: the natural log of a row's weight sum Z (2^40 <= Z < 2^59) over 2^40, as FP32.  The conversion
+// of Z rounds to nearest, the log is the double-precision libm's, 40 ln 2 is the double product 40 * 0x1.62e42fefa39efp-1.
+ATOM_SAMPLE_HD float log_z(uint64_t Z) { return (float)(::log((double)Z) - 0x1.bb9d3beb8c86bp+4); }
 
 // (a * b) >> 32 of the 96-bit product, a < 2^64, the result below 2^64 (a < 2^59 here)
 ATOM_SAMPLE_HD uint64_t mul_shr32(uint64_t a, uint32_t b) { return (a >> 32) * b + (((a & 0xFFFFFFFFull) * b) >> 32); }

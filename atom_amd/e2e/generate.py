@@ -3,6 +3,8 @@
 ``Sampler``, ops.sample: temperature / top-k / top-p, one launch), the token written back as the next input -- and replays it for
 every following token; ``generate`` is the loop around it: eager prefill, then replays.
 Nothing between two steps touches the host: no page-table upload, no ``.item()``, no logits on the host.
+With ``logprobs=`` a step also records the chosen token's log-probability, its rank and the top-n alternatives (ops.logprob, one more
+launch on the same logits); ``score`` / ``perplexity`` run given sequences through one prefill and one ops.logprob.
 """
 from __future__ import annotations
 
@@ -24,6 +26,23 @@ class SamplingParams:
     top_k: int = 0
     top_p: float = 1.0
     seed: int = 0
+
+
+@dataclasses.dataclass
+class TokenLogprobs:
+    """What ``generate(..., logprobs=n)`` records per new token, device tensors with one row per token: ``token_logprobs`` float32
+    [tokens, batch] and ``token_ranks`` int32 [tokens, batch] of the chosen token (rank 0: the greedy token) and, for n >= 1,
+    ``top_ids`` int64 / ``top_logprobs`` float32 [tokens, batch, n], the n most probable tokens in order (else None)."""
+    token_logprobs: torch.Tensor
+    token_ranks: torch.Tensor
+    top_ids: torch.Tensor = None
+    top_logprobs: torch.Tensor = None
+
+
+def _check_logprobs(logprobs):
+    if logprobs is not None and not 0 <= int(logprobs) <= ops.LOGPROB_MAX_TOP:
+        raise ValueError(f"logprobs must be None or 0 .. {ops.LOGPROB_MAX_TOP}, got {logprobs}")
+    return None if logprobs is None else int(logprobs)
 
 
 class Sampler:
@@ -66,9 +85,15 @@ class DecodeGraph:
     one token per sequence, ``argmax`` (``sampler=None``) or ``ops.sample`` reading the device counter as its step.  The first
     ``step()`` runs eagerly: it builds what a capture cannot -- the fused weight operands, the weight-scale pair tags, the workspace.  The second is captured on torch's capture stream (one stream: a single
     chain of launches) and replayed; every later one is a replay.  ``steps_done`` counts on the host; the capacity check is the
-    cache's status word (``static_kv.sync_host()``), read after the loop."""
+    cache's status word (``static_kv.sync_host()``), read after the loop.
 
-    def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None):
+    ``logprobs``: None is the step above.  0 adds one ops.logprob after the argmax / ops.sample, on the same logits with the chosen
+    tokens as targets, and records ``token_logprobs`` float32 / ``token_ranks`` int32 [max_steps, batch]; 1 .. 32 also records the
+    top-n, ``top_ids`` int64 / ``top_logprobs`` float32 [max_steps, batch, n].  The values are the model's distribution at T = 1
+    without truncation, whatever the sampler's parameters."""
+
+    def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None,
+                 logprobs: int = None):
         assert max_steps >= 1
         self.model, self.kv, self.max_steps = model, static_kv, int(max_steps)
         device = static_kv.data.device
@@ -81,6 +106,14 @@ class DecodeGraph:
         self._blen = BatchLenInfo([], batch, device)
         self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
         assert self.sampler is None or self.sampler.batch == batch
+        self.logprobs = n = _check_logprobs(logprobs)
+        self.token_logprobs = self.token_ranks = self.top_ids = self.top_logprobs = None
+        if n is not None:
+            self.token_logprobs = torch.zeros((self.max_steps, batch), dtype=torch.float32, device=device)
+            self.token_ranks = torch.zeros((self.max_steps, batch), dtype=torch.int32, device=device)
+            if n > 0:
+                self.top_ids = torch.zeros((self.max_steps, batch, n), dtype=torch.int64, device=device)
+                self.top_logprobs = torch.zeros((self.max_steps, batch, n), dtype=torch.float32, device=device)
         self._graph = None
         self.steps_done = 0
 
@@ -93,6 +126,11 @@ class DecodeGraph:
         else:
             nxt = self.sampler.sample(logits, step=self._counter, step_offset=1)
         self.tokens.index_copy_(0, self._counter, nxt.unsqueeze(0))
+        if self.logprobs is not None:
+            got = ops.logprob(logits, nxt, self.logprobs)
+            for buf, x in zip((self.token_logprobs, self.token_ranks, self.top_ids, self.top_logprobs), got):
+                if buf is not None:
+                    buf.index_copy_(0, self._counter, x.unsqueeze(0))
         if self.logits is not None:
             self.logits.index_copy_(0, self._counter, logits.unsqueeze(0))
         self.input_ids.copy_(nxt)
@@ -124,7 +162,7 @@ class DecodeGraph:
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, *, eos_token_id: int = None,
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
-             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None):
+             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -134,7 +172,13 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     from ``pool``.  All sequences run all steps (stopping is a host-side cut afterwards).
     ``caches``: one ``KvCacheInt4`` of ``pool`` per prompt to generate into (tokens they already hold are a cached prefix of the
     prompt); they are left consistent -- ``seqlen`` counts the prompt and every token that was fed back, no spare pages.  Default:
-    fresh caches, released at the end.  ``return_logits``: also return every step's logits, fp16 [max_new_tokens, batch, vocab]."""
+    fresh caches, released at the end.  ``return_logits``: also return every step's logits, fp16 [max_new_tokens, batch, vocab].
+    ``logprobs`` (None, or 0 .. 32): a ``TokenLogprobs`` is appended to what is returned -- ``(out, lp)`` or ``(out, all_logits, lp)`` --
+    with ``max_new_tokens`` rows of device tensors, row 0 from the prompts' last prefill rows: every new token's log-probability and
+    rank and, for n >= 1, the n most probable tokens of its step.  The values describe the model's distribution at T = 1 without
+    truncation, whatever ``sampling`` is (a token drawn at another temperature or inside a top-k still gets the probability the
+    untempered, untruncated model gives it).  Rows after a prompt's EOS are computed like its tokens: cutting them is the caller's job."""
+    n_lp = _check_logprobs(logprobs)
     assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
     device = pool.buf.device
     seqs = [KvCacheInt4(pool, 0) for _ in prompts] if caches is None else list(caches)
@@ -151,11 +195,15 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
         new = all_logits.argmax(dim=-1)                        # [1, batch]
     else:
         new = sampler.sample(all_logits[0]).unsqueeze(0)
+    lp = None if n_lp is None else [x if x is None else x.unsqueeze(0) for x in ops.logprob(all_logits[0], new[0], n_lp)]
     if max_new_tokens > 1:
         static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
-            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler)
+            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp)
             new = torch.cat([new, dg.run(new[0])])
+            if lp is not None:
+                rest = (dg.token_logprobs, dg.token_ranks, dg.top_ids, dg.top_logprobs)
+                lp = [a if a is None else torch.cat([a, b]) for a, b in zip(lp, rest)]
             if return_logits:
                 all_logits = torch.cat([all_logits, dg.logits])
         finally:
@@ -168,4 +216,49 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     if caches is None:
         for c in seqs:
             c.release()
-    return (out, all_logits) if return_logits else out
+    res = (out, all_logits) if return_logits else (out,)
+    if lp is not None:
+        res = res + (TokenLogprobs(*lp),)
+    return res if len(res) > 1 else out
+
+
+@torch.no_grad()
+def score(model, sequences: Sequence[Sequence[int]], pool: KvPoolInt4, *, top_n: int = 0):
+    """Teacher-forced log-probabilities of given ``sequences`` (lists of token ids) through the real kernels: one eager prefill of all
+    of them into fresh caches of ``pool`` (released afterwards), then one ops.logprob over all rows, the targets being each sequence
+    shifted by one (-1, ignored, on its last row).  Returns one dict per sequence: ``logprob`` float32 [len - 1] (of token i + 1 given
+    tokens 0 .. i), ``rank`` int32 [len - 1] and, for ``top_n`` >= 1, ``top_ids`` int64 / ``top_logprobs`` float32 [len - 1, top_n];
+    device tensors, empty for a sequence of one token.  Out of scope: sequences scored in chunks over a cached prefix -- a sequence
+    and its logits ([tokens, vocab] fp16) must fit one prefill."""
+    assert len(sequences) > 0 and all(len(s) > 0 for s in sequences)
+    device = pool.buf.device
+    lens = [len(s) for s in sequences]
+    seqs = [KvCacheInt4(pool, 0) for _ in sequences]
+    try:
+        for c, n in zip(seqs, lens):
+            c.acquire(n)
+        ids = torch.tensor([t for s in sequences for t in s], dtype=torch.int64, device=device)
+        logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
+        targets = torch.tensor([t for s in sequences for t in list(s[1:]) + [-1]], dtype=torch.int64, device=device)
+        got = ops.logprob(logits, targets, top_n)
+    finally:
+        for c in seqs:
+            c.release()
+    out, at = [], 0
+    for n in lens:
+        rows = slice(at, at + n - 1)
+        d = dict(logprob=got[0][rows], rank=got[1][rows])
+        if top_n > 0:
+            d.update(top_ids=got[2][rows], top_logprobs=got[3][rows])
+        out.append(d)
+        at += n
+    return out
+
+
+def perplexity(model, sequences: Sequence[Sequence[int]], pool: KvPoolInt4) -> float:
+    """exp(-SUM logprob / SUM (len - 1)) over ``score(model, sequences, pool)``, summed in float64 on the host; at least one sequence
+    must have two tokens."""
+    import math
+    lps = torch.cat([d["logprob"] for d in score(model, sequences, pool)]).cpu().double()
+    assert lps.numel() > 0, "perplexity needs a sequence of at least two tokens"
+    return math.exp(-float(lps.sum()) / lps.numel())

@@ -1048,3 +1048,50 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor = None, top_k: torch.
                                  L.ptr(step), int(step_offset), out.data_ptr(), L.current_stream(logits.device))
     L.check(st, "atom_sample_f16")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ log-probabilities
+LOGPROB_MAX_TOP = 32
+
+
+def logprob(logits: torch.Tensor, targets: torch.Tensor = None, top_n: int = 0, *, out=None):
+    """NEW: per row of ``logits`` (fp16 [rows, vocab], rows ``stride(0) >= vocab`` apart) the log-probability and rank of
+    ``targets`` (int64 [rows] on the GPU) and the ``top_n`` (0 .. 32) most probable tokens with their log-probabilities --
+    ``atom_logprob_f16``, the contract of DESIGN.md 4.14, on the sampler's arithmetic: the distribution ``ops.sample`` draws from at
+    T = 1 without truncation.  Returns ``(logprob, rank, top_ids, top_logprobs)``: float32 [rows], int32 [rows] (0 is the greedy token),
+    int64 and float32 [rows, top_n]; None for what was not asked (no ``targets``: the first two; ``top_n = 0``: the last two).  A
+    target outside 0 .. vocab - 1 is ignored: log-probability 0, rank -1.  ``out``: a tuple of four preallocated buffers (None where
+    nothing is asked) for capture.  One launch; nothing is read back, nothing synchronises."""
+    if not logits.is_cuda:
+        raise L.AtomHipError("logits must live on the GPU: the log-probability op has no CPU fallback")
+    if logits.dtype != torch.float16:
+        raise TypeError(f"logits must be float16, got {logits.dtype}")
+    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [rows, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
+    rows, vocab = logits.shape
+    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), vocab)
+    top_n = int(top_n)
+    if not 0 <= top_n <= LOGPROB_MAX_TOP:
+        raise ValueError(f"top_n must be 0 .. {LOGPROB_MAX_TOP}, got {top_n}")
+    if targets is None and top_n == 0:
+        raise ValueError("nothing to do: no targets and top_n = 0")
+    if targets is not None and not (targets.is_cuda and targets.dtype == torch.int64 and targets.shape == (rows,) and targets.is_contiguous()):
+        raise TypeError(f"targets must be a contiguous int64 tensor of [{rows}] on the GPU, got {targets.dtype} {tuple(targets.shape)} on {targets.device}")
+    want = ((torch.float32, (rows,), targets is not None), (torch.int32, (rows,), targets is not None),
+            (torch.int64, (rows, top_n), top_n > 0), (torch.float32, (rows, top_n), top_n > 0))
+    if out is not None and len(out) != 4:
+        raise TypeError("out must be a tuple of four: (logprob, rank, top_ids, top_logprobs)")
+    bufs = []
+    for i, (dtype, shape, asked) in enumerate(want):
+        b = None if out is None else out[i]
+        if not asked:
+            b = None
+        elif b is None:
+            b = torch.empty(shape, dtype=dtype, device=logits.device)
+        elif not (b.is_cuda and b.dtype == dtype and tuple(b.shape) == shape and b.is_contiguous()):
+            raise TypeError(f"out[{i}] must be a contiguous {dtype} tensor of {list(shape)} on the GPU")
+        bufs.append(b)
+    st = L.lib().atom_logprob_f16(logits.data_ptr(), ld, rows, vocab, L.ptr(targets), L.ptr(bufs[0]), L.ptr(bufs[1]), top_n,
+                                  L.ptr(bufs[2]), L.ptr(bufs[3]), L.current_stream(logits.device))
+    L.check(st, "atom_logprob_f16")
+    return tuple(bufs)

@@ -674,6 +674,34 @@ int atom_kv_quant_u4_f16(const void *k, void *packed, void *param, int64_t T, in
 int atom_sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
                     const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t step_offset, int64_t *tokens, void *stream);
 
+/*
+ * Token log-probabilities: per row of fp16 logits, the log-probability and rank of a target token and the top-n tokens with their
+ * log-probabilities -- csrc/logprob.hip, on the sampler's arithmetic (csrc/sample_math.h), the contract in DESIGN.md 4.14.  What it
+ * reports is the distribution atom_sample_f16 draws from at T = 1 without truncation.
+ *   logits fp16 [rows, vocab], row stride ld >= vocab elements; targets int64 [rows] or NULL; logprob float [rows] or NULL;
+ *   rank int32 [rows] or NULL; top_ids int64 / top_logprobs float [rows, top_n], required exactly when top_n >= 1; 0 <= top_n <= 32.
+ * A row's result is a pure function of the row's bits and its target -- not of the grid, the batch or the order of any atomic:
+ *   1. l_i, the order (l_i descending, lower index first) and m = max l_i as steps 1 - 2 of atom_sample_f16.
+ *   2. w_i = the sampler's weight of l_i under m at T = 1 (never the sampler's temperature); Z = SUM w_i, an exact integer, 2^40 <= Z < 2^59.
+ *   3. lz = (float)(log((double)Z) - 40 ln 2): Z converted round-to-nearest, log in double precision (sample_math.h log_z).
+ *   4. lp_i = (l_i - m) - lz, two FP32 operations, one rounding each; l_i = -inf gives -inf.
+ *   5. targets[r] = t in 0 .. vocab - 1: logprob[r] = lp_t, rank[r] = #{i : l_i > l_t} + #{i < t : l_i = l_t}, the 0-based position in
+ *      the order (the greedy token has rank 0).
+ *   6. any other t (negative, >= vocab): logprob[r] = 0, rank[r] = -1 (a loss's ignore_index); t is compared, never used as an address.
+ *   7. top_ids[r, j], top_logprobs[r, j], j < top_n: the first top_n tokens of the order, in that order, with their lp; entries
+ *      j >= vocab hold -1 and -inf.
+ *   8. a row of -inf only (m = -inf): every lp is -inf, rank = t for a target in range, top_ids are 0, 1, ...
+ * targets == NULL: logprob and rank are ignored, only the top-n is written.  The only inexact step is the double-precision log: a
+ * host's libm may differ from the device's in the last double bit, so after the rounding to float the kernel's lz is a checker's lz
+ * or a float32 neighbour of it.  One launch, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null logits, top_n >= 1 with a null top array, or nothing to do
+ * (top_n = 0 and no targets, or both logprob and rank null); ATOM_ERR_SHAPE for rows < 1, vocab < 1, vocab > 262144, ld < vocab or
+ * top_n outside 0 .. 32; ATOM_ERR_ALIGN for a pointer off its element size (2 bytes for logits, 4 for logprob / rank / top_logprobs,
+ * 8 for targets / top_ids).  Rows whose base is 16-byte aligned with ld % 8 == 0 are read with 16-byte loads.
+ */
+int atom_logprob_f16(const void *logits, int64_t ld, int64_t rows, int64_t vocab, const int64_t *targets, float *logprob, int32_t *rank,
+                     int64_t top_n, int64_t *top_ids, float *top_logprobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
