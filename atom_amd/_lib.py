@@ -99,6 +99,7 @@ SIGNATURES = {
     "atom_kv_quant_u4_f16": (_int, [_vp] * 3 + [_i64, _int, _int, _vp]),
     "atom_sample_f16": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64, _vp, _vp]),
     "atom_logprob_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "atom_penalize_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -9,7 +9,7 @@ launch on the same logits); ``score`` / ``perplexity`` run given sequences throu
 from __future__ import annotations
 
 import dataclasses
-from typing import Sequence, Union
+from typing import Mapping, Sequence, Union
 
 import torch
 
@@ -21,11 +21,26 @@ from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, S
 class SamplingParams:
     """How one sequence draws its tokens (ops.sample): ``temperature`` <= 0 is greedy, ``top_k`` outside 1 .. vocab - 1 and
     ``top_p`` >= 1 are off, ``seed`` is any 64-bit integer.  Token i of a sequence is draw number i of its seed: the stream is a
-    function of the seed and the logits alone, whatever the batch around it."""
+    function of the seed and the logits alone, whatever the batch around it.
+    What the sequence is drawn FROM (ops.penalize, in front of ops.sample): ``repetition_penalty`` divides the positive and multiplies
+    the other logits of every token of the prompt or generated so far (<= 0 and 1 are off), ``presence_penalty`` is subtracted once
+    from, ``frequency_penalty`` once per occurrence of, every token generated so far (the prompt does not count), ``logit_bias`` maps
+    token ids to a float added last (``-inf`` bans a token); at most 512 entries."""
     temperature: float = 1.0
     top_k: int = 0
     top_p: float = 1.0
     seed: int = 0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Mapping[int, float] = None
+
+    @property
+    def penalises(self) -> bool:
+        """False when the four penalty fields change no logit (the neutral row of ops.penalize)"""
+        rep = float(self.repetition_penalty)
+        return not ((not rep > 0 or rep == 1.0) and float(self.presence_penalty) == 0 and float(self.frequency_penalty) == 0
+                    and not self.logit_bias)
 
 
 @dataclasses.dataclass
@@ -73,6 +88,70 @@ class Sampler:
         return ops.sample(logits, self.temperature, self.top_k, self.top_p, self.seeds, step=step, step_offset=step_offset)
 
 
+class LogitPenalties:
+    """The penalty side of ``SamplingParams`` as device buffers at FIXED addresses, so a captured ``ops.penalize`` follows ``set`` and
+    the state it advances itself: ``state`` int16 [batch, vocab rounded up to 8] (per token: the sign bit says it occurs in the
+    prompt, the low 15 bits count how often it was generated), ``repetition`` / ``presence`` / ``frequency`` float32 [batch] and the
+    bias table ``bias_ids`` int32 / ``bias_vals`` float32 [batch, max_bias], padded with -1 / 0.  ``max_bias`` defaults to the longest
+    ``logit_bias`` of ``params``; a later ``set`` must fit it."""
+
+    def __init__(self, batch: int, vocab: int, device, params: Union[SamplingParams, Sequence[SamplingParams]] = SamplingParams(),
+                 max_bias: int = None):
+        self.batch, self.vocab = int(batch), int(vocab)
+        if max_bias is None:
+            ps = [params] if isinstance(params, SamplingParams) else list(params)
+            max_bias = max([len(q.logit_bias or ()) for q in ps if isinstance(q, SamplingParams)] or [0])
+        if not 0 <= int(max_bias) <= ops.PENALTY_MAX_BIAS:
+            raise ValueError(f"logit_bias: at most {ops.PENALTY_MAX_BIAS} entries per sequence, got {max_bias}")
+        self.max_bias = int(max_bias)
+        self.state = torch.zeros((self.batch, -(-self.vocab // 8) * 8), dtype=torch.int16, device=device)
+        self.repetition = torch.empty(self.batch, dtype=torch.float32, device=device)
+        self.presence = torch.empty(self.batch, dtype=torch.float32, device=device)
+        self.frequency = torch.empty(self.batch, dtype=torch.float32, device=device)
+        self.bias_ids = torch.empty((self.batch, self.max_bias), dtype=torch.int32, device=device)
+        self.bias_vals = torch.empty((self.batch, self.max_bias), dtype=torch.float32, device=device)
+        self.set(params)
+
+    def set(self, params: Union[SamplingParams, Sequence[SamplingParams]]):
+        """One ``SamplingParams`` for all sequences or one per sequence, copied into the buffers in place; the state is not touched."""
+        ps = [params] * self.batch if isinstance(params, SamplingParams) else list(params)
+        if len(ps) != self.batch or not all(isinstance(q, SamplingParams) for q in ps):
+            raise ValueError(f"sampling: one SamplingParams, or one per sequence ({self.batch})")
+        ids = torch.full((self.batch, self.max_bias), -1, dtype=torch.int32)
+        vals = torch.zeros((self.batch, self.max_bias), dtype=torch.float32)
+        for b, q in enumerate(ps):
+            bias = sorted((int(t), float(v)) for t, v in (q.logit_bias or {}).items())
+            if len(bias) > self.max_bias:
+                raise ValueError(f"logit_bias: {len(bias)} entries, this LogitPenalties holds {self.max_bias} per sequence")
+            if any(not 0 <= t < 2 ** 31 for t, _ in bias):
+                raise ValueError("logit_bias: token ids must be 0 .. 2^31 - 1")
+            if bias:
+                ids[b, :len(bias)] = torch.tensor([t for t, _ in bias], dtype=torch.int32)
+                vals[b, :len(bias)] = torch.tensor([v for _, v in bias], dtype=torch.float32)
+        self.repetition.copy_(torch.tensor([float(q.repetition_penalty) for q in ps], dtype=torch.float32))
+        self.presence.copy_(torch.tensor([float(q.presence_penalty) for q in ps], dtype=torch.float32))
+        self.frequency.copy_(torch.tensor([float(q.frequency_penalty) for q in ps], dtype=torch.float32))
+        self.bias_ids.copy_(ids)
+        self.bias_vals.copy_(vals)
+
+    def reset(self, prompts: Sequence[Sequence[int]]):
+        """Every count to zero, the prompt flag on the tokens of ``prompts`` (one list of ids per sequence; ids outside the
+        vocabulary are skipped).  Eager torch indexing: it runs once per generation."""
+        assert len(prompts) == self.batch
+        self.state.zero_()
+        rows = [b for b, p in enumerate(prompts) for t in p if 0 <= int(t) < self.vocab]
+        cols = [int(t) for p in prompts for t in p if 0 <= int(t) < self.vocab]
+        if rows:
+            dev = self.state.device
+            self.state[torch.tensor(rows, dtype=torch.int64, device=dev), torch.tensor(cols, dtype=torch.int64, device=dev)] = -32768
+
+    def apply(self, logits: torch.Tensor, fed: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+        """``logits`` fp16 [batch, vocab] penalised (ops.penalize, one launch); ``fed`` int64 [batch]: the tokens to count first."""
+        has_bias = self.max_bias > 0
+        return ops.penalize(logits, self.state, fed, self.repetition, self.presence, self.frequency,
+                            self.bias_ids if has_bias else None, self.bias_vals if has_bias else None, out=out)
+
+
 class DecodeGraph:
     """One decode step over ``static_kv``, run up to ``max_steps`` times: greedy, or sampled with ``sampler`` (a ``Sampler``, or
     ``SamplingParams`` -- one, or one per sequence -- to build ``self.sampler`` from).  Step i (from 0) takes draw number i + 1 of
@@ -90,10 +169,14 @@ class DecodeGraph:
     ``logprobs``: None is the step above.  0 adds one ops.logprob after the argmax / ops.sample, on the same logits with the chosen
     tokens as targets, and records ``token_logprobs`` float32 / ``token_ranks`` int32 [max_steps, batch]; 1 .. 32 also records the
     top-n, ``top_ids`` int64 / ``top_logprobs`` float32 [max_steps, batch, n].  The values are the model's distribution at T = 1
-    without truncation, whatever the sampler's parameters."""
+    without truncation, whatever the sampler's parameters.
+
+    ``penalties`` (a ``LogitPenalties``; needs a sampler): None is the step above, launch for launch.  Otherwise the step counts the
+    tokens of ``input_ids`` in ``penalties.state`` and penalises the logits into the static buffer ``penalised`` (ops.penalize, one
+    more launch), and ops.sample draws from that.  ``logits`` and the log-probabilities stay those of the raw logits."""
 
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None,
-                 logprobs: int = None):
+                 logprobs: int = None, penalties: LogitPenalties = None):
         assert max_steps >= 1
         self.model, self.kv, self.max_steps = model, static_kv, int(max_steps)
         device = static_kv.data.device
@@ -106,6 +189,12 @@ class DecodeGraph:
         self._blen = BatchLenInfo([], batch, device)
         self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
         assert self.sampler is None or self.sampler.batch == batch
+        self.penalties, self.penalised = penalties, None
+        if penalties is not None:
+            if self.sampler is None:
+                raise ValueError("DecodeGraph: penalties need a sampler (temperature = 0 is greedy over the penalised row)")
+            assert penalties.batch == batch and penalties.vocab == model.config.vocab_size
+            self.penalised = torch.zeros((batch, penalties.state.size(1)), dtype=torch.float16, device=device)[:, :penalties.vocab]
         self.logprobs = n = _check_logprobs(logprobs)
         self.token_logprobs = self.token_ranks = self.top_ids = self.top_logprobs = None
         if n is not None:
@@ -123,8 +212,11 @@ class DecodeGraph:
         logits, _ = self.model(self.input_ids, self._blen, None, self.kv)
         if self.sampler is None:
             nxt = logits.argmax(dim=-1)
-        else:
+        elif self.penalties is None:
             nxt = self.sampler.sample(logits, step=self._counter, step_offset=1)
+        else:                                              # the token fed in is counted, then the row is penalised: one launch
+            pen = self.penalties.apply(logits, fed=self.input_ids, out=self.penalised)
+            nxt = self.sampler.sample(pen, step=self._counter, step_offset=1)
         self.tokens.index_copy_(0, self._counter, nxt.unsqueeze(0))
         if self.logprobs is not None:
             got = ops.logprob(logits, nxt, self.logprobs)
@@ -166,7 +258,10 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
-    on the prompts beside it (as far as its logits do not).
+    on the prompts beside it (as far as its logits do not).  The penalty fields of ``SamplingParams`` (repetition, presence,
+    frequency, ``logit_bias``) change the logits a token is drawn from, on the device (ops.penalize): the prompt's tokens are flagged,
+    every new token is counted as it is fed back in.  With all of them at their defaults no state is allocated and no launch added;
+    ``return_logits`` and ``logprobs`` always describe the raw logits.
     The prompts are prefilled eagerly in one forward; the first new token is the argmax of each prompt's last row (or draw 0);
     the other ``max_new_tokens - 1`` come from a ``DecodeGraph`` over a ``StaticBatchedKvCacheInt4`` with that many tokens reserved
     from ``pool``.  All sequences run all steps (stopping is a host-side cut afterwards).
@@ -191,15 +286,22 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     last = torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1).to(device)
     all_logits = logits.index_select(0, last).unsqueeze(0)
     sampler = None if sampling is None else Sampler(len(prompts), device, sampling)
+    penalties = None
+    if sampler is not None and any(q.penalises for q in ([sampling] if isinstance(sampling, SamplingParams) else sampling)):
+        penalties = LogitPenalties(len(prompts), logits.size(-1), device, sampling)
+        penalties.reset(prompts)
     if sampler is None:
         new = all_logits.argmax(dim=-1)                        # [1, batch]
-    else:
+    elif penalties is None:
         new = sampler.sample(all_logits[0]).unsqueeze(0)
+    else:                                                      # nothing is generated yet: the prompt flags alone
+        new = sampler.sample(penalties.apply(all_logits[0])).unsqueeze(0)
     lp = None if n_lp is None else [x if x is None else x.unsqueeze(0) for x in ops.logprob(all_logits[0], new[0], n_lp)]
     if max_new_tokens > 1:
         static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
-            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp)
+            dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp,
+                             penalties=penalties)
             new = torch.cat([new, dg.run(new[0])])
             if lp is not None:
                 rest = (dg.token_logprobs, dg.token_ranks, dg.top_ids, dg.top_logprobs)

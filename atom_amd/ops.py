@@ -1095,3 +1095,68 @@ def logprob(logits: torch.Tensor, targets: torch.Tensor = None, top_n: int = 0, 
                                   L.ptr(bufs[2]), L.ptr(bufs[3]), L.current_stream(logits.device))
     L.check(st, "atom_logprob_f16")
     return tuple(bufs)
+
+
+# ------------------------------------------------------------------------------------------------ logit penalties
+PENALTY_MAX_BIAS = 512
+PENALTY_TILE = 2048            # elements per workgroup of atom_penalize_f16 (csrc/penalize.hip kPenTile)
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+
+
+def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor = None, repetition: torch.Tensor = None,
+             presence: torch.Tensor = None, frequency: torch.Tensor = None, bias_ids: torch.Tensor = None,
+             bias_vals: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+    """NEW: repetition / presence / frequency penalties and a per-row logit bias on ``logits`` (fp16 [batch, vocab], rows
+    ``stride(0) >= vocab`` apart) -- ``atom_penalize_f16``, the contract of DESIGN.md 4.15.  ``state`` int16 [batch, >= vocab] holds one
+    word per (sequence, token): the sign bit says the token occurs in the prompt, the low 15 bits count how often it was generated
+    (saturating).  With ``fed`` (int64 [batch]) the launch first counts token ``fed[b]`` in ``state[b]`` (a value outside
+    0 .. vocab - 1 counts nothing), then penalises.  ``repetition``, ``presence``, ``frequency``: float32 [batch]; ``bias_ids`` int32
+    [batch, max_bias] padded with -1 and ``bias_vals`` float32 [batch, max_bias], max_bias <= 512.  All DEVICE tensors that the launch
+    reads (a captured call follows buffers changed in place); None: no state, nothing fed, neutral, no bias.  Rows whose parameters
+    change nothing and elements that are neither seen nor biased are copied bit for bit.  Returns fp16 [batch, vocab] (``out`` if
+    given; ``out`` may be ``logits``).  One launch; nothing is read back, nothing synchronises."""
+    if not logits.is_cuda:
+        raise L.AtomHipError("logits must live on the GPU: the penalty op has no CPU fallback")
+    if logits.dtype != torch.float16:
+        raise TypeError(f"logits must be float16, got {logits.dtype}")
+    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
+    batch, vocab = logits.shape
+    for name, t in (("repetition", repetition), ("presence", presence), ("frequency", frequency)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == (batch,) and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous float32 tensor of [{batch}] on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    state_ld = 0
+    if state is not None:
+        if not (state.is_cuda and state.dtype == torch.int16 and state.dim() == 2 and state.size(0) == batch and state.size(1) >= vocab
+                and (state.size(1) == 1 or state.stride(1) == 1)):
+            raise TypeError(f"state must be an int16 tensor of [{batch}, >= {vocab}] with contiguous rows on the GPU")
+        state_ld = _row_stride(state)
+    if fed is not None:
+        if state is None:
+            raise ValueError("fed needs state: there is nothing to count into")
+        if not (fed.is_cuda and fed.dtype == torch.int64 and fed.shape == (batch,) and fed.is_contiguous()):
+            raise TypeError(f"fed must be a contiguous int64 tensor of [{batch}] on the GPU")
+    max_bias = 0
+    if (bias_ids is None) != (bias_vals is None):
+        raise ValueError("bias_ids and bias_vals come together")
+    if bias_ids is not None:
+        max_bias = bias_ids.size(1) if bias_ids.dim() == 2 else -1
+        if not (bias_ids.is_cuda and bias_vals.is_cuda and bias_ids.dtype == torch.int32 and bias_vals.dtype == torch.float32
+                and bias_ids.dim() == 2 and bias_ids.size(0) == batch and bias_vals.shape == bias_ids.shape
+                and bias_ids.is_contiguous() and bias_vals.is_contiguous()):
+            raise TypeError(f"bias_ids int32 and bias_vals float32 must be contiguous [{batch}, max_bias] tensors on the GPU")
+        if max_bias > PENALTY_MAX_BIAS:
+            raise ValueError(f"at most {PENALTY_MAX_BIAS} bias entries per row, got {max_bias}")
+    if out is None:
+        out = torch.empty((batch, vocab), dtype=torch.float16, device=logits.device)
+    elif not (out.is_cuda and out.dtype == torch.float16 and out.shape == (batch, vocab) and (vocab == 1 or out.stride(1) == 1)):
+        raise TypeError(f"out must be a float16 tensor of [{batch}, {vocab}] with contiguous rows on the GPU")
+    st = L.lib().atom_penalize_f16(logits.data_ptr(), _row_stride(logits), batch, vocab, L.ptr(state), state_ld, L.ptr(fed),
+                                   L.ptr(repetition), L.ptr(presence), L.ptr(frequency), L.ptr(bias_ids) if max_bias else None,
+                                   L.ptr(bias_vals) if max_bias else None, max_bias, out.data_ptr(), _row_stride(out),
+                                   L.current_stream(logits.device))
+    L.check(st, "atom_penalize_f16")
+    return out

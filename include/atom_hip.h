@@ -702,6 +702,48 @@ int atom_sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab
 int atom_logprob_f16(const void *logits, int64_t ld, int64_t rows, int64_t vocab, const int64_t *targets, float *logprob, int32_t *rank,
                      int64_t top_n, int64_t *top_ids, float *top_logprobs, void *stream);
 
+/*
+ * Logit penalties: repetition, presence and frequency penalties and a per-row logit bias on fp16 logits, with the occurrence state
+ * advanced in the same launch -- csrc/penalize.hip, arithmetic in csrc/penalty_math.h, the contract in DESIGN.md 4.15.  No reference
+ * counterpart.  The output feeds atom_sample_f16.
+ *   logits fp16 [batch, vocab], row stride ld >= vocab; out fp16 [batch, vocab], row stride out_ld >= vocab.  out may equal logits
+ *   (in place, then out_ld == ld); otherwise the two must not overlap.
+ *   state int16 [batch, state_ld >= vocab] or NULL: one word per (sequence, token).  The sign bit: the token occurs in the prompt.  The
+ *   low 15 bits: count, how often the token was fed back as a generated token, saturating at 32767.  NULL: nothing is seen, every
+ *   count is 0 (fed must be NULL too).
+ *   fed int64 [batch] or NULL; rep, pres, freq float [batch] or NULL (neutral: 1, 0, 0); bias_ids int32 [batch, max_bias] padded with
+ *   -1 and bias_vals float [batch, max_bias], 0 <= max_bias <= 512 (both may be NULL when max_bias == 0).  All DEVICE arrays, read by
+ *   the launch: a captured launch follows buffers that are changed in place.
+ * Row b:
+ *   1. Counting comes first: with fed given and 0 <= fed[b] < vocab, the count of state[b, fed[b]] is incremented (saturating, the
+ *      sign bit kept) BEFORE the row is penalised, whatever the row's parameters are.  Any other fed[b] counts nothing; fed is
+ *      compared with element positions, never used as an address.
+ *   2. rep is off (treated as 1) when !(rep > 0); otherwise it is clamped to [2^-10, 2^10].  The row is NEUTRAL when rep is off or 1,
+ *      pres == 0, freq == 0 and no bias entry of the row has an id >= 0: every 16-bit word of a neutral row is copied unchanged.
+ *   3. seen = the sign bit is set or count > 0.  In a non-neutral row an element that is not seen and has no bias entry is copied
+ *      bit for bit (NaN payloads, -0).
+ *   4. Every other element, in FP32 with one rounding per line:
+ *        l = (float)logit
+ *        seen and rep on:  l = l > 0 ? l / rep : l * rep
+ *        l = l - freq * (float)count              (the product, then the difference)
+ *        count > 0:        l = l - pres
+ *        bias entry:       l = l + bias
+ *        out = (fp16)l, round to nearest even
+ *      NaN, +-inf and a -inf bias follow IEEE; a computed NaN is written as 0x7E00 (IEEE leaves the payload open).  The prompt flag
+ *      triggers the repetition penalty only: presence and frequency see generated tokens (the vLLM / OpenAI meaning).
+ *   5. A bias id that is -1 (padding), negative or >= vocab is ignored.  Duplicate ids in one row are the caller's error: the result is
+ *      then one of the addition orders, and stays in bounds.
+ * One launch, a grid of (2048-element tile, row) workgroups, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null logits / out, fed without state, or max_bias > 0 with a null bias
+ * array; ATOM_ERR_SHAPE for batch < 1, batch > 65535, vocab < 1, vocab > 262144, ld / out_ld / state_ld < vocab, max_bias outside
+ * 0 .. 512, or out == logits with out_ld != ld; ATOM_ERR_ALIGN for a pointer off its element size (2 bytes for logits / out / state,
+ * 4 for rep / pres / freq / bias_ids / bias_vals, 8 for fed).  When logits, out and state are 16-byte aligned with leading dimensions
+ * that are multiples of 8, they are accessed 16 bytes at a time.
+ */
+int atom_penalize_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, int16_t *state, int64_t state_ld, const int64_t *fed,
+                      const float *rep, const float *pres, const float *freq, const int32_t *bias_ids, const float *bias_vals,
+                      int64_t max_bias, void *out, int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@
             host-to-device copies), one forward, argmax -- per token
     replay  atom_amd.e2e.DecodeGraph: the page tables stepped on the device (atom_kv_step_i4) and the whole step replayed from one graph
     sampled the same with a sampler (ops.sample in place of argmax: T = 0.8, top-k 50, top-p 0.95, one seed per sequence)
-    pair    replay and sampled, their repetitions alternating in one process (the fair comparison of the two)
+    pair    replay, sampled and penalised, their repetitions alternating in one process (the fair comparison of the three)
+    penalised  sampled with logit penalties in front (ops.penalize: repetition 1.1, presence 0.5, frequency 0.3, 16 bias entries per
+            sequence, 5 % of the vocabulary flagged as prompt tokens); pair leaves it out where --tree has no LogitPenalties
 
     python tools/generate_bench.py [--mode eager|replay|sampled|pair|both] [--batches 1,16] [--ctx 1024] [--steps 64] [--reps 5] [--layers 8]
                                    [--tree DIR]
@@ -87,7 +89,7 @@ def eager(model, batch):
     return [timed(step, args.steps) for _ in range(args.reps)]
 
 
-def replay_graph(model, batch, sampled):
+def replay_graph(model, batch, sampled, penalised=False):
     from atom_amd.e2e import DecodeGraph
     from atom_amd.utils import StaticBatchedKvCacheInt4
     total = WARM + args.reps * args.steps
@@ -97,6 +99,13 @@ def replay_graph(model, batch, sampled):
     if sampled:
         from atom_amd.e2e import SamplingParams
         kw["sampler"] = [SamplingParams(0.8, 50, 0.95, seed=b + 1) for b in range(batch)]
+    if penalised:
+        from atom_amd.e2e import LogitPenalties
+        bias = {t * (args.vocab // 16): -1.0 for t in range(16)}
+        kw["sampler"] = [SamplingParams(0.8, 50, 0.95, seed=b + 1, repetition_penalty=1.1, presence_penalty=0.5, frequency_penalty=0.3,
+                                        logit_bias=bias) for b in range(batch)]
+        kw["penalties"] = LogitPenalties(batch, args.vocab, dev, kw["sampler"])
+        kw["penalties"].reset([list(range(b, args.vocab, 20)) for b in range(batch)])
     dg = DecodeGraph(model, skv, total, **kw)
     timed(dg.step, WARM)                                      # the eager first step, the capture, six replays
     return dg, skv
@@ -110,9 +119,11 @@ def replay(model, batch, sampled=False):
 
 
 def pair(model, batch):
-    """greedy and sampled replay, one repetition of each in turn"""
-    graphs = [replay_graph(model, batch, sampled) for sampled in (False, True)]
-    us = ([], [])
+    """greedy, sampled and (where the tree has them) penalised replay, one repetition of each in turn"""
+    import atom_amd.e2e
+    forms = [(False, False), (True, False)] + ([(True, True)] if hasattr(atom_amd.e2e, "LogitPenalties") else [])
+    graphs = [replay_graph(model, batch, *form) for form in forms]
+    us = tuple([] for _ in graphs)
     for _ in range(args.reps):
         for (dg, _), out in zip(graphs, us):
             out.append(timed(dg.step, args.steps))
@@ -129,7 +140,7 @@ def main():
         for mode in modes:
             with torch.no_grad():
                 if mode == "pair":
-                    results += list(zip(("replay", "sampled"), pair(model, batch)))
+                    results += list(zip(("replay", "sampled", "penalised"), pair(model, batch)))
                 else:
                     results.append((mode, eager(model, batch) if mode == "eager" else replay(model, batch, mode == "sampled")))
         for mode, us in results:
