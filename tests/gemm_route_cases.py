@@ -136,6 +136,13 @@ class _Dev:
     def ptr(self, name):
         return self.t[name][0].data_ptr() + self.t[name][1]
 
+    def dev(self, name):
+        """the array as a torch tensor on the device (a view)"""
+        import torch
+        t, off, dtype, shape = self.t[name]
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        return t[off:off + n].view(torch.from_numpy(np.empty(0, dtype=dtype)).dtype).reshape(shape)
+
     def get(self, name):
         t, off, dtype, shape = self.t[name]
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
@@ -178,29 +185,38 @@ def check_route(lib, case):
         assert fits == 1, name
 
 
-def run(case):
-    """the digest of one case (and what the call returned)"""
+def call(case, src=None, flags=None):
+    """Make the call of one case and return (status, the device arrays by name, the names of its outputs in digest order).  `src`: the
+    operands -- A4 (packed, or the wide form for a case with ATOM_A_WIDE), B4, A8, B8, sA [G, ld], sA8 [ld] in the case's scale layout,
+    sB, sB8 -- in place of the seeded ones (tests/test_gpu_gemm_planted.py); `flags` in place of the case's own."""
     import torch
     from atom_amd import _lib
     lib = _lib.lib()
     name, entry, M, N, K, o = case
-    layout, flags, shift = o.get("layout", PLAIN), o.get("flags", 0), o.get("shift", {})
+    layout, flags, shift = o.get("layout", PLAIN), o.get("flags", 0) if flags is None else flags, o.get("shift", {})
     G = (K - G128) // G128
     stream = _lib.current_stream(torch.device("cuda"))
     nseg = o.get("nseg", 1)
     n_all = N * nseg if entry != "gateup" else 2 * N
-    src = _operands(M, n_all, K, seed=M * 1000003 + n_all * 1009 + K)
+    given = src is not None
+    if not given:
+        src = _operands(M, n_all, K, seed=M * 1000003 + n_all * 1009 + K)
     rng = np.random.default_rng(len(name) + M + n_all + K)
     ld = lib.atom_scale_size(M, layout)
     d = _Dev(shift)
     for k in ("B4", "B8", "sB", "sB8", "A8"):
         d.put(k, src[k])
-    d.put("sA", rng.uniform(0.005, 0.05, (G, ld)).astype(np.float16))
-    d.put("sA8", rng.uniform(0.005, 0.05, (ld,)).astype(np.float16))
-    if flags & A_WIDE:
-        d.put("A4", (rng.integers(-8, 8, (M, K - G128)) * 16).astype(np.int8))
+    if given:
+        assert src["sA"].shape == (G, ld) and src["sA8"].shape == (ld,) and src["A4"].shape == (M, (K - G128) // (1 if flags & A_WIDE else 2))
+        for k in ("sA", "sA8", "A4"):
+            d.put(k, src[k])
     else:
-        d.put("A4", src["A4"])
+        d.put("sA", rng.uniform(0.005, 0.05, (G, ld)).astype(np.float16))
+        d.put("sA8", rng.uniform(0.005, 0.05, (ld,)).astype(np.float16))
+        if flags & A_WIDE:
+            d.put("A4", (rng.integers(-8, 8, (M, K - G128)) * 16).astype(np.int8))
+        else:
+            d.put("A4", src["A4"])
     check_route(lib, case)
     rows = lambda r: (r + 255) // 256 * 256
     if (flags & AB_F6) or entry == "gateup":                    # the BF6 operands, by the library's own re-coding kernels
@@ -258,7 +274,7 @@ def run(case):
         st = lib.atom_gemm_w4a4_multi_q(q, d.put("x", x), None if x2 is None else d.put("x2", x2.astype(np.float16)), res, res_out, idx, 1e-5, 0.9,
                                         *(d.ptr(k) for k in ("B4", "sB", "B8", "sB8")), *seg_outs(), M, N, nseg, K, G128, G128, stream)
     elif entry == "merge_q":
-        part = rng.uniform(0.1, 1.0, (M, K // 128, o["splits"], 130)).astype(np.float32)
+        part = src["part"] if given and "part" in src else rng.uniform(0.1, 1.0, (M, K // 128, o["splits"], 130)).astype(np.float32)
         st = lib.atom_gemm_w4a4_multi_merge_q(d.put("part", part), o["splits"], d.put("idx", rng.permutation(K).astype(np.int16)), 0.9,
                                               *(d.ptr(k) for k in ("B4", "sB", "B8", "sB8")), *seg_outs(), M, N, nseg, K, G128, G128, stream)
     elif entry == "gateup":
@@ -269,6 +285,13 @@ def run(case):
     else:
         raise KeyError(entry)
     torch.cuda.synchronize()
+    return st, d, outs
+
+
+def run(case):
+    """the digest of one case (and what the call returned)"""
+    name, o = case[0], case[5]
+    st, d, outs = call(case)
     assert st == o.get("status", 0), f"{name}: status {st}"
     return f"status {st}" if st != 0 else _sha(*(d.get(k) for k in outs))
 
