@@ -30,6 +30,7 @@ B_SCALE_PAIRS = 0x2000     # ATOM_B_SCALE_PAIRS: output channels 2j, 2j+1 share 
 WS_VERIFY = 0x4000         # ATOM_WS_VERIFY: debug call -- the two assertions above are checked on the device first (synchronises)
 Q_REORDER, Q_RMSNORM, Q_ADD_RMSNORM, Q_SILU_MUL = 1, 2, 3, 4     # atom_gemm_w4a4_multi_q: q_op
 KV_STEP_OVERFLOW, KV_STEP_BAD_LENGTH = 1, 2                      # ATOM_KV_STEP_*: status bits of atom_kv_step_i4
+KV_BEAM_BAD_PARENT, KV_BEAM_BAD_PAGE = 4, 8                      # ATOM_KV_BEAM_*: status bits of atom_kv_beam_fork_i4, same word
 F6_PITCH = 104
 
 _vp = ctypes.c_void_p
@@ -100,6 +101,8 @@ SIGNATURES = {
     "atom_sample_f16": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64, _vp, _vp]),
     "atom_logprob_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "atom_penalize_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _i64, _vp]),
+    "atom_beam_select": (_int, [_vp] * 5 + [_i64, _int, _int, _int, _i64] + [_vp] * 6),
+    "atom_kv_beam_fork_i4": (_int, [_vp] * 10 + [_int, _int, _int, _i64] + [_int] * 4 + [_vp]),
 }
 
 _lib = None

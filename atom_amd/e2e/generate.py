@@ -5,6 +5,8 @@ every following token; ``generate`` is the loop around it: eager prefill, then r
 Nothing between two steps touches the host: no page-table upload, no ``.item()``, no logits on the host.
 With ``logprobs=`` a step also records the chosen token's log-probability, its rank and the top-n alternatives (ops.logprob, one more
 launch on the same logits); ``score`` / ``perplexity`` run given sequences through one prefill and one ops.logprob.
+``beam_search`` / ``BeamDecodeGraph`` are the beam-search form of the same loop: ops.logprob's top-n, ops.beam_select and the device-side
+fork of a ``StaticBeamKvCacheInt4`` inside the replayed step.
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ from typing import Mapping, Sequence, Union
 import torch
 
 from .. import ops
-from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, StaticBatchedKvCacheInt4
+from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, StaticBatchedKvCacheInt4, StaticBeamKvCacheInt4
 
 
 @dataclasses.dataclass(frozen=True)
@@ -254,7 +256,7 @@ class DecodeGraph:
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, *, eos_token_id: int = None,
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
-             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None):
+             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -272,7 +274,16 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     with ``max_new_tokens`` rows of device tensors, row 0 from the prompts' last prefill rows: every new token's log-probability and
     rank and, for n >= 1, the n most probable tokens of its step.  The values describe the model's distribution at T = 1 without
     truncation, whatever ``sampling`` is (a token drawn at another temperature or inside a top-k still gets the probability the
-    untempered, untruncated model gives it).  Rows after a prompt's EOS are computed like its tokens: cutting them is the caller's job."""
+    untempered, untruncated model gives it).  Rows after a prompt's EOS are computed like its tokens: cutting them is the caller's job.
+    ``num_beams`` (1 .. 16): beam search instead -- the tokens of ``beam_search``'s best hypothesis per prompt (``length_penalty`` 1), in
+    the same shape.  Out of scope with it, refused with ``ValueError``: ``sampling``, ``logprobs``, ``return_logits`` and ``caches``.
+    ``num_beams=None`` is the code above, launch for launch."""
+    if num_beams is not None:
+        refused = [name for name, given in (("sampling", sampling is not None), ("logprobs", logprobs is not None),
+                                            ("return_logits", bool(return_logits)), ("caches", caches is not None)) if given]
+        if refused:
+            raise ValueError(f"generate: num_beams does not combine with {', '.join(refused)}")
+        return [hyps[0].tokens for hyps in beam_search(model, prompts, max_new_tokens, pool, num_beams, eos_token_id=eos_token_id)]
     n_lp = _check_logprobs(logprobs)
     assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
     device = pool.buf.device
@@ -322,6 +333,160 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     if lp is not None:
         res = res + (TokenLogprobs(*lp),)
     return res if len(res) > 1 else out
+
+
+@dataclasses.dataclass(frozen=True)
+class BeamHypothesis:
+    """One result of ``beam_search``: the new ``tokens`` (cut after the first EOS), ``sum_logprob`` -- the FP32 sum of their
+    log-probabilities, accumulated on the device -- and ``score`` = sum_logprob / len(tokens) ** length_penalty in float64."""
+    tokens: list
+    sum_logprob: float
+    score: float
+
+
+def backtrack_beams(parents, tokens, cum, num_beams: int, eos_token_id=None, length_penalty: float = 1.0):
+    """The host side of beam search.  ``parents`` / ``tokens``: one list of groups * num_beams entries per step (a parent is the row
+    inside its group), ``cum``: the final rows' summed log-probabilities.  Follows every final row back to step 0, cuts the tokens
+    after the first ``eos_token_id`` and ranks each group by score descending, then beam index: a list of ``BeamHypothesis`` per group."""
+    W, steps = int(num_beams), len(tokens)
+    out = []
+    for g in range(len(cum) // W):
+        hyps = []
+        for b in range(W):
+            row, toks = b, []
+            for t in range(steps - 1, -1, -1):
+                toks.append(int(tokens[t][g * W + row]))
+                row = int(parents[t][g * W + row])
+            toks.reverse()
+            if eos_token_id is not None and eos_token_id in toks:
+                toks = toks[:toks.index(eos_token_id) + 1]
+            s = float(cum[g * W + b])
+            hyps.append((BeamHypothesis(toks, s, s / float(len(toks)) ** float(length_penalty)), b))
+        out.append([h for h, _ in sorted(hyps, key=lambda hb: (-hb[0].score, hb[1]))])
+    return out
+
+
+class BeamDecodeGraph:
+    """One beam-search step over a ``StaticBeamKvCacheInt4``, run up to ``max_steps`` times, as ``DecodeGraph`` runs a decode step: the
+    first ``step()`` eager, the second captured, the rest replays; nothing reaches the host in between.  A step is ``kv.step()``, the
+    model's forward on groups * num_beams rows, ``ops.logprob(top_n=num_beams)``, ``ops.beam_select`` (the beams' state ``cum`` float32 /
+    ``finished`` int32 / ``length`` int32 [rows] is updated in place), the winners' ``parents`` int32 / ``tokens`` int64 recorded in row
+    i of [max_steps, rows] at the device counter, ``kv.fork(parent)`` and the tokens written back as the next input.  The caller sets
+    ``input_ids`` and the state from the step after the prefill (``run``)."""
+
+    def __init__(self, model, beam_kv: StaticBeamKvCacheInt4, max_steps: int, *, eos_token_id: int = None):
+        assert max_steps >= 1
+        self.model, self.kv, self.max_steps = model, beam_kv, int(max_steps)
+        self.eos = -1 if eos_token_id is None else int(eos_token_id)
+        device = beam_kv.data.device
+        self.num_beams = W = beam_kv.num_beams
+        self.batch = batch = beam_kv.groups * W
+        if W > model.config.vocab_size:
+            raise ValueError(f"{W} beams over a vocabulary of {model.config.vocab_size}")
+        self.input_ids = torch.zeros(batch, dtype=torch.int64, device=device)
+        self.tokens = torch.zeros((self.max_steps, batch), dtype=torch.int64, device=device)
+        self.parents = torch.zeros((self.max_steps, batch), dtype=torch.int32, device=device)
+        self.cum = torch.zeros(batch, dtype=torch.float32, device=device)
+        self.finished = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.length = torch.zeros(batch, dtype=torch.int32, device=device)
+        self._parent = torch.zeros(batch, dtype=torch.int32, device=device)
+        self._token = torch.zeros(batch, dtype=torch.int64, device=device)
+        self._top = (None, None, torch.zeros((batch, W), dtype=torch.int64, device=device),
+                     torch.zeros((batch, W), dtype=torch.float32, device=device))
+        self._counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self._blen = BatchLenInfo([], batch, device)
+        self._graph = None
+        self.steps_done = 0
+
+    @torch.no_grad()
+    def _step(self):
+        self.kv.step()
+        logits, _ = self.model(self.input_ids, self._blen, None, self.kv)
+        _, _, top_ids, top_lp = ops.logprob(logits, None, self.num_beams, out=self._top)
+        ops.beam_select(top_ids, top_lp, self.cum, self.finished, self.length, self.eos, self.num_beams,
+                        out=(self._parent, self._token, self.cum, self.finished, self.length))
+        self.parents.index_copy_(0, self._counter, self._parent.unsqueeze(0))
+        self.tokens.index_copy_(0, self._counter, self._token.unsqueeze(0))
+        self.kv.fork(self._parent)
+        self.input_ids.copy_(self._token)
+        self._counter.add_(1)
+
+    def step(self):
+        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
+        if self.steps_done >= self.max_steps:
+            raise RuntimeError(f"BeamDecodeGraph: all {self.max_steps} steps are taken")
+        if self.steps_done == 0:
+            self._step()
+        else:
+            if self._graph is None:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
+                    self._step()
+                self._graph = graph
+            self._graph.replay()
+        self.steps_done += 1
+
+    def run(self, first_tokens: torch.Tensor, cum: torch.Tensor, finished: torch.Tensor, length: torch.Tensor):
+        """Feed the winners of the step after the prefill ([rows] each) and take every step that is left; returns ``(parents, tokens)``."""
+        self.input_ids.copy_(first_tokens.reshape(self.batch))
+        self.cum.copy_(cum)
+        self.finished.copy_(finished)
+        self.length.copy_(length)
+        while self.steps_done < self.max_steps:
+            self.step()
+        return self.parents, self.tokens
+
+
+@torch.no_grad()
+def beam_search(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, num_beams: int, *,
+                eos_token_id: int = None, length_penalty: float = 1.0, num_return: int = 1, return_trace: bool = False):
+    """Beam search for a batch of prompts (lists of token ids) with ``num_beams`` (1 .. 16) beams each: per prompt a list of the
+    ``num_return`` best ``BeamHypothesis``, best first.  The prompts are prefilled eagerly in one forward, as ``generate`` does; the
+    first beams are the ``num_beams`` most probable first tokens (ops.logprob on the prompts' last rows, ops.beam_select with one row
+    per group); the other ``max_new_tokens - 1`` steps come from a ``BeamDecodeGraph`` over a ``StaticBeamKvCacheInt4`` reserved from
+    ``pool`` (per prompt about num_beams x the pages of the new tokens, plus one spare per beam).  All beams run all steps: a beam that
+    produced ``eos_token_id`` is frozen -- it keeps its summed log-probability and competes with it, un-normalised, against the live
+    beams.  After the loop one read of the cache's status word, then the host follows ``parents`` / ``tokens`` back,
+    cuts every hypothesis after its first EOS and ranks by ``sum_logprob / length ** length_penalty`` (float64), ties by beam index.
+    ``return_trace``: also return the search's record ``(parents int32, tokens int64 [max_new_tokens, rows], sum_logprob float32
+    [rows])``, rows = prompts x num_beams, as device tensors -- what the host followed back.
+    Out of scope: sampling, penalties, log-probability records, returned logits, caller-owned caches, early stopping."""
+    W = int(num_beams)
+    if not 1 <= W <= ops.BEAM_MAX_BEAMS:
+        raise ValueError(f"num_beams must be 1 .. {ops.BEAM_MAX_BEAMS}, got {num_beams}")
+    if not 1 <= int(num_return) <= W:
+        raise ValueError(f"num_return must be 1 .. num_beams, got {num_return}")
+    assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
+    device, G = pool.buf.device, len(prompts)
+    lens = [len(p) for p in prompts]
+    seqs = [KvCacheInt4(pool, 0) for _ in prompts]
+    try:
+        for c, n in zip(seqs, lens):
+            c.acquire(n)
+        ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=device)
+        logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
+        if W > logits.size(-1):
+            raise ValueError(f"{W} beams over a vocabulary of {logits.size(-1)}")
+        last = torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1).to(device)
+        _, _, top_ids, top_lp = ops.logprob(logits.index_select(0, last), None, W)
+        zi = torch.zeros(G, dtype=torch.int32, device=device)
+        parent, token, cum, finished, length = ops.beam_select(top_ids, top_lp, torch.zeros(G, dtype=torch.float32, device=device), zi, zi,
+                                                               eos_token_id, W, w_in=1)
+        parents, tokens = parent.unsqueeze(0), token.unsqueeze(0)
+        if max_new_tokens > 1:
+            kv = StaticBeamKvCacheInt4(seqs, W, reserve=max_new_tokens - 1)
+            try:
+                bg = BeamDecodeGraph(model, kv, max_new_tokens - 1, eos_token_id=eos_token_id)
+                more = bg.run(token, cum, finished, length)
+                parents, tokens, cum = torch.cat([parents, more[0]]), torch.cat([tokens, more[1]]), bg.cum
+            finally:
+                kv.close()                                     # the one sync_host()
+        hyps = backtrack_beams(parents.tolist(), tokens.tolist(), cum.tolist(), W, eos_token_id, length_penalty)
+    finally:
+        for c in seqs:
+            c.release()
+    hyps = [h[:int(num_return)] for h in hyps]
+    return (hyps, (parents, tokens, cum)) if return_trace else hyps
 
 
 @torch.no_grad()

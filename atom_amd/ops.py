@@ -1160,3 +1160,78 @@ def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor
                                    L.current_stream(logits.device))
     L.check(st, "atom_penalize_f16")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ beam search
+BEAM_MAX_BEAMS = 16
+
+
+def beam_select(top_ids: torch.Tensor, top_lp: torch.Tensor, cum: torch.Tensor, finished: torch.Tensor, length: torch.Tensor,
+                eos, w_out: int, *, w_in: int = None, out=None):
+    """NEW: the selection step of beam search -- ``atom_beam_select``, the contract of DESIGN.md 4.16.  ``top_ids`` int64 / ``top_lp``
+    float32 [groups * w_in, C] are ``ops.logprob(..., top_n=C)``'s outputs for the ``w_in`` rows of every prompt group (``w_in=1``
+    for the step after the prefill, default ``w_out``; ``w_out`` <= C <= 32); ``cum`` float32, ``finished`` int32 and ``length`` int32
+    [groups * w_in] each row's summed log-probability, end flag and token count; ``eos`` the ending token (None or negative: none).
+    Returns ``(parent, token, cum, finished, length)`` of the ``w_out`` (1 .. 16) winners per group, [groups * w_out] each: ``parent``
+    int32 is the row INSIDE the group.  The winners are the first of (score descending, parent ascending, candidate ascending) with
+    score = cum + top_lp in one FP32 addition; a finished row is one frozen candidate.  ``out``: a tuple of five preallocated
+    buffers for capture; with ``w_in == w_out`` the last three may be ``cum``, ``finished``, ``length`` themselves.  One launch; nothing
+    is read back, nothing synchronises."""
+    for t in (top_ids, top_lp, cum, finished, length):
+        if not t.is_cuda:
+            raise L.AtomHipError("beam_select operands must live on the GPU: no CPU fallback")
+    w_out = int(w_out)
+    if not 1 <= w_out <= BEAM_MAX_BEAMS:
+        raise ValueError(f"w_out must be 1 .. {BEAM_MAX_BEAMS}, got {w_out}")
+    if top_ids.dim() != 2 or top_ids.shape != top_lp.shape or top_ids.dtype != torch.int64 or top_lp.dtype != torch.float32:
+        raise TypeError("top_ids int64 and top_lp float32 must both be [rows, C]")
+    rows, C = top_ids.shape
+    if not w_out <= C <= LOGPROB_MAX_TOP:
+        raise ValueError(f"C must be w_out .. {LOGPROB_MAX_TOP}, got {C} for w_out {w_out}")
+    w_in = w_out if w_in is None else int(w_in)
+    if w_in not in (1, w_out) or rows % w_in:
+        raise ValueError(f"w_in must be 1 or w_out ({w_out}) and divide the {rows} rows, got {w_in}")
+    groups = rows // w_in
+    for name, t, dtype in (("cum", cum, torch.float32), ("finished", finished, torch.int32), ("length", length, torch.int32)):
+        if not (t.dtype == dtype and t.shape == (rows,) and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous {dtype} tensor of [{rows}]")
+    if not (top_ids.is_contiguous() and top_lp.is_contiguous()):
+        raise TypeError("top_ids and top_lp must be contiguous")
+    want = (torch.int32, torch.int64, torch.float32, torch.int32, torch.int32)
+    if out is not None and len(out) != 5:
+        raise TypeError("out must be a tuple of five: (parent, token, cum, finished, length)")
+    if out is None:
+        out = tuple(torch.empty(groups * w_out, dtype=d, device=top_ids.device) for d in want)
+    for i, (b, d) in enumerate(zip(out, want)):
+        if not (b.is_cuda and b.dtype == d and b.shape == (groups * w_out,) and b.is_contiguous()):
+            raise TypeError(f"out[{i}] must be a contiguous {d} tensor of [{groups * w_out}] on the GPU")
+    st = L.lib().atom_beam_select(top_ids.data_ptr(), top_lp.data_ptr(), cum.data_ptr(), finished.data_ptr(), length.data_ptr(),
+                                  groups, w_in, w_out, C, -1 if eos is None else int(eos), *(b.data_ptr() for b in out),
+                                  L.current_stream(top_ids.device))
+    L.check(st, "atom_beam_select")
+    return tuple(out)
+
+
+def kv_beam_fork_i4(kv, parent: torch.Tensor):
+    """NEW: the cache step of beam search -- row r of a utils.StaticBeamKvCacheInt4 continues the history of row ``parent[r]`` of its
+    group (``parent`` int32 [rows], the row inside the group: ``ops.beam_select``'s output).  ``atom_kv_beam_fork_i4``
+    shares the parent's full pages by reference and copies its one partial page into the row's spare page; it gathers into
+    ``kv.table_out``, and one device-to-device copy on the same stream brings ``kv.page_table`` / ``kv.spare`` up to date, so
+    ``ops.kv_step_i4`` keeps reading the one fixed table.  Two stream operations, no host synchronisation, capturable.  A parent outside
+    the group keeps its row and sets the cache's status word (read by ``kv.sync_host()``)."""
+    tensors = (kv.page_table, kv.table_out, kv.spare, kv.spare_out, kv.row_pages, kv.lengths, kv.state, parent)
+    for t in tensors + (kv.data, kv.param):
+        if not t.is_cuda:
+            raise L.AtomHipError("KV-cache page tables must live on the GPU: no CPU fallback")
+    for t in tensors:
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    batch, cap = kv.page_table.shape
+    assert kv.table_out.shape == (batch, cap) and kv.spare.numel() == kv.spare_out.numel() == kv.row_pages.numel() == batch
+    assert kv.lengths.numel() == 2 * batch and kv.state.numel() == 4 and parent.numel() == batch and batch % kv.num_beams == 0
+    num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
+    st = L.lib().atom_kv_beam_fork_i4(kv.data.data_ptr(), kv.param.data_ptr(), kv.page_table.data_ptr(), kv.table_out.data_ptr(),
+                                      kv.spare.data_ptr(), kv.spare_out.data_ptr(), kv.row_pages.data_ptr(), kv.lengths.data_ptr(),
+                                      kv.state.data_ptr(), parent.data_ptr(), batch, kv.num_beams, cap, kv.data.size(0), num_layers,
+                                      num_heads, page_size, head_dim, L.current_stream(kv.page_table.device))
+    L.check(st, "atom_kv_beam_fork_i4")
+    kv.tables.copy_(kv.tables_out)                           # page_table and spare are views of one buffer: one copy

@@ -3,7 +3,8 @@ KvCacheInt4 :58-98, BatchedKvCacheInt4 :101-128): same class / property / method
 code written against the reference's objects runs on these.  Host-side only; the device work is in atom_amd.ops
 (init_kv_i4 / append_kv_i4 / batch_decode_i4 -> csrc/kv_i4.hip, batch_prefill_i4 -> csrc/prefill_i4.hip).
 ``StaticBatchedKvCacheInt4`` (not in the reference) keeps the page tables at fixed device addresses and advances them on the device
-(ops.kv_step_i4 -> csrc/kv_step.hip), for decode steps replayed from a captured graph.
+(ops.kv_step_i4 -> csrc/kv_step.hip), for decode steps replayed from a captured graph.  ``StaticBeamKvCacheInt4`` is its beam-search
+form: several rows per prompt that share full pages and are reordered on the device (ops.kv_beam_fork_i4 -> csrc/beam.hip).
 
 Pool layout (reference kvcache.py:17-26, page.cuh:78-110):
     buf    uint8 [capacity, num_layers, 2, num_heads, block_len, head_dim // 2]   packed u4, K at [.., 0, ..], V at [.., 1, ..]
@@ -180,3 +181,103 @@ class StaticBatchedKvCacheInt4:
         finally:
             for c in self._kv:
                 c.trim()
+
+
+class StaticBeamKvCacheInt4:
+    """The static cache of a beam search: ``num_beams`` rows per prompt (row g * W + b is beam b of prompt g, ``groups`` prompts), with
+    the attributes of ``StaticBatchedKvCacheInt4`` -- every attention op and ``ops.kv_step_i4`` take it unchanged -- plus ``fork(parent)``
+    (ops.kv_beam_fork_i4): row r continues the history of row ``parent[r]`` of its group, on the device.  Full pages are shared between
+    rows by reference; only the one partial page is ever copied, into the row's ``spare`` page.
+
+    ``prompt_seqs`` hold the prefilled prompts (no spare pages).  Per row the constructor takes from the pool the pages from the
+    prompt's partial-page position to the end of ``reserve`` more tokens (beam 0 starts in the prompt's own last page, so one fewer
+    where that page is partial) and one spare; if the pool cannot give them all it raises before keeping any.  Every row is pointed at
+    its prompt's pages, then one ``fork`` with every parent 0: beam 0 keeps appending into the prompt's own last page, the other beams
+    get copies.  From then on pages change rows on the device; the host tracks only the SET it allocated, and ``close()`` returns
+    exactly that set.  The prompt sequences keep their page lists and lengths, but the contents of a prompt's partial last page are
+    consumed by the search: release the prompt sequences after ``close()``, not before.
+
+    ``page_table`` / ``spare`` are views of one buffer ``tables`` and ``table_out`` / ``spare_out`` of ``tables_out``: a fork gathers
+    from the first into the second and copies back in one device-to-device copy."""
+
+    def __init__(self, prompt_seqs: Sequence[KvCacheInt4], num_beams: int, reserve: int):
+        assert len(prompt_seqs) > 0 and 1 <= int(num_beams) <= 16 and reserve >= 0
+        pool = prompt_seqs[0].pool
+        assert all(c.pool is pool for c in prompt_seqs)
+        assert len({id(c) for c in prompt_seqs}) == len(prompt_seqs)
+        P, W, device = pool.block_len, int(num_beams), pool.buf.device
+        assert all(len(c.indicies) == -(-c.seqlen // P) for c in prompt_seqs), "prompt sequences must hold no spare pages"
+        self.groups, self.num_beams = len(prompt_seqs), W
+        row_pages = [max(1, -(-(c.seqlen + reserve) // P)) for c in prompt_seqs]
+        # pages a row needs of its own: from the prompt's partial-page position on (beam 0: from behind the prompt's pages), one spare
+        need = [[n - (len(c.indicies) if b == 0 else c.seqlen // P) + 1 for b in range(W)] for c, n in zip(prompt_seqs, row_pages)]
+        total = sum(sum(x) for x in need)
+        if total > pool.num_free_blocks:
+            raise RuntimeError(f"StaticBeamKvCacheInt4: {total} pages needed ({self.groups} prompts x {W} beams, reserve {reserve}), "
+                               f"{pool.num_free_blocks} free in the pool")
+        self._pool = pool
+        self._pages = [pool.alloc_block() for _ in range(total)]     # the set close() returns
+        fresh = iter(self._pages)
+        batch, cap = self.groups * W, max(row_pages)
+        rows, spare = [], []
+        for c, n, per_beam in zip(prompt_seqs, row_pages, need):
+            for b in range(W):
+                own = [next(fresh) for _ in range(per_beam[b])]
+                spare.append(own.pop())
+                row = list(c.indicies[:n - len(own)]) + own
+                rows.append(row + [row[-1]] * (cap - n))              # padding: never read (row_pages bounds every row)
+        self.data = pool.buf
+        self.param = pool.param
+        self.max_pages = cap
+        self.seqlens = [c.seqlen for c in prompt_seqs for _ in range(W)]
+        self.tables = torch.tensor([i for r in rows for i in r] + spare, dtype=torch.int32, device=device)
+        self.tables_out = torch.zeros_like(self.tables)
+        self.page_table, self.spare = self.tables[:batch * cap].view(batch, cap), self.tables[batch * cap:]
+        self.table_out, self.spare_out = self.tables_out[:batch * cap].view(batch, cap), self.tables_out[batch * cap:]
+        self.row_pages = torch.tensor([n for n in row_pages for _ in range(W)], dtype=torch.int32, device=device)
+        self._dev = torch.tensor(self.seqlens + [0] * batch + [0, 0, 0, 0], dtype=torch.int32, device=device)
+        self.lengths = self._dev[:2 * batch]
+        self.state = self._dev[2 * batch:]
+        self.indptr = torch.zeros(batch + 1, dtype=torch.int32, device=device)
+        self.indicies = torch.zeros(batch * cap, dtype=torch.int32, device=device)
+        self.last_page_offset = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.fork(torch.zeros(batch, dtype=torch.int32, device=device))
+        self.step(0)
+
+    @property
+    def page_size(self):
+        return self.data.size(-2)
+
+    def step(self, add: int = 1):
+        """One launch on the current stream: every row gains ``add`` tokens (0: rebuild the tables only).  Capturable."""
+        from .. import ops
+        ops.kv_step_i4(self, add)
+
+    def fork(self, parent: torch.Tensor):
+        """Row r continues row ``parent[r]`` (int32 [groups * num_beams] on the device, the row inside the group) of its group:
+        ops.kv_beam_fork_i4.  The next ``step()`` rebuilds the tables the attention ops read.  Capturable."""
+        from .. import ops
+        ops.kv_beam_fork_i4(self, parent)
+
+    def sync_host(self):
+        """Read the lengths and the status word back (one copy, the only synchronisation) into ``seqlens``.  Raises if a row ran out of
+        reserved pages, a stored length was out of range, or a fork met a parent outside its group or a page outside the pool (the
+        row was kept as it was); the status word is cleared."""
+        batch = self.groups * self.num_beams
+        host = self._dev.tolist()
+        status, parity = host[2 * batch], host[2 * batch + 1] & 1
+        self.seqlens = host[parity * batch:(parity + 1) * batch]
+        if status:
+            self.state[0].zero_()
+            raise RuntimeError(f"StaticBeamKvCacheInt4: status {status} (1: a row needed more than its reserved pages and was not "
+                               f"advanced, 2: a stored length was out of range, 4: a fork's parent was outside its group, 8: a fork met "
+                               f"a page id outside the pool); lengths now {self.seqlens}")
+
+    def close(self):
+        """``sync_host()``, then every page the constructor took goes back to the pool."""
+        try:
+            self.sync_host()
+        finally:
+            for idx in self._pages:
+                self._pool.free_block(idx)
+            self._pages = []

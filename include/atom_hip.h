@@ -744,6 +744,71 @@ int atom_penalize_f16(const void *logits, int64_t ld, int64_t batch, int64_t voc
                       const float *rep, const float *pres, const float *freq, const int32_t *bias_ids, const float *bias_vals,
                       int64_t max_bias, void *out, int64_t out_ld, void *stream);
 
+/*
+ * Beam search, the selection step: per prompt group, the next w_out beams out of the candidates of its w_in rows -- csrc/beam.hip,
+ * arithmetic in csrc/beam_math.h, the contract in DESIGN.md 4.16.  No reference counterpart.  The candidates are the top-n of
+ * atom_logprob_f16: the best w_out of all w_in x vocab continuations lie within the union of each row's best w_out.
+ *   top_ids int64 / top_lp float [groups * w_in, C]: row b's C most probable tokens and their log-probabilities, in its order;
+ *   cum float, finished int32 (0 / non-zero), length int32 [groups * w_in]: each row's sum of log-probabilities, whether it has ended
+ *   and how many tokens it holds; eos: the token that ends a hypothesis, negative for none.
+ *   parent int32 (the row INSIDE the group, 0 .. w_in - 1), token int64, cum_out float, finished_out int32, length_out int32
+ *   [groups * w_out].  An output may be the input of the same name when w_in == w_out; otherwise the arrays must not overlap.
+ *   1 <= w_out <= 16; w_in is 1 (the step after the prefill) or w_out; w_out <= C <= 32.
+ * Group g, rows b = 0 .. w_in - 1:
+ *   1. A live row (finished == 0) has the candidates (b, c), c = 0 .. C - 1, with score s = cum[b] + top_lp[b][c]: ONE FP32 addition.
+ *   2. A finished row has exactly one candidate, (b, 0), with score cum[b]: the hypothesis is frozen and competes by its final sum.
+ *      Nothing is normalised by length during the search.
+ *   3. Scores are compared through a 32-bit key: u = the score's bits; -0 -> +0; NaN -> -inf; key = u & 0x80000000 ? ~u : u | 0x80000000.
+ *      A larger key is a larger score; -inf has the smallest key.  No NaN arises from clean inputs: a log-probability is never +inf,
+ *      hence neither is a sum of them, and -inf + lp is -inf.
+ *   4. The winners are the first w_out candidates of the total order: key descending, then b ascending, then c ascending
+ *      (atom_logprob_f16 already orders equal log-probabilities by token id).  Output i of the group is the i-th of them.
+ *   5. A winner (b, c) of a live row: parent = b, token = top_ids[b][c], cum_out = s, length_out = length[b] + 1,
+ *      finished_out = (eos >= 0 and token == eos).
+ *   6. The winner of a finished row: parent = b, token = max(eos, 0), cum_out = cum[b], length_out = length[b], finished_out = 1.
+ *   7. Fewer than w_out candidates (only w_in == 1 with a finished row): the remaining outputs are parent 0, token max(eos, 0),
+ *      cum_out -inf, finished_out 1, length_out = length[0].
+ * Token ids pass through unchanged: they are never used as an address here.  One launch of `groups` workgroups, no workspace, nothing
+ * read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer; ATOM_ERR_SHAPE for groups < 1, w_out outside 1 .. 16,
+ * w_in neither 1 nor w_out, C < w_out or C > 32; ATOM_ERR_ALIGN for a pointer off its element size (8 bytes for top_ids / token, 4 for
+ * the others).
+ */
+int atom_beam_select(const int64_t *top_ids, const float *top_lp, const float *cum, const int32_t *finished, const int32_t *length,
+                     int64_t groups, int w_in, int w_out, int C, int64_t eos, int32_t *parent, int64_t *token, float *cum_out,
+                     int32_t *finished_out, int32_t *length_out, void *stream);
+
+/*
+ * Beam search, the cache step: the rows of a static INT4 paged cache (the buffers of atom_kv_step_i4) reordered by `parent`, on the
+ * device -- csrc/beam.hip, DESIGN.md 4.16.  Row r of group r / w continues the history of row p = (r / w) * w + parent[r].
+ *   kv_data / kv_param: the pool (layout above), `capacity` pages; both 16-byte aligned.
+ *   table_in int32 [batch, cap], spare_in int32 [batch]: the page tables and one page per row that no table references (read only);
+ *   table_out, spare_out: what the launch writes; they must not overlap table_in / spare_in (rows are read by other rows'
+ *   workgroups).  The caller copies them back, device to device on the same stream.
+ *   row_pages, lens, state: as atom_kv_step_i4; the lengths are READ at the current parity (state[1] & 1) and not written.
+ *   parent int32 [batch], each in 0 .. w - 1; batch is a multiple of w, 1 <= w <= 16.
+ * All rows of a group hold the same number of tokens L (the invariant of beam search).  With full = L / page_size, off = L % page_size:
+ *   j < full             table_out[r][j] = table_in[p][j]: full pages are immutable and shared by reference.
+ *   j == full, off > 0   p == r: table_in[r][j].  Otherwise page table_in[p][j] is copied whole (both pool buffers: all layers, K and V,
+ *                        all heads; 16-byte loads and stores) into page spare_in[r]; table_out[r][j] = spare_in[r] and
+ *                        spare_out[r] = table_in[r][j].  (Else spare_out[r] = spare_in[r].)
+ *   later j              table_out[r][j] = table_in[r][j]: the row's own untouched reserve.
+ * So no partial page is ever referenced by two rows, and the page a row writes is never one another row reads in the same launch.
+ * A parent outside 0 .. w - 1 keeps the row as it is and sets ATOM_KV_BEAM_BAD_PARENT in state[0]; a length outside the row's reserve
+ * is clamped and sets ATOM_KV_STEP_BAD_LENGTH; a page id outside 0 .. capacity - 1 where a copy is due keeps the row and sets
+ * ATOM_KV_BEAM_BAD_PAGE -- it is never used as an address.  Every id written is one read from table_in or spare_in.
+ * One launch, nothing read back: capturable.
+ * Errors: ATOM_ERR_INVALID_ARG for a null pointer or table_out / spare_out overlapping table_in / spare_in; ATOM_ERR_SHAPE for the
+ * cache's shape (head_dim != 128, page_size not a multiple of 16, ...), w outside 1 .. 16, batch not a multiple of w, cap < 1,
+ * capacity < 1, cap * page_size or batch * cap beyond int32; ATOM_ERR_ALIGN for kv_data / kv_param off 16 bytes or a table off 4.
+ */
+#define ATOM_KV_BEAM_BAD_PARENT 4
+#define ATOM_KV_BEAM_BAD_PAGE 8
+int atom_kv_beam_fork_i4(void *kv_data, void *kv_param, const int32_t *table_in, int32_t *table_out, const int32_t *spare_in,
+                         int32_t *spare_out, const int32_t *row_pages, const int32_t *lens, int32_t *state, const int32_t *parent,
+                         int batch, int w, int cap, int64_t capacity, int num_layers, int num_heads, int page_size, int head_dim,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
