@@ -1352,17 +1352,24 @@ struct QSa {
 };
 #endif
 
-template <class C, bool PAIR = false>
+template <class C, bool PAIR = false, bool SA2 = false>
 struct QRegs {
   v8i af[4];            // feature fragments of the current stage
   v8i bf[3];            // token fragments: [2] block 0, [0] blocks 2,4,6, [1] odd blocks
   float sb[2][PAIR ? 4 : 8];   // weight scales of feature-block pair h: [h][2 r + (fb & 1)]; PAIR (channels 2 j, 2 j + 1 share theirs): [h][r]
   QSa sa[4];            // token scales, ring by token block % 4
+  v2f_t sa2[2];         // SA2: the same ring as the pairs one two-address read returns: [0] blocks 0,1 (mod 4), [1] blocks 2,3
   v4f_t acc[2][2];
   // lane byte addresses in LDS, [set][piece]: set 0 serves stage slots 0 and 1 (+ instruction offset), set 1 = + 2 stages for
   // slot 2.  All opaque to the compiler: it would otherwise re-derive one from another with a v_add per use, or merge two 8-byte
   // loads of a fragment into a ds_read2_b64 (half the LDS rate).
   int aW[2][3], aA[2][3], aS[2], aB[2];
+  int aS2[3][4];        // SA2: lane address of token row 32 j + 2 (l % 16) in stage slot s, [s][j] (ds_read2 offsets are 8 bits: no
+                        // instruction offset reaches another slot or block pair)
+  __device__ __forceinline__ float tscale(int tb) const {
+    if constexpr (SA2) return sa2[(tb & 3) >> 1][tb & 1];
+    else return sa[tb & 3];
+  }
 #ifdef ATOM_F6_PAIR128                       // tools, TIMING ONLY: lane addresses of a pair-interleaved record (see q_frag_pair)
   int aWp[2][3];
 #endif
@@ -1373,12 +1380,33 @@ struct QRegs {
 template <int SL> __device__ __forceinline__ constexpr int q_set() { return SL == 2 ? 1 : 0; }
 template <class C, int SL> __device__ __forceinline__ constexpr int q_imm() { return SL == 1 ? QC<C>::STAGE : 0; }
 
-template <class C, int SL>
+// A load from a lane's LDS byte address + a compile-time offset, for a kernel whose `lds` array starts at LDS byte 0 (the q kernel: no
+// static LDS, and its LDS-DMA's M0 values assume the same).  Through `lds + a + imm` the compiler learns the array's base too late to
+// fold it, and where imm is 0 a `v_add_u32 x, 0, a` stays in front of the load (9 per three K steps in the 256x256 kernel's loop).
+template <class T>
+__device__ __forceinline__ T q_ld0(int a, int imm) {
+#if defined(__HIP_DEVICE_COMPILE__)                           // (an LDS pointer is 32 bits wide on the device only)
+  typedef const __attribute__((address_space(3))) char *cp_t;
+  typedef const __attribute__((address_space(3))) T *tp_t;
+  return *(tp_t)((cp_t)(unsigned)a + imm);
+#else
+  return T{};
+#endif
+}
+template <class C, int SL, bool Z = false>   // Z: `lds` is LDS byte 0 (q_ld0)
 __device__ __forceinline__ v8i q_frag(const char *lds, const int (&a)[2][3], int off, int ro) {
   const char *b = lds + (SL < 0 ? ro : q_imm<C, SL>()) + off;
-  const v2u x = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][0]);
-  const v2u y = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][1]);
-  const v2u z = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][2]);
+  v2u x, y, z;
+  if constexpr (Z) {
+    const int imm = (SL < 0 ? 0 : q_imm<C, SL>()) + off, r = SL < 0 ? ro : 0;
+    x = q_ld0<v2u>(a[q_set<SL>()][0] + r, imm);
+    y = q_ld0<v2u>(a[q_set<SL>()][1] + r, imm);
+    z = q_ld0<v2u>(a[q_set<SL>()][2] + r, imm);
+  } else {
+    x = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][0]);
+    y = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][1]);
+    z = *reinterpret_cast<const v2u *>(b + a[q_set<SL>()][2]);
+  }
   asm volatile("" ::: "memory");   // keeps the compiler from pairing this fragment's loads with the next fragment's
   return v8i{(int)x.x, (int)x.y, (int)y.x, (int)y.y, (int)z.x, (int)z.y, 0, 0};
 }
@@ -1412,6 +1440,14 @@ __device__ __forceinline__ QSa q_scale(const char *lds, const RG &R, int off, in
   // i.e. the fp16 copy read as a float; found by tests/test_gpu_block.py, kept out by tests/test_abi_cpu.py's disassembly check)
   return QSa(*reinterpret_cast<const v2f_t *>(lds + (SL < 0 ? ro : q_imm<C, SL>()) + off + R.aS[q_set<SL>()]));
 #endif
+}
+// SA2: the token scales of blocks 2 j and 2 j + 1 in ONE read.  Their rows 32 j + 2 (l % 16) and that + 1 are adjacent records, so the
+// two fp32 copies sit at dwords 25 and 51 off the same lane address: a two-address dword read (ds_read2_b32), 4 scale reads per K step
+// instead of 8.  Both halves of the result are used, so the pair is one live value until its first use without QSa's help.
+template <class C, int SL, class RG>
+__device__ __forceinline__ v2f_t q_scale2(const char *lds, const RG &R, int j, int ro) {
+  const int a = R.aS2[SL < 0 ? 0 : SL][j] + (SL < 0 ? ro : 0);
+  return v2f_t{q_ld0<float>(a, 100), q_ld0<float>(a, PITCH + 100)};
 }
 template <class C, int SL, class RG>
 __device__ __forceinline__ void q_load_sb(const char *lds, RG &R, int h, int ro) {   // 8 consecutive features of pair h
@@ -1458,8 +1494,8 @@ __device__ __forceinline__ void q_piece(const QDma &d, const uint8_t *wsrc, cons
 // behind the MFMAs of slots 8..15.
 struct QNoEarly { __device__ __forceinline__ void operator()(int) const {} };
 // `early(i)`, i = 0..7: behind the MFMAs of slots 0..7 (step 0 issues the LDS-DMA of stage 1 there; published by the same mid-step barrier)
-template <class C, int SL, bool PAIR, class FS, class FD, class FE = QNoEarly>
-__device__ __forceinline__ void q_step(QRegs<C, PAIR> &R, const char *lds, float (&c)[4][8][4], FS sync, FD mid, int ro = 0, int rn = 0,
+template <class C, int SL, bool PAIR, bool SA2, class FS, class FD, class FE = QNoEarly>
+__device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, float (&c)[4][8][4], FS sync, FD mid, int ro = 0, int rn = 0,
                                        bool LAST = false, FE early = FE(), unsigned *tp = nullptr) {   // LAST (only with SL < 0): no next int4 stage to prefetch from
   // tp (traced tools build, ONE step of two workgroups): s_memtime at the head of every pair slot [i], in front of / behind the mid-step
   // wait + barrier [16], [17], behind the step [18], and around every slot's loads-and-DMA section [32 + 2 i], [33 + 2 i] -- with an
@@ -1482,32 +1518,36 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR> &R, const char *lds, float
     stamp(32 + 2 * i);
     // ---- loads behind this slot's MFMAs, into registers whose last reader has just issued
     if (h == 1 && i < 12 && tb + 2 < 8) {
-      R.bf[p_buf(tb + 2)] = q_frag<C, SL>(lds, R.aA, p_row(tb + 2) * PITCH, ro);
-      R.sa[(tb + 2) & 3] = q_scale<C, SL>(lds, R, p_row(tb + 2) * PITCH, ro);
+      R.bf[p_buf(tb + 2)] = q_frag<C, SL, SA2>(lds, R.aA, p_row(tb + 2) * PITCH, ro);
+      if constexpr (SA2) {                                   // blocks tb + 2, tb + 3 together; the ring pair's last reader (block
+        if ((tb & 1) == 0) R.sa2[((tb + 2) & 3) >> 1] = q_scale2<C, SL>(lds, R, (tb + 2) >> 1, ro);   // tb - 1, de-quantised in slot i - 1) is done
+      } else R.sa[(tb + 2) & 3] = q_scale<C, SL>(lds, R, p_row(tb + 2) * PITCH, ro);
     }
     if (!LAST) {
       if (i == 12) {                                         // next step's block 0 (buffer 2: free since slot 1)
-        R.bf[2] = q_frag<C, NX>(lds, R.aA, p_row(0) * PITCH, rn);
-        R.sa[0] = q_scale<C, NX>(lds, R, p_row(0) * PITCH, rn);
+        R.bf[2] = q_frag<C, NX, SA2>(lds, R.aA, p_row(0) * PITCH, rn);
+        if constexpr (!SA2) R.sa[0] = q_scale<C, NX>(lds, R, p_row(0) * PITCH, rn);
       }
       if (i == 13) {                                         // fragments fb 0,1: last read by this slot
 #ifdef ATOM_F6_PAIR128
         q_frag_pair<C, NX>(lds, R.aWp, p_row(0) * PITCH, rn, R.af[0], R.af[1]);
 #else
-        R.af[0] = q_frag<C, NX>(lds, R.aW, p_row(0) * PITCH, rn);
-        R.af[1] = q_frag<C, NX>(lds, R.aW, p_row(1) * PITCH, rn);
+        R.af[0] = q_frag<C, NX, SA2>(lds, R.aW, p_row(0) * PITCH, rn);
+        R.af[1] = q_frag<C, NX, SA2>(lds, R.aW, p_row(1) * PITCH, rn);
 #endif
       }
       if (i == 15) {
 #ifdef ATOM_F6_PAIR128
         q_frag_pair<C, NX>(lds, R.aWp, p_row(2) * PITCH, rn, R.af[2], R.af[3]);
 #else
-        R.af[2] = q_frag<C, NX>(lds, R.aW, p_row(2) * PITCH, rn);
-        R.af[3] = q_frag<C, NX>(lds, R.aW, p_row(3) * PITCH, rn);
+        R.af[2] = q_frag<C, NX, SA2>(lds, R.aW, p_row(2) * PITCH, rn);
+        R.af[3] = q_frag<C, NX, SA2>(lds, R.aW, p_row(3) * PITCH, rn);
 #endif
-        R.bf[1] = q_frag<C, NX>(lds, R.aA, p_row(1) * PITCH, rn);        // next step's block 1
-        R.sa[1] = q_scale<C, NX>(lds, R, p_row(1) * PITCH, rn);
+        R.bf[1] = q_frag<C, NX, SA2>(lds, R.aA, p_row(1) * PITCH, rn);        // next step's block 1
+        if constexpr (!SA2) R.sa[1] = q_scale<C, NX>(lds, R, p_row(1) * PITCH, rn);
       }
+      // SA2: the next step's blocks 0 and 1 in slot 14 -- block 5, the last reader of this ring pair, is de-quantised in slot 12
+      if constexpr (SA2) { if (i == 14) R.sa2[0] = q_scale2<C, NX>(lds, R, 0, rn); }
     }
     if (i >= 8) mid(i - 8);
     else early(i);
@@ -1517,7 +1557,7 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR> &R, const char *lds, float
     // ---- de-quantisation of the previous slot's pair (slot 15 of the previous step for i == 0)
     {
       const int j = (i + 15) & 15, dtb = p_tb(j), dh = p_h(j);
-      deq_pair<PAIR>(R.acc[j & 1][0], R.acc[j & 1][1], R.sa[dtb & 3], R.sb[dh], c[2 * dh][dtb], c[2 * dh + 1][dtb]);
+      deq_pair<PAIR>(R.acc[j & 1][0], R.acc[j & 1][1], R.tscale(dtb), R.sb[dh], c[2 * dh][dtb], c[2 * dh + 1][dtb]);
     }
     // weight scales: pair 0's registers die with slot 13's de-quantisation (done in slot 14) and take the next stage's values;
     // pair 1's die with the carried pair (slot 15, done in the next step's slot 0) and take the current stage's
@@ -1543,7 +1583,10 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR> &R, const char *lds, float
 //    they are converted and stored (two 16-byte stores per lane) behind the MFMAs of the following slot, so that the kernel's
 //    store tail -- 2-4 us with all 256 workgroups storing 32 MiB at once after the loop -- shrinks to the last block's.
 // Same arithmetic as p_keeper: bit-identical results.  Same-box A/B at 4096^3: two pipelined half-steps 56.6 us, this 55.6.
-template <class C, bool STORE, int NTB>
+//  * WHOLE (the caller's wave-uniform promise that the tile lies inside the output and that its byte offsets fit 32 bits): a store is
+//    scalar base of the token block's first row + one loop-invariant 32-bit lane offset + instruction offset 64 h -- no bounds compare
+//    and no 64-bit multiply per store.  Ragged tiles keep the checked path.
+template <class C, bool STORE, int NTB, bool WHOLE = false>
 __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, const char *slot1, int wm, int wn, int lane, float (&c)[4][NTB][4],
                                          int m0, int n0) {
   constexpr bool MERGED = true;
@@ -1579,13 +1622,18 @@ __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sb[h][j] = (float)hv[j]; asm volatile("" : "+v"(sb[h][j])); }   // opaque: no v_fma_mix re-folding
   }
+  unsigned dvoff = 0;                                                  // WHOLE: byte offset of (row 2 l15, feature 8 kb) of this wave's part
+  if constexpr (STORE && WHOLE) {
+    dvoff = (unsigned)(((wm * (16 * NTB) + 2 * l15) * p.N + wn * 64 + 8 * kb) * 2);
+    asm volatile("" : "+v"(dvoff));
+  }
   auto store_block = [&](int tb) {                                     // fp16 outputs of token block tb: 8 consecutive features per pair
     const int m = m0 + wm * (16 * NTB) + p_row(tb) + 2 * l15;
-    if (m >= p.M) return;
+    if constexpr (!WHOLE) { if (m >= p.M) return; }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int n = n0 + wn * 64 + 32 * h + 8 * kb;
-      if (n >= p.N) continue;
+      if constexpr (!WHOLE) { if (n >= p.N) continue; }
       v4u o;
       half_t *ov = reinterpret_cast<half_t *>(&o);
 #pragma unroll
@@ -1593,7 +1641,12 @@ __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, 
         ov[2 * r] = f2h(c[2 * h][tb][r]);
         ov[2 * r + 1] = f2h(c[2 * h + 1][tb][r]);
       }
-      *reinterpret_cast<v4u *>(p.D + (int64_t)m * p.N + n) = o;
+      if constexpr (WHOLE) {
+        char *dtb = reinterpret_cast<char *>(p.D + ((int64_t)(m0 + p_row(tb)) * p.N + n0));   // the block's first row: wave-uniform
+        *reinterpret_cast<v4u *>(dtb + dvoff + 64 * h) = o;
+      } else {
+        *reinterpret_cast<v4u *>(p.D + (int64_t)m * p.N + n) = o;
+      }
     }
   };
   auto dequant = [&](int j) {                                          // pair slot j: token block j / 2, feature-block pair j % 2
@@ -1720,7 +1773,12 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
   kstamp(2);
 
   const int l15 = lane & 15, kb = lane >> 4;
-  QRegs<C, PAIR> R;
+#ifdef ATOM_Q_NO_SA2                                        // A/B builds (tools/ab_build.sh): the token scales one read each
+  constexpr bool SA2 = false;
+#else
+  constexpr bool SA2 = PAIR && GU == 0;                     // the headline instantiation: it has the registers for aS2 (see QRegs)
+#endif
+  QRegs<C, PAIR, SA2> R;
   {
     const int lw = wn * 64 * PITCH + l15 * (2 * PITCH) + kb * 24;
     const int la = C::A_OFF + wm * 128 * PITCH + l15 * (2 * PITCH);
@@ -1738,17 +1796,32 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
       }
       R.aS[st] = la + 96 + st * 2 * Q::STAGE;
       R.aB[st] = (wn * 64 + 8 * kb) * 4 + st * 2 * Q::STAGE;
-      asm volatile("" : "+v"(R.aS[st]), "+v"(R.aB[st]));
+      if constexpr (!SA2) asm volatile("" : "+v"(R.aS[st]));
+      asm volatile("" : "+v"(R.aB[st]));
     }
-    R.bf[2] = q_frag<C, 0>(lds, R.aA, p_row(0) * PITCH, 0);
+    if constexpr (SA2) {
 #pragma unroll
-    for (int fb = 0; fb < 4; ++fb) R.af[fb] = q_frag<C, 0>(lds, R.aW, p_row(fb) * PITCH, 0);
-    R.bf[1] = q_frag<C, 0>(lds, R.aA, p_row(1) * PITCH, 0);
+      for (int sl = 0; sl < 3; ++sl)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          R.aS2[sl][j] = la + sl * Q::STAGE + p_row(2 * j) * PITCH;
+          asm volatile("" : "+v"(R.aS2[sl][j]));
+        }
+    }
+    R.bf[2] = q_frag<C, 0, SA2>(lds, R.aA, p_row(0) * PITCH, 0);
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) R.af[fb] = q_frag<C, 0, SA2>(lds, R.aW, p_row(fb) * PITCH, 0);
+    R.bf[1] = q_frag<C, 0, SA2>(lds, R.aA, p_row(1) * PITCH, 0);
     R.bf[0] = R.bf[1];
-    R.sa[0] = q_scale<C, 0>(lds, R, p_row(0) * PITCH, 0);
-    R.sa[1] = q_scale<C, 0>(lds, R, p_row(1) * PITCH, 0);
-    R.sa[2] = 0.f;
-    R.sa[3] = 0.f;                                          // the "carried pair" of the first step: zeros x 0
+    if constexpr (SA2) {
+      R.sa2[0] = q_scale2<C, 0>(lds, R, 0, 0);
+      R.sa2[1] = v2f_t{0.f, 0.f};                           // the "carried pair" of the first step: zeros x 0
+    } else {
+      R.sa[0] = q_scale<C, 0>(lds, R, p_row(0) * PITCH, 0);
+      R.sa[1] = q_scale<C, 0>(lds, R, p_row(1) * PITCH, 0);
+      R.sa[2] = 0.f;
+      R.sa[3] = 0.f;                                        // the "carried pair" of the first step: zeros x 0
+    }
     q_load_sb<C, 0>(lds, R, 0, 0);
     q_load_sb<C, 0>(lds, R, 1, 0);
 #pragma unroll
@@ -1762,12 +1835,16 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
   // step s on slot SL: regular (the LDS-DMA of int4 stage s + 2 behind the mid-step barrier), K0 / K1 (the keeper halves instead)
   auto reg = [&](auto sl, int s) {
     constexpr int SL = decltype(sl)::value;
-    if constexpr (TR) { if (s < 44) kstamp(16 + s); }
+#ifndef ATOM_TR_LOOP_ONLY                                   // (-DATOM_TR_LOOP_ONLY, tools/ab_build.sh: a traced build stamped around the whole
+    if constexpr (TR) { if (s < 44) kstamp(16 + s); }       //  loop only -- every step then runs the code the product build runs)
+#endif
     const int g = s + 2;
     const uint8_t *wsrc = wsrc0 + g * wstep, *asrc = asrc0 + g * astep;
     const float *sbsrc = sbsrc0 + (int64_t)g * p.f6_rows_b;
     unsigned *tp = nullptr;
+#ifndef ATOM_TR_LOOP_ONLY
     if constexpr (TR) { if (trb && s == 9) tp = trb + 64; }   // the in-step stamps of K step 9 (a slot-0 body in the middle of the loop)
+#endif
     q_step<C, SL, PAIR>(R, lds, c, sync, [&](int i) { q_piece<C, (SL + 2) % 3>(d, wsrc, asrc, sbsrc, i); }, 0, 0, false, QNoEarly(), tp);
   };
   using S0 = std::integral_constant<int, 0>;
@@ -1794,7 +1871,9 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
   if (s + 2 < G) { reg(S0(), s); ++s; }
   if (s + 2 < G) { reg(S1(), s); ++s; }
   for (; s < G; ++s) {
+#ifndef ATOM_TR_LOOP_ONLY
     if constexpr (TR) { if (s < 44) kstamp(16 + s); }
+#endif
     const int g = s + 2;                                    // the stage this step's LDS-DMA fetches: int4 g, or keeper half g - G
     const int dsl = g % 3;
     const uint8_t *wsrc = wsrc0 + g * wstep, *asrc = asrc0 + g * astep;
@@ -1809,13 +1888,23 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
                   },
                   (s % 3) * Q::STAGE, ((s + 1) % 3) * Q::STAGE, s + 1 == G);
   }
-  deq_pair<PAIR>(R.acc[1][0], R.acc[1][1], R.sa[3], R.sb[1], c[2][7], c[3][7]);   // the carried pair (slot 15) of the last int4 step
+  deq_pair<PAIR>(R.acc[1][0], R.acc[1][1], R.tscale(7), R.sb[1], c[2][7], c[3][7]);   // the carried pair (slot 15) of the last int4 step
   // keeper half 0 was published by the last mid-step barrier; half 1 was issued behind it: ONE step over both once it has landed
   kstamp(4);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   kstamp(5); kstamp(6);
-  q_keeper<C, GU == 0>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);   // GU == 0: the fp16 output leaves from inside this step
+  if constexpr (GU == 0) {                                  // the fp16 output leaves from inside this step
+#ifdef ATOM_Q_NO_WHOLE                                      // A/B builds: every tile through the checked stores
+    const bool whole = false;
+#else
+    const bool whole = m0 + C::BM <= p.M && n0 + C::BN <= p.N && p.N <= (1 << 21);   // decided once per workgroup; see q_keeper
+#endif
+    if (whole) q_keeper<C, true, 8, true>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+    else q_keeper<C, true, 8, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+  } else {
+    q_keeper<C, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+  }
   if constexpr (TR) {
     kstamp(7);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2480,7 +2569,7 @@ static bool launch_gemm_f6_tools(const GemmParams &p, int cfg, hipStream_t s, in
          : cfg == 1016 ? f6::launch_p<C256, 16>(q, s)
          : cfg == 1005 ? f6::launch_x16<f6::Cfg<128, 128, 2, 2, 3, 1>, false, 2, false, true>(q, s)
          : cfg == 1009 ? f6::launch_x16<f6::Cfg<64, 128, 1, 3, 3, 1>, false, 2, false, true>(q, s)
-         : cfg == 2016 ? f6::launch_q<C256, 0, true>(q, s)
+         : cfg == 2016 ? (q.b_pairs ? f6::launch_q<C256, 0, true, true>(q, s) : f6::launch_q<C256, 0, true>(q, s))   // (pairs: the headline's body)
                        : f6::launch_qk<f6::Cfg<128, 128, 2, 3, 3, 1>, true>(q, s);
     return true;
   }
