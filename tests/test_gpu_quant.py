@@ -8,7 +8,7 @@ import torch
 
 from oracle import atom_oracle as O
 from tests import quant_planted as P
-from tests.helpers import assert_quant_equal, bits16, rand_act, scales_plain, t2n, wide_codes
+from tests.helpers import _check_tail, assert_quant_equal, bits16, rand_act, scales_plain, t2n, wide_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -16,29 +16,6 @@ pytestmark = pytest.mark.gpu
 def _ops():
     from atom_amd import ops
     return ops
-
-
-def _check_tail(outs, ref, M, layout, exact=True, xq_ref=None):
-    o8, o4, s8, s4 = outs[:4]
-    q4 = O.unpack_int4(t2n(o4).view(np.uint8))
-    q8 = t2n(o8)
-    s4p = scales_plain(s4, M, layout).T          # -> [M, G]
-    s8p = scales_plain(s8, M, layout)
-    if exact:
-        assert np.array_equal(q4, ref["q4"]), f"int4 codes differ at {np.argwhere(q4 != ref['q4'])[:5]}"
-        assert np.array_equal(q8, ref["q8"])
-        assert np.array_equal(bits16(s4p), bits16(ref["s4"]))
-        assert np.array_equal(bits16(s8p), bits16(ref["s8"]))
-        if len(outs) == 5 and xq_ref is not None:
-            assert np.array_equal(bits16(t2n(outs[4])), bits16(xq_ref))
-    else:
-        # transcendental (expf) differs by ulps between libraries: codes +-1 on a tiny fraction, scales 1 fp16 ulp
-        d4 = np.abs(q4.astype(np.int32) - ref["q4"])
-        d8 = np.abs(q8.astype(np.int32) - ref["q8"])
-        assert d4.max() <= 1 and d8.max() <= 1
-        assert (d4 > 0).mean() < 2e-3 and (d8 > 0).mean() < 2e-3
-        assert np.abs(bits16(s4p).astype(np.int32) - bits16(ref["s4"]).astype(np.int32)).max() <= 1
-        assert np.abs(bits16(s8p).astype(np.int32) - bits16(ref["s8"]).astype(np.int32)).max() <= 1
 
 
 SHAPES = [(1, 256), (9, 1024), (33, 4096), (5, 5120), (3, 11008), (2, 13824), (2, 16384), (300, 512)]
