@@ -19,6 +19,11 @@
 // Why the lengths are double-buffered: every workgroup reads ALL current lengths while slice 0 of each group writes the new ones.  The
 // last workgroup to arrive (one agent-scope atomic per workgroup, after its reads) flips the parity for the next launch; nothing in
 // a launch ever reads what the same launch wrote.
+//
+// atom_kv_step_rows_i4 (speculative decoding) is the same kernel body with the count read per sequence from a device
+// array `adds` and a look-ahead: `lens` receives the COMMITTED length len + adds[b], the tables are built for that length + lookahead.
+// The slots behind the committed length are tentative -- a verify step writes K + 1 tokens there, the next launch commits the accepted
+// ones and the rest is overwritten; there is no rollback and no negative count.
 #include "common.h"
 #include "kv_attn.h"
 
@@ -31,18 +36,26 @@ struct KvStepParams {
   const int32_t *table, *rows;
   int32_t *lens, *indptr, *indices, *lpo, *state;
   int batch, cap, P, add;
+  const int32_t *adds;   // atom_kv_step_rows_i4: the count per sequence instead of `add`
+  int look;              // ... and the tentative slots behind the committed length that the tables cover too
 };
 
-// new length of a sequence and its status bits; its reserve holds min(row_pages, cap) * P tokens
-__device__ __forceinline__ int step_len(int len, int add, int row_pages, int cap, int P, int &flag) {
+// A sequence's new COMMITTED length (the return value, what goes into `lens`), the length its tables are built for (`tab`: the
+// committed length + look) and its status bits; its reserve holds min(row_pages, cap) * P tokens.  If add + look does not fit the
+// reserve, the whole request is refused: the sequence keeps its length and its tables are those of that length.
+__device__ __forceinline__ int step_len(int len, int add, int look, int row_pages, int cap, int P, int &flag, int &tab) {
   const int maxlen = min(max(row_pages, 0), cap) * P;
   flag = 0;
   if (len < 0) { len = 0; flag = ATOM_KV_STEP_BAD_LENGTH; }
   if (len > maxlen) { len = maxlen; flag = ATOM_KV_STEP_BAD_LENGTH; }
-  if (add > maxlen - len) { flag |= ATOM_KV_STEP_OVERFLOW; return len; }
+  if (add < 0) { add = 0; flag |= ATOM_KV_STEP_BAD_LENGTH; }           // (a per-sequence count only: the scalar entry refuses it on the host)
+  if (add > maxlen - len || look > maxlen - len - add) { flag |= ATOM_KV_STEP_OVERFLOW; return tab = len; }
+  tab = len + add + look;
   return len + add;
 }
 
+// ROWS: atom_kv_step_rows_i4 (p.adds, p.look); else the scalar step (p.add for every sequence, no look-ahead: tab == the new length)
+template <bool ROWS>
 __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(KvStepParams p) {
   __shared__ int s_part[kStepThreads / 64];
   __shared__ int s_off[kStepRows], s_cnt[kStepRows];
@@ -51,10 +64,15 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(KvStepParams p) {
   const int32_t *cur = p.lens + (int64_t)parity * p.batch;
   int32_t *nxt = p.lens + (int64_t)(parity ^ 1) * p.batch;
   const int row0 = blockIdx.x * kStepRows;
+  const int look = ROWS ? p.look : 0;
+  const auto add_of = [&](int r) { return ROWS ? p.adds[r] : p.add; };
 
   // pages of every sequence in front of this group
-  int acc = 0, flag;
-  for (int r = tid; r < row0; r += kStepThreads) acc += (step_len(cur[r], p.add, p.rows[r], p.cap, p.P, flag) + p.P - 1) / p.P;
+  int acc = 0, flag, tab;
+  for (int r = tid; r < row0; r += kStepThreads) {
+    step_len(cur[r], add_of(r), look, p.rows[r], p.cap, p.P, flag, tab);
+    acc += (tab + p.P - 1) / p.P;
+  }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
   if (lane == 0) s_part[wave] = acc;
@@ -62,11 +80,11 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(KvStepParams p) {
   // the group's own sequences: one lane each, inclusive scan of the page counts over the wave
   const int row = row0 + lane;
   int len = 0, cnt = 0, inc = 0;
-  flag = 0;
+  flag = 0, tab = 0;
   if (wave == 0) {
     if (row < p.batch) {
-      len = step_len(cur[row], p.add, p.rows[row], p.cap, p.P, flag);
-      cnt = (len + p.P - 1) / p.P;
+      len = step_len(cur[row], add_of(row), look, p.rows[row], p.cap, p.P, flag, tab);
+      cnt = (tab + p.P - 1) / p.P;
     }
     inc = cnt;
 #pragma unroll
@@ -82,7 +100,7 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(KvStepParams p) {
 
   if (wave == 0 && blockIdx.y == 0 && row < p.batch) {
     nxt[row] = len;
-    p.lpo[row] = len > 0 ? (len - 1) % p.P + 1 : 0;       // an empty sequence: no page, offset 0 (what the attention ops skip)
+    p.lpo[row] = tab > 0 ? (tab - 1) % p.P + 1 : 0;       // an empty sequence: no page, offset 0 (what the attention ops skip)
     p.indptr[row + 1] = base + inc;
     if (row == 0) p.indptr[0] = 0;
     if (flag) atomicOr(&p.state[0], flag);
@@ -121,6 +139,21 @@ static int step_slices(int batch, int cap) {
   return s;
 }
 
+// the checks both entries share (`adds`: null for the scalar entry), then the launch
+static int kv_step(KvStepParams p, bool rows, hipStream_t stream) {
+  if (!p.table || !p.rows || !p.lens || !p.indptr || !p.indices || !p.lpo || !p.state || (rows && !p.adds)) return ATOM_ERR_INVALID_ARG;
+  if (p.add < 0 || p.look < 0) return ATOM_ERR_INVALID_ARG;
+  if (p.batch < 1 || p.cap < 1 || p.P < 16 || (p.P % 16) != 0) return ATOM_ERR_SHAPE;
+  if ((int64_t)p.cap * p.P > 0x7fffffff || (int64_t)p.batch * p.cap > 0x7fffffff) return ATOM_ERR_SHAPE;
+  for (const void *q : {(const void *)p.table, (const void *)p.rows, (const void *)p.lens, (const void *)p.indptr, (const void *)p.indices,
+                        (const void *)p.lpo, (const void *)p.state, (const void *)p.adds})
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
+  const dim3 grid((unsigned)((p.batch + kStepRows - 1) / kStepRows), (unsigned)step_slices(p.batch, p.cap));
+  if (rows) hipLaunchKernelGGL(kv_step_kernel<true>, grid, dim3(kStepThreads), 0, stream, p);
+  else hipLaunchKernelGGL(kv_step_kernel<false>, grid, dim3(kStepThreads), 0, stream, p);
+  return check_launch();
+}
+
 }  // namespace atom
 
 using namespace atom;
@@ -129,17 +162,15 @@ extern "C" {
 
 int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                     int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, void *stream) {
-  if (!page_table || !row_pages || !lens || !kv_indptr || !kv_indices || !last_page_offset || !state) return ATOM_ERR_INVALID_ARG;
-  if (add < 0) return ATOM_ERR_INVALID_ARG;
-  if (batch < 1 || cap < 1 || page_size < 16 || (page_size % 16) != 0) return ATOM_ERR_SHAPE;
-  if ((int64_t)cap * page_size > 0x7fffffff || (int64_t)batch * cap > 0x7fffffff) return ATOM_ERR_SHAPE;
-  for (const void *q : {(const void *)page_table, (const void *)row_pages, (const void *)lens, (const void *)kv_indptr, (const void *)kv_indices,
-                        (const void *)last_page_offset, (const void *)state})
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
-  KvStepParams p{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add};
-  const dim3 grid((unsigned)((batch + kStepRows - 1) / kStepRows), (unsigned)step_slices(batch, cap));
-  hipLaunchKernelGGL(kv_step_kernel, grid, dim3(kStepThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
-  return check_launch();
+  return kv_step(KvStepParams{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0},
+                 false, reinterpret_cast<hipStream_t>(stream));
+}
+
+int atom_kv_step_rows_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                         int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, const int32_t *adds, int lookahead,
+                         void *stream) {
+  return kv_step(KvStepParams{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, 0, adds, lookahead},
+                 true, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

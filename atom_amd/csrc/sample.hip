@@ -45,6 +45,7 @@ struct SampleParams {
   const int64_t *step;
   int64_t step_offset;
   int64_t *tokens;
+  int rows_per_seq;                             // atom_sample_rows_f16: step is [batch / rows_per_seq]; 0: step is one element
 };
 
 struct SampleShared {
@@ -280,7 +281,9 @@ __global__ __launch_bounds__(kSampleThreads) void sample_kernel(SampleParams p) 
     // up to three trips
     const float top_p = p.top_p ? p.top_p[row_id] : 1.0f;
     const uint64_t seed = p.seeds ? p.seeds[row_id] : 0;
-    const uint64_t step = (uint64_t)((p.step ? *p.step : 0) + p.step_offset);
+    // the draw number: *step, or (atom_sample_rows_f16) the sequence's base + the row's place inside the sequence
+    const int64_t step0 = !p.step ? 0 : (p.rows_per_seq > 0 ? p.step[row_id / p.rows_per_seq] + row_id % p.rows_per_seq : *p.step);
+    const uint64_t step = (uint64_t)(step0 + p.step_offset);
     kept = Prefix{-1, 0u, (uint32_t)vocab, 0};
     if (!top_k_on) {
       uint32_t c = 0;
@@ -381,6 +384,23 @@ static int launch_sample(const SampleParams &p, bool vec, int batch, hipStream_t
   return vec ? launch_sample_as<NQ, NL, true>(p, batch, s) : launch_sample_as<NQ, NL, false>(p, batch, s);
 }
 
+// both entries: rows_per_seq 0 is atom_sample_f16 (step of one element)
+static int sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
+                      const float *top_p, const uint64_t *seeds, const int64_t *step, int rows_per_seq, int64_t step_offset,
+                      int64_t *tokens, void *stream) {
+  if (!logits || !tokens) return ATOM_ERR_INVALID_ARG;
+  if (batch < 1 || batch > 0x7fffffff || vocab < 1 || vocab > sample::kMaxVocab || ld < vocab) return ATOM_ERR_SHAPE;
+  const auto off = [](const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
+  if (off(logits, 1u) || off(temperature, 3u) || off(top_k, 3u) || off(top_p, 3u) || off(seeds, 7u) || off(step, 7u) || off(tokens, 7u))
+    return ATOM_ERR_ALIGN;
+  SampleParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, temperature, top_k, top_p, seeds, step, step_offset, tokens, rows_per_seq};
+  const bool vec = aligned16(logits) && (ld % 8) == 0;         // every row starts on 16 bytes
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (vocab <= 4 * kSampleSlab) return launch_sample<4, 0>(p, vec, (int)batch, s);
+  if (vocab <= (kSampleRegSlabs + kSampleLdsSlabs) * kSampleSlab) return launch_sample<kSampleRegSlabs, kSampleLdsSlabs>(p, vec, (int)batch, s);
+  return launch_sample<0, 0>(p, vec, (int)batch, s);
+}
+
 }  // namespace atom
 
 using namespace atom;
@@ -389,17 +409,15 @@ extern "C" {
 
 int atom_sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
                     const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t step_offset, int64_t *tokens, void *stream) {
-  if (!logits || !tokens) return ATOM_ERR_INVALID_ARG;
-  if (batch < 1 || batch > 0x7fffffff || vocab < 1 || vocab > sample::kMaxVocab || ld < vocab) return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
-  if (off(logits, 1u) || off(temperature, 3u) || off(top_k, 3u) || off(top_p, 3u) || off(seeds, 7u) || off(step, 7u) || off(tokens, 7u))
-    return ATOM_ERR_ALIGN;
-  SampleParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, temperature, top_k, top_p, seeds, step, step_offset, tokens};
-  const bool vec = aligned16(logits) && (ld % 8) == 0;         // every row starts on 16 bytes
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (vocab <= 4 * kSampleSlab) return launch_sample<4, 0>(p, vec, (int)batch, s);
-  if (vocab <= (kSampleRegSlabs + kSampleLdsSlabs) * kSampleSlab) return launch_sample<kSampleRegSlabs, kSampleLdsSlabs>(p, vec, (int)batch, s);
-  return launch_sample<0, 0>(p, vec, (int)batch, s);
+  return sample_f16(logits, ld, batch, vocab, temperature, top_k, top_p, seeds, step, 0, step_offset, tokens, stream);
+}
+
+int atom_sample_rows_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
+                         const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t rows_per_seq, int64_t step_offset,
+                         int64_t *tokens, void *stream) {
+  if (!step) return ATOM_ERR_INVALID_ARG;
+  if (rows_per_seq < 1 || rows_per_seq > 0x7fffffff || (batch >= 1 && batch % rows_per_seq != 0)) return ATOM_ERR_SHAPE;
+  return sample_f16(logits, ld, batch, vocab, temperature, top_k, top_p, seeds, step, (int)rows_per_seq, step_offset, tokens, stream);
 }
 
 }  // extern "C"

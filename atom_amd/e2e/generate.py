@@ -7,6 +7,9 @@ With ``logprobs=`` a step also records the chosen token's log-probability, its r
 launch on the same logits); ``score`` / ``perplexity`` run given sequences through one prefill and one ops.logprob.
 ``beam_search`` / ``BeamDecodeGraph`` are the beam-search form of the same loop: ops.logprob's top-n, ops.beam_select and the device-side
 fork of a ``StaticBeamKvCacheInt4`` inside the replayed step.
+``SpecDecodeGraph`` / ``generate(speculative=)`` spend a step's nearly free rows on speculative decoding: n-gram drafts, one verify forward
+over K + 1 positions per sequence, accept and commit on the device (ops.spec_draft_ngram, ops.spec_accept, ops.kv_step_rows_i4;
+DESIGN.md 4.17).
 """
 from __future__ import annotations
 
@@ -253,10 +256,183 @@ class DecodeGraph:
         return self.tokens
 
 
+@dataclasses.dataclass(frozen=True)
+class SpeculativeParams:
+    """Speculative decoding: every step feeds each sequence its last token and ``num_draft_tokens`` (K, 1 .. 8)
+    guessed ones, scores the K + 1 positions in one forward and keeps the longest prefix of guesses the model agrees with, so a step
+    emits 1 .. K + 1 tokens.  The shipped drafter looks the sequence's last ``ngram_max`` .. ``ngram_min`` tokens (1 .. 8) up in its own
+    history.  ``poll_every``: the loop reads its 4-byte ``done`` word every so many steps -- its only synchronisation."""
+    num_draft_tokens: int = 4
+    ngram_max: int = 3
+    ngram_min: int = 1
+    poll_every: int = 8
+
+    def __post_init__(self):
+        if not 1 <= int(self.num_draft_tokens) <= ops.SPEC_MAX_DRAFT:
+            raise ValueError(f"num_draft_tokens must be 1 .. {ops.SPEC_MAX_DRAFT}, got {self.num_draft_tokens}")
+        if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= ops.SPEC_MAX_NGRAM:
+            raise ValueError(f"n-gram sizes must satisfy 1 <= ngram_min <= ngram_max <= {ops.SPEC_MAX_NGRAM}, "
+                             f"got {self.ngram_min} .. {self.ngram_max}")
+        if int(self.poll_every) < 1:
+            raise ValueError(f"poll_every must be positive, got {self.poll_every}")
+
+
+@dataclasses.dataclass(frozen=True)
+class SpecStats:
+    """What ``generate(..., return_spec_stats=True)`` adds: per sequence the drafts accepted and the steps that emitted a token
+    (tokens = 1 + accepted + steps; the first token comes from the prefill)."""
+    accepted: list
+    steps: list
+
+
+class NgramDrafter:
+    """The shipped drafter: ``ops.spec_draft_ngram`` over the sequence's own history (prompt-lookup decoding).  A drafter is any object
+    with ``propose(hist, hist_len, n_out, out)`` that writes K drafts per row into ``out`` (int64 [batch, K], a strided view of the
+    step's ``input_ids``) with capturable device work only: ``hist`` int32 [batch, hist_cap] / ``hist_len`` int32 [batch] hold the
+    prompt and every emitted token, ``n_out`` int32 [batch] counts the emitted ones."""
+
+    def __init__(self, ngram_max: int = 3, ngram_min: int = 1):
+        self.ngram_max, self.ngram_min = int(ngram_max), int(ngram_min)
+
+    def propose(self, hist, hist_len, n_out, out):
+        ops.spec_draft_ngram(hist, hist_len, out, ngram_max=self.ngram_max, ngram_min=self.ngram_min)
+
+
+class SpecDecodeGraph:
+    """One speculative step over ``static_kv``, run until every sequence holds ``max_new`` tokens (its budget), as ``DecodeGraph`` runs
+    a decode step: the first ``step()`` eager, the second captured, the rest replays.  With Q = K + 1 a step is
+      1. ``static_kv.step_rows(adds, lookahead=Q)``: the tokens the last step accepted are committed, Q tentative slots follow them;
+      2. ``drafter.propose``: K drafts into columns 1 .. K of ``input_ids`` (column 0 is the last emitted token);
+      3. the model's forward over the ``batch * Q`` rows as Q-token prefill requests on the static cache (the verify forward);
+      4. ``argmax`` per row, or with ``sampler`` ``ops.sample(..., step=draw, rows_per_seq=Q)``: row j of a sequence takes draw number
+         ``n_out + j``, the draw non-speculative sampling takes for that token, so accepting is comparing;
+      5. ``ops.spec_accept``: the agreed prefix and the model's own next token go to ``tokens`` and ``hist``, every counter moves.
+    Static buffers: ``input_ids`` int64 [batch, Q], ``tokens`` int64 [batch, max_new], ``hist`` int32 [batch, hist_cap] / ``hist_len``,
+    ``n_out`` / ``budget`` / ``adds`` int32 [batch], ``draw`` int64 [batch], ``accepted`` / ``steps`` int32 [batch], ``done`` int32 [1].
+    ``start`` fills them from the prompts and the first token; ``step()`` never synchronises; ``run()`` replays until ``done``.
+    The cache must hold ``max_new + K`` reserved tokens per sequence (see ``generate``).  ``sampler``: a ``Sampler`` (or
+    ``SamplingParams``) of ``batch`` rows; its four buffers are expanded Q-fold ONCE here, so a later ``sampler.set`` is not followed."""
+
+    def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_new: int, *, params: SpeculativeParams = SpeculativeParams(),
+                 drafter=None, sampler=None):
+        assert max_new >= 2
+        self.model, self.kv, self.max_new, self.params = model, static_kv, int(max_new), params
+        device = static_kv.data.device
+        self.batch = batch = static_kv.last_page_offset.numel()
+        self.K = K = int(params.num_draft_tokens)
+        self.Q = Q = K + 1
+        self.max_steps = self.max_new - 1                      # every step emits a token for every unfinished row: the all-rejected bound
+        self.drafter = NgramDrafter(params.ngram_max, params.ngram_min) if drafter is None else drafter
+        self.hist_cap = max(static_kv.seqlens) + self.max_new   # the longest prompt (the cache's lengths at construction) + every new token
+        i32 = dict(dtype=torch.int32, device=device)
+        self.input_ids = torch.zeros((batch, Q), dtype=torch.int64, device=device)
+        self.tokens = torch.zeros((batch, self.max_new), dtype=torch.int64, device=device)
+        self.hist = torch.zeros((batch, self.hist_cap), **i32)
+        self.hist_len, self.n_out, self.budget, self.adds = (torch.zeros(batch, **i32) for _ in range(4))
+        self.accepted, self.steps = torch.zeros(batch, **i32), torch.zeros(batch, **i32)
+        self.draw = torch.zeros(batch, dtype=torch.int64, device=device)
+        self.done = torch.zeros(1, **i32)
+        self._targets = torch.zeros(batch * Q, dtype=torch.int64, device=device)
+        self._blen = BatchLenInfo([Q] * batch, 0, device)
+        self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
+        assert self.sampler is None or self.sampler.batch == batch
+        self._sample_rows = None
+        if self.sampler is not None:
+            s = self.sampler
+            self._sample_rows = tuple(t.repeat_interleave(Q) for t in (s.temperature, s.top_k, s.top_p, s.seeds))
+        self._graph = None
+        self.steps_done = 0
+
+    def start(self, prompts: Sequence[Sequence[int]], first_tokens: torch.Tensor, budget: Sequence[int] = None):
+        """The state after the prefill: ``hist`` = each prompt and its first new token (draw 0), one token emitted.  ``budget``: new
+        tokens per sequence, the first included (default ``max_new`` each; at most that)."""
+        assert len(prompts) == self.batch and max(len(p) for p in prompts) + self.max_new <= self.hist_cap
+        budget = [self.max_new] * self.batch if budget is None else [int(x) for x in budget]
+        assert len(budget) == self.batch and all(1 <= x <= self.max_new for x in budget)
+        device = self.hist.device
+        first = first_tokens.reshape(self.batch).to(torch.int64)
+        rows = torch.zeros((self.batch, self.hist_cap), dtype=torch.int32)
+        for b, p in enumerate(prompts):
+            rows[b, :len(p)] = torch.tensor(list(p), dtype=torch.int32)
+        lens = torch.tensor([len(p) for p in prompts], dtype=torch.int64, device=device)
+        self.hist.copy_(rows)
+        self.hist.scatter_(1, lens.unsqueeze(1), first.to(torch.int32).unsqueeze(1))
+        self.hist_len.copy_((lens + 1).to(torch.int32))
+        self.tokens.zero_()
+        self.tokens[:, 0] = first
+        self.input_ids.zero_()
+        self.input_ids[:, 0] = first
+        self.n_out.fill_(1)
+        self.draw.fill_(1)
+        self.budget.copy_(torch.tensor(budget, dtype=torch.int32))
+        for t in (self.adds, self.accepted, self.steps, self.done):
+            t.zero_()
+
+    @torch.no_grad()
+    def _step(self):
+        Q = self.Q
+        self.kv.step_rows(self.adds, lookahead=Q)
+        self.drafter.propose(self.hist, self.hist_len, self.n_out, self.input_ids[:, 1:])
+        logits, _ = self.model(self.input_ids.view(-1), self._blen, self.kv, None)
+        if self.sampler is None:
+            targets = logits.argmax(dim=-1)
+        else:
+            targets = ops.sample(logits, *self._sample_rows, step=self.draw, rows_per_seq=Q, out=self._targets)
+        ops.spec_accept(targets.view(self.batch, Q), self.input_ids, self.n_out, self.budget, self.tokens, self.hist, self.hist_len,
+                        self.adds, self.draw, self.accepted, self.steps, self.done)
+
+    def step(self):
+        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
+        if self.steps_done >= self.max_steps:
+            raise RuntimeError(f"SpecDecodeGraph: all {self.max_steps} steps are taken")
+        if self.steps_done == 0:
+            self._step()
+        else:
+            if self._graph is None:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
+                    self._step()
+                self._graph = graph
+            self._graph.replay()
+        self.steps_done += 1
+
+    def commit(self):
+        """After the last step: its accepted tokens become part of the sequences (``step_rows`` without look-ahead; the count is
+        zeroed so that a second call commits nothing).  ``static_kv.sync_host()`` / ``close()`` then read prompt + tokens fed back."""
+        self.kv.step_rows(self.adds, lookahead=0)
+        self.adds.zero_()
+
+    def run(self) -> torch.Tensor:
+        """Steps until every sequence has its budget -- the ``done`` word is read every ``params.poll_every`` steps, the only
+        synchronisation -- and at most ``max_new - 1`` of them, then ``commit()``; returns ``tokens`` [batch, max_new] (row b holds
+        ``n_out[b]`` tokens)."""
+        poll = int(self.params.poll_every)
+        while self.steps_done < self.max_steps:
+            self.step()
+            if self.steps_done % poll == 0 and self.steps_done < self.max_steps and int(self.done.item()):
+                break
+        self.commit()
+        return self.tokens
+
+
+def _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams):
+    refused = [name for name, given in (("num_beams", num_beams is not None), ("logprobs", logprobs is not None),
+                                        ("return_logits", bool(return_logits)), ("caches", caches is not None)) if given]
+    if sampling is not None:
+        neutral = SamplingParams()
+        for q in ([sampling] if isinstance(sampling, SamplingParams) else sampling):
+            for field in ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"):
+                if isinstance(q, SamplingParams) and q.penalises and getattr(q, field) != getattr(neutral, field) and field not in refused:
+                    refused.append(field)
+    if refused:
+        raise ValueError(f"generate: speculative does not combine with {', '.join(refused)}")
+
+
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, *, eos_token_id: int = None,
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
-             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None):
+             sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None,
+             speculative: SpeculativeParams = None, drafter=None, return_spec_stats: bool = False):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -277,7 +453,22 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     untempered, untruncated model gives it).  Rows after a prompt's EOS are computed like its tokens: cutting them is the caller's job.
     ``num_beams`` (1 .. 16): beam search instead -- the tokens of ``beam_search``'s best hypothesis per prompt (``length_penalty`` 1), in
     the same shape.  Out of scope with it, refused with ``ValueError``: ``sampling``, ``logprobs``, ``return_logits`` and ``caches``.
-    ``num_beams=None`` is the code above, launch for launch."""
+    ``num_beams=None`` is the code above, launch for launch.
+    ``speculative`` (a ``SpeculativeParams``): prefill and the first token as above (draw 0); the rest comes from a ``SpecDecodeGraph``,
+    1 .. K + 1 tokens per replayed step, drafted by ``drafter`` (default: ``NgramDrafter`` with the parameters' n-gram sizes).  The
+    tokens are those of the verify forward: greedy rows are its argmax, sampled rows the draws non-speculative sampling would take from
+    the same logits.  (A verify row and a one-token step run different kernels, so near-ties of the logits may resolve differently from
+    ``speculative=None``.)  The reserve is ``max_new_tokens + K`` tokens per sequence: a sequence commits at most its prompt and the
+    ``max_new_tokens - 1`` tokens fed back, and every step -- those a finished sequence idles through included -- addresses K + 1
+    tentative slots behind the committed ones, so ``prompt + max_new_tokens - 1 + K + 1`` is the furthest slot and the cache's overflow
+    bit is never set by a correct run.  ``return_spec_stats=True`` appends a ``SpecStats`` (per sequence: drafts accepted, steps).
+    Out of scope with it, refused with ``ValueError``: ``num_beams``, ``logprobs``, ``return_logits``, ``caches`` and the penalty fields
+    of ``SamplingParams`` (their state is defined token by token); stopping at EOS stays a host-side cut.
+    ``speculative=None`` is the code above, launch for launch."""
+    if speculative is not None:
+        _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams)
+    elif drafter is not None or return_spec_stats:
+        raise ValueError("generate: drafter and return_spec_stats need speculative")
     if num_beams is not None:
         refused = [name for name, given in (("sampling", sampling is not None), ("logprobs", logprobs is not None),
                                             ("return_logits", bool(return_logits)), ("caches", caches is not None)) if given]
@@ -308,7 +499,21 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     else:                                                      # nothing is generated yet: the prompt flags alone
         new = sampler.sample(penalties.apply(all_logits[0])).unsqueeze(0)
     lp = None if n_lp is None else [x if x is None else x.unsqueeze(0) for x in ops.logprob(all_logits[0], new[0], n_lp)]
-    if max_new_tokens > 1:
+    stats = None
+    if speculative is not None:
+        rows, stats = new.t().tolist(), SpecStats([0] * len(prompts), [0] * len(prompts))
+        if max_new_tokens > 1:
+            static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens + int(speculative.num_draft_tokens))
+            try:
+                sg = SpecDecodeGraph(model, static, max_new_tokens, params=speculative, drafter=drafter, sampler=sampler)
+                sg.start(prompts, new[0])
+                toks, counts = sg.run().tolist(), sg.n_out.tolist()
+                rows = [row[:n] for row, n in zip(toks, counts)]
+                stats = SpecStats(sg.accepted.tolist(), sg.steps.tolist())
+            finally:
+                static.close()
+        new = None
+    elif max_new_tokens > 1:
         static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
             dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp,
@@ -322,7 +527,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
         finally:
             static.close()
     out = []
-    for row in new.t().tolist():
+    for row in (rows if speculative is not None else new.t().tolist()):
         if eos_token_id is not None and eos_token_id in row:
             row = row[:row.index(eos_token_id) + 1]
         out.append(row)
@@ -332,6 +537,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     res = (out, all_logits) if return_logits else (out,)
     if lp is not None:
         res = res + (TokenLogprobs(*lp),)
+    if return_spec_stats:
+        res = res + (stats,)
     return res if len(res) > 1 else out
 
 

@@ -256,6 +256,8 @@ class LlamaAttention(nn.Module):
     harness); this class attends to the de-quantised projections it has just written to the cache (causal, RoPE at
     positions 0..len-1) -- the values a later decode step reads back.  A prefill request whose cache already holds tokens (chunked
     prefill: its length exceeds the request's) attends to them too, through ops.batch_prefill_i4 (DecodeFusion.prefill_attn).
+    A ``StaticBatchedKvCacheInt4`` as the prefill cache (the verify step of speculative decoding, capturable) always takes that op:
+    its lengths live on the device, so no host-side prefix is looked at.
     Grouped-query attention: ``config.num_key_value_heads`` (default num_attention_heads) K/V heads, query head h reads K/V head
     h // G; k_proj / v_proj are num_key_value_heads * 128 wide, the paged caches hold num_key_value_heads heads."""
 
@@ -314,7 +316,11 @@ class LlamaAttention(nn.Module):
         self._check_cache(prefill_kv)
         self._check_cache(decode_kv)
         prefixes = []
-        if len(blen.prefills) > 0:
+        # a static cache as the prefill cache (the verify step of speculative decoding): its lengths live on the device and its host list
+        # is stale during replay, so there is no host-side prefix to check -- the requests always attend through ops.batch_prefill_i4,
+        # which takes every position from the device tables
+        static_prefill = bool(getattr(prefill_kv, "device_lengths", False))
+        if len(blen.prefills) > 0 and not static_prefill:
             # cached tokens in front of each prefill request's chunk (host-side lengths: no synchronisation)
             assert prefill_kv is not None
             prefixes = [s - n for s, n in zip(prefill_kv.seqlens, blen.prefills)]
@@ -354,7 +360,7 @@ class LlamaAttention(nn.Module):
             ks = k_sz[:blen.doff].view(-1, nkv, 2)
             vs = v_sz[:blen.doff].view(-1, nkv, 2)
             ops.init_kv_i4(prefill_kv, k, v, ks, vs, blen.indptr, self.layer_idx)
-            if self.fusion.prefill_attn or max(prefixes) > 0:
+            if static_prefill or self.fusion.prefill_attn or max(prefixes) > 0:
                 # every prefill request in ONE launch, over its cached prefix and its new tokens (csrc/prefill_i4.hip)
                 q = q_proj[:blen.doff].view(-1, nh, hd)
                 o = ops.batch_prefill_i4(q, blen.indptr, prefill_kv, self.layer_idx, rope_theta=self.rope_theta,

@@ -623,11 +623,8 @@ def quant_append_kv_i4(kv, k_f32: torch.Tensor, v_f32: torch.Tensor, layer_idx: 
     L.check(st, "atom_kv_quant_append_f32")
 
 
-def kv_step_i4(kv, add: int = 1):
-    """NEW (page tables stepped on the device): every sequence of a utils.StaticBatchedKvCacheInt4 gains ``add`` tokens (0: none) and
-    its ``indptr`` / ``indicies`` / ``last_page_offset`` are rebuilt in place from its padded page table (atom_kv_step_i4) -- one
-    launch on the current stream, no host synchronisation, capturable.  A sequence that would outgrow its reserved pages keeps its
-    length and sets the cache's status word (read by ``kv.sync_host()``)."""
+def _kv_step_tables(kv):
+    """the seven device tables of a static cache as atom_kv_step_i4 / atom_kv_step_rows_i4 take them, checked: (tensors, batch, cap)"""
     tensors = (kv.page_table, kv.row_pages, kv.lengths, kv.indptr, kv.indicies, kv.last_page_offset, kv.state)
     for t in tensors:
         if not t.is_cuda:
@@ -636,9 +633,37 @@ def kv_step_i4(kv, add: int = 1):
     batch, cap = kv.page_table.shape
     assert kv.row_pages.numel() == batch and kv.lengths.numel() == 2 * batch and kv.indptr.numel() == batch + 1
     assert kv.indicies.numel() == batch * cap and kv.last_page_offset.numel() == batch and kv.state.numel() == 4
+    return tensors, batch, cap
+
+
+def kv_step_i4(kv, add: int = 1):
+    """NEW (page tables stepped on the device): every sequence of a utils.StaticBatchedKvCacheInt4 gains ``add`` tokens (0: none) and
+    its ``indptr`` / ``indicies`` / ``last_page_offset`` are rebuilt in place from its padded page table (atom_kv_step_i4) -- one
+    launch on the current stream, no host synchronisation, capturable.  A sequence that would outgrow its reserved pages keeps its
+    length and sets the cache's status word (read by ``kv.sync_host()``)."""
+    tensors, batch, cap = _kv_step_tables(kv)
     st = L.lib().atom_kv_step_i4(*(t.data_ptr() for t in tensors), batch, cap, kv.page_size, int(add),
                                   L.current_stream(kv.page_table.device))
     L.check(st, "atom_kv_step_i4")
+
+
+def kv_step_rows_i4(kv, adds: torch.Tensor, lookahead: int = 0):
+    """NEW (speculative decoding): ``kv_step_i4`` with a count per sequence -- ``adds`` int32 [batch] on the device, read by the launch --
+    and ``lookahead`` >= 0 tentative slots (atom_kv_step_rows_i4).  The length a sequence keeps is ``len + adds[b]``; its tables are
+    built for ``lookahead`` tokens more, so a verify step can write and attend to K + 1 tokens of which the next call commits only the
+    accepted ones.  A negative count is taken as 0 and flagged; a sequence whose ``len + adds[b] + lookahead`` outgrows its reserved
+    pages keeps its length and its tables (the cache's status word, read by ``kv.sync_host()``).  One launch, no host synchronisation,
+    capturable."""
+    tensors, batch, cap = _kv_step_tables(kv)
+    if not adds.is_cuda:
+        raise L.AtomHipError("adds must live on the GPU: no CPU fallback")
+    if not (adds.dtype == torch.int32 and adds.shape == (batch,) and adds.is_contiguous()):
+        raise TypeError(f"adds must be a contiguous int32 tensor of [{batch}], got {adds.dtype} {tuple(adds.shape)}")
+    if int(lookahead) < 0:
+        raise ValueError(f"lookahead must be non-negative, got {lookahead}")
+    st = L.lib().atom_kv_step_rows_i4(*(t.data_ptr() for t in tensors), batch, cap, kv.page_size, adds.data_ptr(), int(lookahead),
+                                       L.current_stream(kv.page_table.device))
+    L.check(st, "atom_kv_step_rows_i4")
 
 
 def _qo_heads(num_qo_heads: int, num_kv_heads: int) -> int:
@@ -1014,14 +1039,18 @@ _SAMPLE_PARAMS = (("temperature", torch.float32), ("top_k", torch.int32), ("top_
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor = None, top_k: torch.Tensor = None, top_p: torch.Tensor = None,
-           seeds: torch.Tensor = None, step: torch.Tensor = None, step_offset: int = 0, out: torch.Tensor = None) -> torch.Tensor:
+           seeds: torch.Tensor = None, step: torch.Tensor = None, step_offset: int = 0, out: torch.Tensor = None, *,
+           rows_per_seq: int = None) -> torch.Tensor:
     """NEW: one token per row of ``logits`` (fp16 [batch, vocab], rows ``stride(0) >= vocab`` apart) under temperature, top-k and
     top-p -- ``atom_sample_f16``, the contract of DESIGN.md 4.13: the token is an exact function of the row's bits, its parameters
     and the draw number ``step[0] + step_offset``; it does not depend on the batch or on timing.  The parameters are DEVICE tensors of
     ``[batch]`` that the launch reads (a captured call follows buffers changed in place): ``temperature`` float32 (<= 0: greedy, the
     first index of the maximum), ``top_k`` int32 (outside 1 .. vocab - 1: off), ``top_p`` float32 (>= 1: off), ``seeds`` int64 (the 64
     bits are the Philox key; uint64 is taken too), ``step`` int64 [1].  None: T = 1, off, off, seed 0, step 0.  Returns int64 [batch]
-    (``out`` if given).  One launch; nothing is read back, nothing synchronises."""
+    (``out`` if given).  One launch; nothing is read back, nothing synchronises.
+    ``rows_per_seq`` (the verify rows of speculative decoding, ``atom_sample_rows_f16``): the rows are ``batch / rows_per_seq``
+    sequences of that many consecutive rows, ``step`` is int64 ``[batch / rows_per_seq]`` and row r draws number
+    ``step[r // rows_per_seq] + r % rows_per_seq + step_offset``; the four parameter tensors stay per ROW."""
     if not logits.is_cuda:
         raise L.AtomHipError("logits must live on the GPU: the sampler has no CPU fallback")
     if logits.dtype != torch.float16:
@@ -1038,15 +1067,25 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor = None, top_k: torch.
         ok = t.dtype == dtype or (name == "seeds" and t.dtype == torch.uint64)
         if not (t.is_cuda and ok and t.shape == (batch,) and t.is_contiguous()):
             raise TypeError(f"{name} must be a contiguous {dtype} tensor of [{batch}] on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    if step is not None and not (step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
+    if rows_per_seq is not None:
+        q = int(rows_per_seq)
+        if q < 1 or batch % q:
+            raise ValueError(f"rows_per_seq must be positive and divide the {batch} rows, got {rows_per_seq}")
+        if step is None or not (step.is_cuda and step.dtype == torch.int64 and step.shape == (batch // q,) and step.is_contiguous()):
+            raise TypeError(f"with rows_per_seq={q} step must be a contiguous int64 tensor of [{batch // q}] on the GPU")
+    elif step is not None and not (step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
         raise TypeError("step must be an int64 tensor of one element on the GPU")
     if out is None:
         out = torch.empty(batch, dtype=torch.int64, device=logits.device)
     elif not (out.is_cuda and out.dtype == torch.int64 and out.shape == (batch,) and out.is_contiguous()):
         raise TypeError(f"out must be a contiguous int64 tensor of [{batch}] on the GPU")
-    st = L.lib().atom_sample_f16(logits.data_ptr(), ld, batch, vocab, L.ptr(temperature), L.ptr(top_k), L.ptr(top_p), L.ptr(seeds),
-                                 L.ptr(step), int(step_offset), out.data_ptr(), L.current_stream(logits.device))
-    L.check(st, "atom_sample_f16")
+    params = (logits.data_ptr(), ld, batch, vocab, L.ptr(temperature), L.ptr(top_k), L.ptr(top_p), L.ptr(seeds), L.ptr(step))
+    if rows_per_seq is None:
+        st = L.lib().atom_sample_f16(*params, int(step_offset), out.data_ptr(), L.current_stream(logits.device))
+        L.check(st, "atom_sample_f16")
+    else:
+        st = L.lib().atom_sample_rows_f16(*params, int(rows_per_seq), int(step_offset), out.data_ptr(), L.current_stream(logits.device))
+        L.check(st, "atom_sample_rows_f16")
     return out
 
 
@@ -1235,3 +1274,80 @@ def kv_beam_fork_i4(kv, parent: torch.Tensor):
                                       num_heads, page_size, head_dim, L.current_stream(kv.page_table.device))
     L.check(st, "atom_kv_beam_fork_i4")
     kv.tables.copy_(kv.tables_out)                           # page_table and spare are views of one buffer: one copy
+
+
+# ------------------------------------------------------------------------------------------------ speculative decoding
+SPEC_MAX_DRAFT = 8
+SPEC_MAX_NGRAM = 8
+
+
+def _require_spec(name, t, dtype, shape):
+    if not t.is_cuda:
+        raise L.AtomHipError(f"{name} must live on the GPU: the speculative-decoding ops have no CPU fallback")
+    if not (t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise TypeError(f"{name} must be a contiguous {dtype} tensor of {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def spec_draft_ngram(hist: torch.Tensor, hist_len: torch.Tensor, out: torch.Tensor, *, ngram_max: int = 3, ngram_min: int = 1):
+    """NEW: K draft tokens per sequence by n-gram lookup in the sequence's own history -- ``atom_spec_draft_ngram``, the contract of
+    DESIGN.md 4.17.  ``hist`` int32 [batch, hist_cap] holds the prompt and every emitted token, ``hist_len`` int32 [batch] how many;
+    ``out`` int64 [batch, K] (1 <= K <= 8) receives the drafts and may be a strided view with contiguous rows -- columns 1 .. K of the
+    verify step's ``input_ids``.  The longest of the last ``ngram_max`` .. ``ngram_min`` tokens (1 .. 8) that occurs earlier in the
+    history wins, at its most recent occurrence; the drafts are the tokens that followed it, padded with the last token, which is also
+    every draft when nothing occurs twice.  Returns ``out``.  One launch; nothing is read back, nothing synchronises."""
+    for name, t in (("hist", hist), ("hist_len", hist_len), ("out", out)):
+        if not t.is_cuda:
+            raise L.AtomHipError(f"{name} must live on the GPU: the speculative-decoding ops have no CPU fallback")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.size(0) < 1 or hist.size(1) < 1 or not hist.is_contiguous():
+        raise TypeError(f"hist must be a contiguous int32 tensor of [batch, hist_cap], got {hist.dtype} {tuple(hist.shape)}")
+    batch, hist_cap = hist.shape
+    _require_spec("hist_len", hist_len, torch.int32, (batch,))
+    if out.dtype != torch.int64 or out.dim() != 2 or out.size(0) != batch or (out.size(1) > 1 and out.stride(1) != 1):
+        raise TypeError(f"out must be an int64 tensor of [{batch}, K] with contiguous rows, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    K = out.size(1)
+    if not 1 <= K <= SPEC_MAX_DRAFT:
+        raise ValueError(f"K (out's columns) must be 1 .. {SPEC_MAX_DRAFT}, got {K}")
+    if not 1 <= int(ngram_min) <= int(ngram_max) <= SPEC_MAX_NGRAM:
+        raise ValueError(f"n-gram sizes must satisfy 1 <= ngram_min <= ngram_max <= {SPEC_MAX_NGRAM}, got {ngram_min} .. {ngram_max}")
+    out_ld = _row_stride(out)
+    if out_ld < K:
+        raise ValueError(f"out's rows overlap: row stride {out_ld} for {K} columns")
+    st = L.lib().atom_spec_draft_ngram(hist.data_ptr(), hist_len.data_ptr(), batch, hist_cap, int(ngram_min), int(ngram_max), K,
+                                       out.data_ptr(), out_ld, L.current_stream(hist.device))
+    L.check(st, "atom_spec_draft_ngram")
+    return out
+
+
+def spec_accept(targets: torch.Tensor, input_ids: torch.Tensor, n_out: torch.Tensor, budget: torch.Tensor, tokens: torch.Tensor,
+                hist: torch.Tensor, hist_len: torch.Tensor, adds: torch.Tensor, draw: torch.Tensor, accepted: torch.Tensor,
+                steps: torch.Tensor, done: torch.Tensor):
+    """NEW: the accept / commit step of speculative decoding -- ``atom_spec_accept``, the contract of DESIGN.md 4.17.  ``targets`` int64
+    [batch, K + 1] are the tokens chosen at the verify rows, ``input_ids`` int64 [batch, K + 1] the last emitted token and the K
+    drafts.  Per row the leading drafts that equal their targets are accepted; e = accepted + 1 tokens, cut at ``budget - n_out``
+    (int32 [batch] each), are appended to ``tokens`` int64 [batch, max_new] at ``n_out`` and to ``hist`` int32 [batch, hist_cap] at
+    ``hist_len``; ``n_out`` and ``hist_len`` grow by e, ``adds`` int32 [batch] receives e (for ``kv_step_rows_i4``), ``input_ids[:, 0]``
+    the last emitted token, ``draw`` int64 [batch] the new ``n_out``, ``accepted`` / ``steps`` int32 [batch] count e - 1 and 1, and
+    ``done`` int32 [1] says whether every row has reached its budget.  Everything is updated in place by one launch; nothing is read
+    back, nothing synchronises."""
+    if not targets.is_cuda:
+        raise L.AtomHipError("targets must live on the GPU: the speculative-decoding ops have no CPU fallback")
+    if targets.dtype != torch.int64 or targets.dim() != 2 or targets.size(0) < 1 or not targets.is_contiguous():
+        raise TypeError(f"targets must be a contiguous int64 tensor of [batch, K + 1], got {targets.dtype} {tuple(targets.shape)}")
+    batch, Q = targets.shape
+    if not 1 <= Q - 1 <= SPEC_MAX_DRAFT:
+        raise ValueError(f"K (targets' columns - 1) must be 1 .. {SPEC_MAX_DRAFT}, got {Q - 1}")
+    _require_spec("input_ids", input_ids, torch.int64, (batch, Q))
+    for name, t in (("tokens", tokens), ("hist", hist)):
+        if t.dim() != 2 or t.size(1) < 1:
+            raise TypeError(f"{name} must be [batch, n], got {tuple(t.shape)}")
+    _require_spec("tokens", tokens, torch.int64, (batch, tokens.size(1)))
+    _require_spec("hist", hist, torch.int32, (batch, hist.size(1)))
+    for name, t in (("n_out", n_out), ("budget", budget), ("hist_len", hist_len), ("adds", adds), ("accepted", accepted), ("steps", steps)):
+        _require_spec(name, t, torch.int32, (batch,))
+    _require_spec("draw", draw, torch.int64, (batch,))
+    _require_spec("done", done, torch.int32, (1,))
+    st = L.lib().atom_spec_accept(targets.data_ptr(), input_ids.data_ptr(), n_out.data_ptr(), budget.data_ptr(), tokens.data_ptr(),
+                                  hist.data_ptr(), hist_len.data_ptr(), adds.data_ptr(), draw.data_ptr(), accepted.data_ptr(),
+                                  steps.data_ptr(), done.data_ptr(), batch, Q - 1, tokens.size(1), hist.size(1),
+                                  L.current_stream(targets.device))
+    L.check(st, "atom_spec_accept")

@@ -123,6 +123,8 @@ class StaticBatchedKvCacheInt4:
     the page table, so the attention ops size their KV split by the reserve, not by the current lengths.
     While this object is open the sequences hold spare pages: build no ``BatchedKvCacheInt4`` from them before ``close()``."""
 
+    device_lengths = True      # the lengths live on the device: ``seqlens`` is stale between sync_host() calls (read by LlamaAttention)
+
     def __init__(self, kv: Sequence[KvCacheInt4], reserve: int):
         assert len(kv) > 0
         pool = kv[0].pool
@@ -158,6 +160,13 @@ class StaticBatchedKvCacheInt4:
         """One launch on the current stream: every sequence gains ``add`` tokens (0: rebuild the tables only).  Capturable."""
         from .. import ops
         ops.kv_step_i4(self, add)
+
+    def step_rows(self, adds: torch.Tensor, lookahead: int = 0):
+        """One launch on the current stream (ops.kv_step_rows_i4): sequence b gains ``adds[b]`` tokens (int32 [batch] on the device)
+        and the tables cover ``lookahead`` tentative slots behind that -- the K + 1 tokens a verify step of speculative decoding
+        writes, of which the next ``step_rows`` commits the accepted ones.  ``sync_host()`` reads the committed lengths.  Capturable."""
+        from .. import ops
+        ops.kv_step_rows_i4(self, adds, lookahead)
 
     def sync_host(self):
         """Read the lengths and the status word back (one copy, the only synchronisation) and bring ``seqlens`` and the sequences'

@@ -510,6 +510,19 @@ int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, 
 int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                     int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, void *stream);
 
+/* The same step with a count per sequence and a look-ahead (speculative decoding; the same kernel body):
+ *   adds int32 [batch] on the device: sequence b gains adds[b] tokens; lookahead >= 0.
+ * The COMMITTED length len_b + adds[b] is what `lens` receives; kv_indptr / kv_indices / last_page_offset are built for the committed
+ * length + lookahead.  The `lookahead` slots behind the committed length are tentative: a verify step writes its K + 1 tokens there, the
+ * next launch commits the accepted ones through adds, and the others are overwritten.  Nothing is ever rolled back.
+ * adds[b] < 0 counts as 0 and sets ATOM_KV_STEP_BAD_LENGTH.  If len_b + adds[b] + lookahead exceeds the sequence's reserve, the whole
+ * request is refused as above: the sequence keeps len_b, its tables are those of len_b, and ATOM_KV_STEP_OVERFLOW is set.  With
+ * lookahead 0 and every adds[b] = add the result is atom_kv_step_i4's.  Both entries flip the parity once per launch and may be mixed.
+ * Errors: as atom_kv_step_i4, with ATOM_ERR_INVALID_ARG for a null adds or lookahead < 0 and ATOM_ERR_ALIGN for adds off 4 bytes. */
+int atom_kv_step_rows_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                         int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, const int32_t *adds, int lookahead,
+                         void *stream);
+
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised
  * asymmetrically to n_bits in FP16 opmath -- scale = ((max - min) * clip).clamp(1e-5) / (2^n - 1), base =
@@ -674,6 +687,15 @@ int atom_kv_quant_u4_f16(const void *k, void *packed, void *param, int64_t T, in
 int atom_sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
                     const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t step_offset, int64_t *tokens, void *stream);
 
+/* The same with a draw number per sequence (the verify rows of speculative decoding): the `batch` rows are batch / rows_per_seq
+ * sequences of rows_per_seq consecutive rows, step is int64 [batch / rows_per_seq], and row r draws number
+ * s = step[r / rows_per_seq] + r % rows_per_seq + step_offset.  Everything else -- the per-ROW parameter arrays, the arithmetic, the
+ * kernel -- is atom_sample_f16's.  Errors: as above, with ATOM_ERR_INVALID_ARG for a null step and ATOM_ERR_SHAPE for rows_per_seq < 1
+ * or a batch that is not a multiple of it. */
+int atom_sample_rows_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const float *temperature, const int32_t *top_k,
+                         const float *top_p, const uint64_t *seeds, const int64_t *step, int64_t rows_per_seq, int64_t step_offset,
+                         int64_t *tokens, void *stream);
+
 /*
  * Token log-probabilities: per row of fp16 logits, the log-probability and rank of a target token and the top-n tokens with their
  * log-probabilities -- csrc/logprob.hip, on the sampler's arithmetic (csrc/sample_math.h), the contract in DESIGN.md 4.14.  What it
@@ -808,6 +830,51 @@ int atom_kv_beam_fork_i4(void *kv_data, void *kv_param, const int32_t *table_in,
                          int32_t *spare_out, const int32_t *row_pages, const int32_t *lens, int32_t *state, const int32_t *parent,
                          int batch, int w, int cap, int64_t capacity, int num_layers, int num_heads, int page_size, int head_dim,
                          void *stream);
+
+/*
+ * Speculative decoding, the drafter: K guessed tokens per sequence by n-gram lookup in the sequence's own history (prompt-lookup
+ * decoding) -- csrc/spec.hip, the integer rules in csrc/spec_math.h, DESIGN.md 4.17.
+ *   hist int32 [batch, hist_cap]: the prompt and every emitted token; hist_len int32 [batch]
+ *   1 <= ngram_min <= ngram_max <= 8; 1 <= K <= 8
+ *   out int64, row b at out + b * out_ld (out_ld >= K elements): the drafts land directly in columns 1 .. K of the verify step's
+ *   input_ids [batch, K + 1] (out = input_ids + 1, out_ld = K + 1); nothing else of a row is written.
+ * One row, len = hist_len[b]:
+ *   1. For n = ngram_max down to ngram_min, skipping every n with len <= n:
+ *   2. among the starts s with 0 <= s and s + n <= len - 1 keep those with hist[s .. s+n) == hist[len-n .. len);
+ *   3. take the largest such s (the most recent occurrence); 4. the first n that has one wins.
+ *   5. Draft j (0 .. K - 1) is hist[s + n + j] if s + n + j < len, otherwise hist[len - 1].
+ *   6. With no occurrence at any n, all K drafts are hist[len - 1].
+ * A row with len <= 0 or len > hist_cap gets K drafts of token 0 and nothing of it is read.  No index outside 0 .. len - 1 of the row
+ * is ever read.  One launch of `batch` workgroups, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer; ATOM_ERR_SHAPE for batch < 1, hist_cap < 1 (either
+ * beyond int32), K or the n-gram sizes outside the ranges above, out_ld < K; ATOM_ERR_ALIGN for hist / hist_len off 4 bytes, out off 8.
+ */
+int atom_spec_draft_ngram(const int32_t *hist, const int32_t *hist_len, int64_t batch, int64_t hist_cap, int ngram_min, int ngram_max,
+                          int K, int64_t *out, int64_t out_ld, void *stream);
+
+/*
+ * Speculative decoding, accept and commit: compares the drafts with the tokens chosen at the verify rows, emits the agreed prefix
+ * plus the model's own next token and prepares the next step -- csrc/spec.hip, DESIGN.md 4.17.  Q = K + 1, 1 <= K <= 8.
+ *   targets   int64 [batch, Q]   the token chosen at every verify row (read only)
+ *   input_ids int64 [batch, Q]   column 0 the last emitted token, columns 1 .. K the drafts
+ *   n_out int32 [batch] tokens emitted so far; budget int32 [batch] (read only)
+ *   tokens int64 [batch, max_new]; hist int32 [batch, hist_cap], hist_len int32 [batch]
+ *   adds int32 [batch], draw int64 [batch], accepted int32 [batch], steps int32 [batch], done int32 [1]
+ * Row b: a = the number of leading j < K with input_ids[b][1 + j] == targets[b][j]; e = min(a + 1, max(budget[b] - n_out[b], 0)).
+ *   tokens[b][n_out .. n_out + e) = targets[b][0 .. e), the same e tokens go to hist[b] at hist_len[b]; a position outside
+ *   0 .. max_new - 1 (0 .. hist_cap - 1) is skipped, whatever the buffers hold.
+ *   adds[b] = e (what the next atom_kv_step_rows_i4 commits).  With e > 0: n_out[b] += e, hist_len[b] += e,
+ *   input_ids[b][0] = targets[b][e - 1], draw[b] = the new n_out[b] (the sampler's next draw base), accepted[b] += e - 1, steps[b] += 1.
+ *   With e = 0 (a row at its budget) nothing but adds[b] = 0 is written.
+ *   done[0] = 1 if every row has n_out >= budget after this launch, else 0: computed from all rows inside the launch.
+ * A row's targets and drafts are read before anything of the row is written.  One launch of one workgroup, no workspace, nothing
+ * read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer; ATOM_ERR_SHAPE for batch < 1, K outside 1 .. 8,
+ * max_new < 1, hist_cap < 1 (each beyond int32 too); ATOM_ERR_ALIGN for a pointer off its element size.
+ */
+int atom_spec_accept(const int64_t *targets, int64_t *input_ids, int32_t *n_out, const int32_t *budget, int64_t *tokens, int32_t *hist,
+                     int32_t *hist_len, int32_t *adds, int64_t *draw, int32_t *accepted, int32_t *steps, int32_t *done, int64_t batch,
+                     int K, int64_t max_new, int64_t hist_cap, void *stream);
 
 #ifdef __cplusplus
 }
