@@ -481,9 +481,13 @@ template <bool PAIR, bool INTER = true>
 __device__ __forceinline__ void deq_pair(const v4f_t &a0, const v4f_t &a1, float sa, const float *sb, float (&c0)[4], float (&c1)[4]) {
   if constexpr (PAIR) {
     static_assert(INTER, "shared products need the interleaved rows");
+#ifdef ATOM_F6_SCALE4X4                      // tools, TIMING ONLY (ABFLAGS=-DATOM_F6_SCALE4X4 tools/ab_build.sh): the four products as ONE
+    const v4f_t s = __builtin_amdgcn_mfma_f32_4x4x1f32(sb[0], sa, v4f_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);   // v_mfma_f32_4x4x1_16b_f32 on the two registers at
+#else                                        // hand -- the RESULTS ARE GARBAGE; what it measured: DESIGN.md section 8, profiles/f6q_scale_mfma/probe.txt
     float s[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) s[r] = sa * sb[r];
+#endif
 #pragma unroll
     for (int r = 0; r < 4; ++r) { c0[r] = __builtin_fmaf(a0[r], s[r], c0[r]); asm volatile("" : "+v"(c0[r])); }
 #pragma unroll
@@ -509,6 +513,32 @@ __device__ __forceinline__ void deq_pair(const v4f_t &a0, const v4f_t &a1, float
 #pragma unroll
     for (int r = 0; r < 4; ++r) { c1[r] = __builtin_fmaf(a1[r], s[r], c1[r]); asm volatile("" : "+v"(c1[r])); }
   }
+}
+
+// The scale products of FOUR pair slots of the q kernel's step as ONE v_mfma_f32_16x16x1_4b_f32 instead of 16 v_mul_f32.  That step is
+// bound by vector ISSUE (a v_mul costs 4 issue cycles) and leaves the matrix pipe more than half idle.  The instruction multiplies, in
+// each of 4 blocks, a 16 x 1 column by a 1 x 16 row: lane l supplies A[l % 16] and B[l % 16] of block l / 16 and receives, in register
+// 4 b + r, D[4 (l / 16) + r][l % 16] of block b -- A of lane 16 b + 4 (l / 16) + r times B of lane 16 b + l % 16.  With
+//   B of lane (b, j) = the scale of token j of the token block of slot b, A of lane (b, i) = the scale of channel pair i of the
+//   feature-block pair of slot b (QRegs::sbq, saq)
+// lane l receives sA[token l % 16] * sB[pair 4 (l / 16) + r] for b = 0..3: the four products deq_pair<true> computes, for four slots.
+// (A 4x4x1 MFMA per slot -- 4 results per lane -- was measured first and is no faster than the multiplies: an MFMA of any length costs a
+// wave ~18-24 issue cycles beside the BF6 MFMAs)
+// Bit-identical to the multiplies: both factors are fp16 values held as fp32 (the contract, include/atom_hip.h), so the significand
+// product has at most 22 bits and the exponent is at least 2^-48 -- the product is exact and normal in fp32, and no rounding or flush
+// mode of the MFMA can change it.  With C = 0 the MFMA returns a * b + 0; the one difference from v_mul is a -0 product coming out as
+// +0, and that cannot reach an output: fma(idot, +-0, c) leaves every non-zero c as it is, and (+0) + (-0) = +0.  Inf and NaN scales
+// behave as under v_mul (inf * 0 + 0 is NaN too).
+typedef float v16f_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ v16f_t scale_tile4(float sb_lane, float sa_lane) {
+  return __builtin_amdgcn_mfma_f32_16x16x1f32(sb_lane, sa_lane, v16f_t{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+}
+// deq_pair<true> on block b of a scale tile
+__device__ __forceinline__ void deq_pair_t(const v4f_t &a0, const v4f_t &a1, const v16f_t &t, int b, float (&c0)[4], float (&c1)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { c0[r] = __builtin_fmaf(a0[r], t[4 * b + r], c0[r]); asm volatile("" : "+v"(c0[r])); }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { c1[r] = __builtin_fmaf(a1[r], t[4 * b + r], c1[r]); asm volatile("" : "+v"(c1[r])); }
 }
 
 __device__ __forceinline__ void dequant4x(const v4f_t &acc, float sa, const v2u &sb, float (&c)[4]) {
@@ -1358,18 +1388,19 @@ struct QRegs {
   v8i bf[3];            // token fragments: [2] block 0, [0] blocks 2,4,6, [1] odd blocks
   float sb[2][PAIR ? 4 : 8];   // weight scales of feature-block pair h: [h][2 r + (fb & 1)]; PAIR (channels 2 j, 2 j + 1 share theirs): [h][r]
   QSa sa[4];            // token scales, ring by token block % 4
-  v2f_t sa2[2];         // SA2: the same ring as the pairs one two-address read returns: [0] blocks 0,1 (mod 4), [1] blocks 2,3
+  // SA2 (the headline instantiation): no scale ring -- the products of pair slots 4 q .. 4 q + 3 ("group" q) come from one scale_tile4,
+  // made behind the de-quantisation of slot 4 q - 1 (the old tile's last reader), first read one slot later.  Its operands, one dword each:
+  float sbq[2];         //   the weight scale of pair l % 16 of feature-block pair h: [0] h = (l / 16) % 2 (groups 0-2: slots (tb, 0), (tb, 1),
+                        //   (tb + 1, 0), (tb + 1, 1)), [1] h = l / 32 (group 3: slots (6, 0), (7, 0), (6, 1), (7, 1))
+  float saq;            //   the scale of token l % 16 of token block 2 q + l / 32 (group 3: 6 + (l / 16) % 2) of the NEXT tile
+  v16f_t st;            //   the tile: register 4 b + r = slot 4 q + b, channel pair 4 (l / 16) + r
   v4f_t acc[2][2];
   // lane byte addresses in LDS, [set][piece]: set 0 serves stage slots 0 and 1 (+ instruction offset), set 1 = + 2 stages for
   // slot 2.  All opaque to the compiler: it would otherwise re-derive one from another with a v_add per use, or merge two 8-byte
   // loads of a fragment into a ds_read2_b64 (half the LDS rate).
   int aW[2][3], aA[2][3], aS[2], aB[2];
-  int aS2[3][4];        // SA2: lane address of token row 32 j + 2 (l % 16) in stage slot s, [s][j] (ds_read2 offsets are 8 bits: no
-                        // instruction offset reaches another slot or block pair)
-  __device__ __forceinline__ float tscale(int tb) const {
-    if constexpr (SA2) return sa2[(tb & 3) >> 1][tb & 1];
-    else return sa[tb & 3];
-  }
+  int aSq[2][2], aBq[2][2];   // SA2: lane addresses of saq ([set][0] groups 0-2 (+ 32 q rows), [set][1] group 3) and of sbq ([set][k])
+  __device__ __forceinline__ float tscale(int tb) const { return sa[tb & 3]; }
 #ifdef ATOM_F6_PAIR128                       // tools, TIMING ONLY: lane addresses of a pair-interleaved record (see q_frag_pair)
   int aWp[2][3];
 #endif
@@ -1441,13 +1472,15 @@ __device__ __forceinline__ QSa q_scale(const char *lds, const RG &R, int off, in
   return QSa(*reinterpret_cast<const v2f_t *>(lds + (SL < 0 ? ro : q_imm<C, SL>()) + off + R.aS[q_set<SL>()]));
 #endif
 }
-// SA2: the token scales of blocks 2 j and 2 j + 1 in ONE read.  Their rows 32 j + 2 (l % 16) and that + 1 are adjacent records, so the
-// two fp32 copies sit at dwords 25 and 51 off the same lane address: a two-address dword read (ds_read2_b32), 4 scale reads per K step
-// instead of 8.  Both halves of the result are used, so the pair is one live value until its first use without QSa's help.
+// SA2: scale_tile4's operands (QRegs::saq of group q, QRegs::sbq[k]): one ds_read_b32 each -- 4 token-scale reads and 2 weight-scale
+// reads per K step (the per-block form above: 8 and 4)
 template <class C, int SL, class RG>
-__device__ __forceinline__ v2f_t q_scale2(const char *lds, const RG &R, int j, int ro) {
-  const int a = R.aS2[SL < 0 ? 0 : SL][j] + (SL < 0 ? ro : 0);
-  return v2f_t{q_ld0<float>(a, 100), q_ld0<float>(a, PITCH + 100)};
+__device__ __forceinline__ float q_scale_q(const RG &R, int q, int ro) {
+  return q_ld0<float>(R.aSq[q_set<SL>()][q == 3] + (SL < 0 ? ro : 0), (SL < 0 ? 0 : q_imm<C, SL>()) + (q == 3 ? 96 : 32 * q) * PITCH + 100);
+}
+template <class C, int SL, class RG>
+__device__ __forceinline__ float q_load_sbq(const RG &R, int k, int ro) {
+  return q_ld0<float>(R.aBq[q_set<SL>()][k] + (SL < 0 ? ro : 0), SL < 0 ? 0 : q_imm<C, SL>());   // (SB_OFF is in the lane address: with a stage offset it passes 16 bits)
 }
 template <class C, int SL, class RG>
 __device__ __forceinline__ void q_load_sb(const char *lds, RG &R, int h, int ro) {   // 8 consecutive features of pair h
@@ -1519,10 +1552,10 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
     // ---- loads behind this slot's MFMAs, into registers whose last reader has just issued
     if (h == 1 && i < 12 && tb + 2 < 8) {
       R.bf[p_buf(tb + 2)] = q_frag<C, SL, SA2>(lds, R.aA, p_row(tb + 2) * PITCH, ro);
-      if constexpr (SA2) {                                   // blocks tb + 2, tb + 3 together; the ring pair's last reader (block
-        if ((tb & 1) == 0) R.sa2[((tb + 2) & 3) >> 1] = q_scale2<C, SL>(lds, R, (tb + 2) >> 1, ro);   // tb - 1, de-quantised in slot i - 1) is done
-      } else R.sa[(tb + 2) & 3] = q_scale<C, SL>(lds, R, p_row(tb + 2) * PITCH, ro);
+      if constexpr (!SA2) R.sa[(tb + 2) & 3] = q_scale<C, SL>(lds, R, p_row(tb + 2) * PITCH, ro);
     }
+    // SA2: the token scales of the next tile, two slots ahead of it (the previous tile was issued in slot i - 2)
+    if constexpr (SA2) { if ((i & 3) == 2 && i < 14) R.saq = q_scale_q<C, SL>(R, (i + 2) >> 2, ro); }
     if (!LAST) {
       if (i == 12) {                                         // next step's block 0 (buffer 2: free since slot 1)
         R.bf[2] = q_frag<C, NX, SA2>(lds, R.aA, p_row(0) * PITCH, rn);
@@ -1546,8 +1579,12 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
         R.bf[1] = q_frag<C, NX, SA2>(lds, R.aA, p_row(1) * PITCH, rn);        // next step's block 1
         if constexpr (!SA2) R.sa[1] = q_scale<C, NX>(lds, R, p_row(1) * PITCH, rn);
       }
-      // SA2: the next step's blocks 0 and 1 in slot 14 -- block 5, the last reader of this ring pair, is de-quantised in slot 12
-      if constexpr (SA2) { if (i == 14) R.sa2[0] = q_scale2<C, NX>(lds, R, 0, rn); }
+      // SA2: the next step's group 0 in slot 14; the weight scales of the next stage behind their last tiles of this one (slots 8 and 12)
+      if constexpr (SA2) {
+        if (i == 14) R.saq = q_scale_q<C, NX>(R, 0, rn);
+        if (i == 10) R.sbq[0] = q_load_sbq<C, NX>(R, 0, rn);
+        if (i == 13) R.sbq[1] = q_load_sbq<C, NX>(R, 1, rn);
+      }
     }
     if (i >= 8) mid(i - 8);
     else early(i);
@@ -1557,13 +1594,19 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
     // ---- de-quantisation of the previous slot's pair (slot 15 of the previous step for i == 0)
     {
       const int j = (i + 15) & 15, dtb = p_tb(j), dh = p_h(j);
-      deq_pair<PAIR>(R.acc[j & 1][0], R.acc[j & 1][1], R.tscale(dtb), R.sb[dh], c[2 * dh][dtb], c[2 * dh + 1][dtb]);
+      if constexpr (SA2) deq_pair_t(R.acc[j & 1][0], R.acc[j & 1][1], R.st, j & 3, c[2 * dh][dtb], c[2 * dh + 1][dtb]);
+      else deq_pair<PAIR>(R.acc[j & 1][0], R.acc[j & 1][1], R.tscale(dtb), R.sb[dh], c[2 * dh][dtb], c[2 * dh + 1][dtb]);
     }
-    // weight scales: pair 0's registers die with slot 13's de-quantisation (done in slot 14) and take the next stage's values;
-    // pair 1's die with the carried pair (slot 15, done in the next step's slot 0) and take the current stage's
     __builtin_amdgcn_sched_barrier(0);
-    if (!LAST && i == 14) q_load_sb<C, NX>(lds, R, 0, rn);
-    if (i == 0) q_load_sb<C, SL>(lds, R, 1, ro);
+    if constexpr (SA2) {
+      // the scale tile of slots i .. i + 3: its predecessor's last reader (slot i - 1) has just issued, its first one runs a slot from here
+      if ((i & 3) == 0) { R.st = scale_tile4(R.sbq[i == 12], R.saq); __builtin_amdgcn_sched_barrier(0); }
+    } else {
+      // weight scales: pair 0's registers die with slot 13's de-quantisation (done in slot 14) and take the next stage's values;
+      // pair 1's die with the carried pair (slot 15, done in the next step's slot 0) and take the current stage's
+      if (!LAST && i == 14) q_load_sb<C, NX>(lds, R, 0, rn);
+      if (i == 0) q_load_sb<C, SL>(lds, R, 1, ro);
+    }
   }
   stamp(18);
 }
@@ -1776,7 +1819,7 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
 #ifdef ATOM_Q_NO_SA2                                        // A/B builds (tools/ab_build.sh): the token scales one read each
   constexpr bool SA2 = false;
 #else
-  constexpr bool SA2 = PAIR && GU == 0;                     // the headline instantiation: it has the registers for aS2 (see QRegs)
+  constexpr bool SA2 = PAIR && GU == 0;                     // the headline instantiation: scale products from scale_tile4 (see QRegs)
 #endif
   QRegs<C, PAIR, SA2> R;
   {
@@ -1801,11 +1844,12 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
     }
     if constexpr (SA2) {
 #pragma unroll
-      for (int sl = 0; sl < 3; ++sl)
+      for (int st = 0; st < 2; ++st)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          R.aS2[sl][j] = la + sl * Q::STAGE + p_row(2 * j) * PITCH;
-          asm volatile("" : "+v"(R.aS2[sl][j]));
+        for (int k = 0; k < 2; ++k) {
+          R.aSq[st][k] = la + (k ? (kb & 1) : (kb >> 1)) * PITCH + st * 2 * Q::STAGE;
+          R.aBq[st][k] = Q::SB_OFF + (wn * 64 + 32 * (k ? (kb >> 1) : (kb & 1)) + 2 * l15) * 4 + st * 2 * Q::STAGE;
+          asm volatile("" : "+v"(R.aSq[st][k]), "+v"(R.aBq[st][k]));
         }
     }
     R.bf[2] = q_frag<C, 0, SA2>(lds, R.aA, p_row(0) * PITCH, 0);
@@ -1814,16 +1858,20 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
     R.bf[1] = q_frag<C, 0, SA2>(lds, R.aA, p_row(1) * PITCH, 0);
     R.bf[0] = R.bf[1];
     if constexpr (SA2) {
-      R.sa2[0] = q_scale2<C, 0>(lds, R, 0, 0);
-      R.sa2[1] = v2f_t{0.f, 0.f};                           // the "carried pair" of the first step: zeros x 0
+      R.saq = q_scale_q<C, 0>(R, 0, 0);
+      R.sbq[0] = q_load_sbq<C, 0>(R, 0, 0);
+      R.sbq[1] = q_load_sbq<C, 0>(R, 1, 0);
+      R.st = scale_tile4(R.sbq[1], 0.f);                    // the "carried pair" of the first step (block 3): zeros x 0 x its weight scales
     } else {
       R.sa[0] = q_scale<C, 0>(lds, R, p_row(0) * PITCH, 0);
       R.sa[1] = q_scale<C, 0>(lds, R, p_row(1) * PITCH, 0);
       R.sa[2] = 0.f;
       R.sa[3] = 0.f;                                        // the "carried pair" of the first step: zeros x 0
     }
-    q_load_sb<C, 0>(lds, R, 0, 0);
-    q_load_sb<C, 0>(lds, R, 1, 0);
+    if constexpr (!SA2) {
+      q_load_sb<C, 0>(lds, R, 0, 0);
+      q_load_sb<C, 0>(lds, R, 1, 0);
+    }
 #pragma unroll
     for (int k = 0; k < 2; ++k) R.acc[1][k] = v4f_t{0.f, 0.f, 0.f, 0.f};
   }
@@ -1888,7 +1936,9 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
                   },
                   (s % 3) * Q::STAGE, ((s + 1) % 3) * Q::STAGE, s + 1 == G);
   }
-  deq_pair<PAIR>(R.acc[1][0], R.acc[1][1], R.tscale(7), R.sb[1], c[2][7], c[3][7]);   // the carried pair (slot 15) of the last int4 step
+  // the carried pair (slot 15) of the last int4 step
+  if constexpr (SA2) deq_pair_t(R.acc[1][0], R.acc[1][1], R.st, 3, c[2][7], c[3][7]);
+  else deq_pair<PAIR>(R.acc[1][0], R.acc[1][1], R.tscale(7), R.sb[1], c[2][7], c[3][7]);
   // keeper half 0 was published by the last mid-step barrier; half 1 was issued behind it: ONE step over both once it has landed
   kstamp(4);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -9,7 +9,12 @@ instruction classes per region (static) and along the path a launch with G int4 
 with the per-SIMD costs the project's probes measured (profiles/r06/pk_mfma_probe.txt, profiles/r05/rate_probe.txt,
 profiles/r01_gemm_experiments.txt section 5): everything a wave issues adds up on its SIMD, two waves share a SIMD.
 
-    cycles per SIMD = 2 waves x (16 x MFMA + 4 x VALU + 4 x LDS)
+    cycles per SIMD = 2 waves x (16 x MFMA + 32 x scale MFMA + 4 x VALU + 4 x LDS)
+
+Two classes of matrix instruction: `mfma` is the dot products (BF6 v_mfma_f32_16x16x128_f8f6f4, INT8 v_mfma_i32_16x16x64_i8: 16 cycles),
+`mfma_scale` the scale-product tiles (v_mfma_f32_16x16x1_4b_f32, scale_tile4 in the kernel source: 8 passes = 32 pipe cycles; the
+v_mfma_f32_4x4x1_16b_f32 of the -DATOM_F6_SCALE4X4 probe build counts here too, its 8 pipe cycles priced as 32 as well -- the probe
+measured 18-24 issue cycles for it, profiles/f6q_scale_mfma/probe.txt).
 
 Regions, found from the loop labels and the MFMA counts (the BF6 MFMA marks a K step: 32 per step; the INT8 MFMA the keeper):
     prologue   kernel entry .. header of the main loop: tile setup, prologue LDS-DMA, first fragments, K steps 0-2 (96 MFMA)
@@ -33,8 +38,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "atom_amd", "csrc")
 HEADLINE = "gemm_w4a4_f6q_kernelINS0_3CfgILi256ELi256ELi4ELi3ELi2ELi0EEELi0ELb0ELb1EEE"
-CLASSES = ("mfma", "valu", "lds", "vmem", "salu", "waitcnt", "barrier")
-COST = {"mfma": 16, "valu": 4, "lds": 4}          # cycles per instruction on a SIMD shared by two waves
+CLASSES = ("mfma", "mfma_scale", "valu", "lds", "vmem", "salu", "waitcnt", "barrier")
+COST = {"mfma": 16, "mfma_scale": 32, "valu": 4, "lds": 4}          # cycles per instruction on a SIMD shared by two waves
 WAVES_PER_SIMD = 2
 
 
@@ -104,6 +109,8 @@ def classify(line):
     if not t or t.startswith((";", ".", "//")) or t.endswith(":") or re.match(r"^\.?[A-Za-z_][\w.$]*:", t):
         return None
     op = t.split()[0]
+    if op.startswith(("v_mfma_f32_16x16x1_", "v_mfma_f32_4x4x1_")):
+        return "mfma_scale"
     if op.startswith("v_mfma"):
         return "mfma"
     if op.startswith("v_"):
@@ -238,7 +245,7 @@ def model(asm, G=31, clock_ghz=2.0):
         "kernel": facts["name"], "facts": facts, "spill_or_scratch": check_resources(body, facts),
         "G": G, "clock_ghz": clock_ghz, "static": static, "runs": sched, "dynamic": dyn,
         "region_cycles": cyc, "cycles_per_simd": total, "predicted_us": total / (clock_ghz * 1e3),
-        "per_step": {"mfma": static["loop"]["mfma"] / 3.0, "valu": static["loop"]["valu"] / 3.0, "lds": static["loop"]["lds"] / 3.0,
+        "per_step": {"mfma": static["loop"]["mfma"] / 3.0, "mfma_scale": static["loop"]["mfma_scale"] / 3.0, "valu": static["loop"]["valu"] / 3.0, "lds": static["loop"]["lds"] / 3.0,
                      "cycles": cyc["loop"] / 3.0},
         "loop_waits": sorted((w, sum(1 for l in loop if l.strip() == w)) for w in {l.strip() for l in loop if l.strip().startswith("s_waitcnt")}),
         "valu_per_mfma": dyn["valu"] / dyn["mfma"] if dyn["mfma"] else 0.0,
@@ -254,23 +261,23 @@ def render(r):
         f.get("sgpr_spill_count", -1), f.get("Occupancy", -1), f.get("codeLenInByte", -1)))
     o.append("")
     o.append("static counts per wave")
-    o.append("%-14s %6s %6s %6s %6s %6s %8s %8s %6s %10s" % (("region",) + CLASSES + ("runs", "cycles/run")))
+    o.append("%-14s %6s %10s %6s %6s %6s %6s %8s %8s %6s %10s" % (("region",) + CLASSES + ("runs", "cycles/run")))
     for k in ("prologue", "loop", "tail_ct", "tail_gen", "keeper", "keeper_ragged"):
         if k in r["static"]:
             s = r["static"][k]
             runs = r["runs"].get(k, 0)
-            o.append("%-14s %6d %6d %6d %6d %6d %8d %8d %6g %10d" % ((k,) + tuple(s[c] for c in CLASSES) + (runs, r["region_cycles"][k])))
+            o.append("%-14s %6d %10d %6d %6d %6d %6d %8d %8d %6g %10d" % ((k,) + tuple(s[c] for c in CLASSES) + (runs, r["region_cycles"][k])))
     o.append("(tail_ct holds two K steps; runs counts it in halves.  keeper_ragged is the copy a ragged tile takes.)")
     o.append("")
     p = r["per_step"]
-    o.append("main loop per K step: %.0f MFMA, %.2f VALU (%.3f per MFMA), %.0f LDS, %.0f cycles" % (
-        p["mfma"], p["valu"], p["valu"] / p["mfma"], p["lds"], p["cycles"]))
+    o.append("main loop per K step: %.0f MFMA, %.0f scale MFMA, %.2f VALU (%.3f per MFMA), %.0f LDS, %.0f cycles" % (
+        p["mfma"], p["mfma_scale"], p["valu"], p["valu"] / p["mfma"], p["lds"], p["cycles"]))
     o.append("main loop waits: " + ", ".join("%s x%d" % (w.replace("s_waitcnt ", ""), n) for w, n in r["loop_waits"]))
     o.append("")
     d = r["dynamic"]
-    o.append("dynamic counts per wave at G = %d: %d MFMA, %d VALU (%.2f per MFMA), %d LDS, %d VMEM, %d SALU" % (
-        r["G"], d["mfma"], d["valu"], r["valu_per_mfma"], d["lds"], d["vmem"], d["salu"]))
-    o.append("model: 2 waves x (16 x MFMA + 4 x VALU + 4 x LDS) = %d cycles per SIMD = %.2f us at %.3f GHz" % (
+    o.append("dynamic counts per wave at G = %d: %d MFMA, %d scale MFMA, %d VALU (%.2f per MFMA), %d LDS, %d VMEM, %d SALU" % (
+        r["G"], d["mfma"], d["mfma_scale"], d["valu"], r["valu_per_mfma"], d["lds"], d["vmem"], d["salu"]))
+    o.append("model: 2 waves x (16 x MFMA + 32 x scale MFMA + 4 x VALU + 4 x LDS) = %d cycles per SIMD = %.2f us at %.3f GHz" % (
         r["cycles_per_simd"], r["predicted_us"], r["clock_ghz"]))
     if r["spill_or_scratch"]:
         o.append("FAIL: " + "; ".join(r["spill_or_scratch"]))
