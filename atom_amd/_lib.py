@@ -31,6 +31,8 @@ WS_VERIFY = 0x4000         # ATOM_WS_VERIFY: debug call -- the two assertions ab
 Q_REORDER, Q_RMSNORM, Q_ADD_RMSNORM, Q_SILU_MUL = 1, 2, 3, 4     # atom_gemm_w4a4_multi_q: q_op
 KV_STEP_OVERFLOW, KV_STEP_BAD_LENGTH = 1, 2                      # ATOM_KV_STEP_*: status bits of atom_kv_step_i4
 KV_BEAM_BAD_PARENT, KV_BEAM_BAD_PAGE = 4, 8                      # ATOM_KV_BEAM_*: status bits of atom_kv_beam_fork_i4, same word
+GUIDE_FREE, GUIDE_DEAD = -1, -2                                  # ATOM_GUIDE_*: state values of atom_guide_mask_f16 / atom_guide_advance
+GUIDE_REJECTED, GUIDE_BAD_STATE = 1, 2                           # ... and their status bits
 F6_PITCH = 104
 
 _vp = ctypes.c_void_p
@@ -107,6 +109,8 @@ SIGNATURES = {
     "atom_sample_rows_f16": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64, _i64, _vp, _vp]),
     "atom_spec_draft_ngram": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _i64, _vp]),
     "atom_spec_accept": (_int, [_vp] * 12 + [_i64, _int, _i64, _i64, _vp]),
+    "atom_guide_mask_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "atom_guide_advance": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,128 @@
+// atom_guide_mask_f16 / atom_guide_advance: guided decoding over a token-level automaton (the rules are guide_math.h).
+//
+// Mask: one launch, a grid of (tile, row) workgroups of 256 threads as in penalize.hip; a tile is 2048 elements, thread t owns
+// elements 8 t .. 8 t + 7 of it: one 16-byte load of logits, ONE BYTE of the state's mask row (bits 8 t .. 8 t + 7 of the tile: a
+// wave reads 64 consecutive bytes, 16 mask words), one 16-byte store where the bases and leading dimensions allow; 2-byte accesses
+// otherwise and in a row's tail.  The row's state is one scalar load, the same in every thread of the workgroup, and it is compared
+// with 0 .. num_states - 1 before it scales the mask row's address.  A FREE / DEAD / bad row is copied (in place: nothing to do, the
+// workgroup returns before it loads anything); a bad row's first workgroup sets ATOM_GUIDE_BAD_STATE.
+// No workgroup reads what another writes and none waits: a row of 32,000 tokens is 16 workgroups.
+//
+// Advance: one launch, one thread per sequence: a binary search of tokens[b] in the sorted edge tokens of state[b], the state
+// rewritten in place.  Every index is clamped into its array before it is used (guide_math.h advance).
+#include "common.h"
+#include "guide_math.h"
+
+namespace atom {
+
+namespace gm = guide;
+
+constexpr int kGuideThreads = 256;
+constexpr int kGuideTile = 8 * kGuideThreads;
+constexpr int kGuideMaxBatch = 65535;                          // rows are the grid's y
+constexpr int kGuideAdvThreads = 64;
+
+struct GuideMaskParams {
+  const uint16_t *logits;
+  int64_t ld;
+  int vocab;
+  const int32_t *state;
+  const uint32_t *mask;
+  int64_t mask_ld, num_states;
+  uint16_t *out;
+  int64_t out_ld;
+  int32_t *status;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(kGuideThreads) void guide_mask_kernel(GuideMaskParams p) {
+  const int tid = threadIdx.x, row = blockIdx.y, vocab = p.vocab;
+  const int e0 = blockIdx.x * kGuideTile + tid * 8;
+  const int n = min(8, vocab - e0);                            // <= 0: a thread past the row's end
+  const uint16_t *lrow = p.logits + (int64_t)row * p.ld;
+  uint16_t *orow = p.out + (int64_t)row * p.out_ld;
+  const int32_t s = p.state[row];                              // wave-uniform
+  const int kind = gm::row_kind(s, p.num_states);
+  if (kind == gm::kCopiedBad && blockIdx.x == 0 && tid == 0) atomicOr(p.status, gm::kBadState);
+  if (n <= 0 || (kind != gm::kMasked && orow == lrow)) return;
+
+  uint32_t lg[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) lg[c] = 0;
+  if (VEC && n == 8) {
+    const v4u x = *reinterpret_cast<const v4u *>(lrow + e0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { lg[2 * i] = x[i] & 0xFFFFu; lg[2 * i + 1] = x[i] >> 16; }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < n) lg[c] = lrow[e0 + c];
+  }
+  if (kind == gm::kMasked) {
+    // byte e0 / 8 of the row (little endian: bits e0 .. e0 + 7 of word e0 / 32); e0 < vocab, so the word is below ceil(vocab / 32)
+    const uint32_t byte = reinterpret_cast<const uint8_t *>(p.mask + (int64_t)s * p.mask_ld)[e0 >> 3];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) lg[c] = gm::select(lg[c], gm::allowed(byte, (uint32_t)c));   // bits past n are computed, never stored
+  }
+  if (VEC && n == 8) {
+    v4u x;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = (lg[2 * i] & 0xFFFFu) | (lg[2 * i + 1] << 16);
+    *reinterpret_cast<v4u *>(orow + e0) = x;
+  } else {
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (c < n) orow[e0 + c] = (uint16_t)lg[c];
+  }
+}
+
+__global__ __launch_bounds__(kGuideAdvThreads) void guide_advance_kernel(int32_t *state, const int64_t *tokens, int batch, const int32_t *indptr,
+                                                                          const int32_t *edge_tok, const int32_t *edge_next, int64_t num_states,
+                                                                          int64_t num_edges, int32_t *status) {
+  const int b = blockIdx.x * kGuideAdvThreads + threadIdx.x;
+  if (b >= batch) return;
+  int32_t bits = 0;
+  const int32_t s = state[b];
+  const int32_t s1 = gm::advance(s, tokens[b], indptr, edge_tok, edge_next, num_states, num_edges, bits);
+  if (s1 != s) state[b] = s1;
+  if (bits) atomicOr(status, bits);
+}
+
+}  // namespace atom
+
+using namespace atom;
+
+extern "C" {
+
+int atom_guide_mask_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const int32_t *state, const uint32_t *mask,
+                        int64_t mask_ld, int64_t num_states, void *out, int64_t out_ld, int32_t *status, void *stream) {
+  if (!logits || !state || !mask || !out || !status) return ATOM_ERR_INVALID_ARG;
+  if (batch < 1 || batch > kGuideMaxBatch || vocab < 1 || vocab > guide::kMaxVocab || ld < vocab || out_ld < vocab ||
+      mask_ld < (vocab + 31) / 32 || num_states < 1 || num_states > INT32_MAX || mask_ld > INT32_MAX || num_states * mask_ld > INT32_MAX ||
+      (out == logits && out_ld != ld))
+    return ATOM_ERR_SHAPE;
+  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  if (off(logits, 1u) || off(out, 1u) || off(state, 3u) || off(mask, 3u) || off(status, 3u)) return ATOM_ERR_ALIGN;
+  GuideMaskParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, state, mask, mask_ld, num_states, static_cast<uint16_t *>(out), out_ld, status};
+  // every row of both buffers starts on 16 bytes (the mask is read by the byte: it needs no more than its element's alignment)
+  const bool vec = aligned16(logits) && (ld % 8) == 0 && aligned16(out) && (out_ld % 8) == 0;
+  const dim3 grid((unsigned)((vocab + kGuideTile - 1) / kGuideTile), (unsigned)batch);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (vec) hipLaunchKernelGGL((guide_mask_kernel<true>), grid, dim3(kGuideThreads), 0, s, p);
+  else hipLaunchKernelGGL((guide_mask_kernel<false>), grid, dim3(kGuideThreads), 0, s, p);
+  return check_launch();
+}
+
+int atom_guide_advance(int32_t *state, const int64_t *tokens, int64_t batch, const int32_t *indptr, const int32_t *edge_tok,
+                       const int32_t *edge_next, int64_t num_states, int64_t num_edges, int32_t *status, void *stream) {
+  if (!state || !tokens || !indptr || !status || (num_edges > 0 && (!edge_tok || !edge_next))) return ATOM_ERR_INVALID_ARG;
+  if (batch < 1 || batch > kGuideMaxBatch || num_states < 1 || num_states >= INT32_MAX || num_edges < 0 || num_edges > INT32_MAX) return ATOM_ERR_SHAPE;
+  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  if (off(state, 3u) || off(tokens, 7u) || off(indptr, 3u) || off(edge_tok, 3u) || off(edge_next, 3u) || off(status, 3u)) return ATOM_ERR_ALIGN;
+  const unsigned blocks = (unsigned)((batch + kGuideAdvThreads - 1) / kGuideAdvThreads);
+  hipLaunchKernelGGL(guide_advance_kernel, dim3(blocks), dim3(kGuideAdvThreads), 0, reinterpret_cast<hipStream_t>(stream), state, tokens,
+                     (int)batch, indptr, edge_tok, edge_next, num_states, num_edges, status);
+  return check_launch();
+}
+
+}  // extern "C"

@@ -4,5 +4,6 @@ from .llama import (LinearInt4, LlamaAttention, LlamaDecoderLayer, LlamaForCausa
                     LlamaRMSNorm, LlamaRMSNormInt4)
 from .generate import BeamDecodeGraph, BeamHypothesis, DecodeGraph, LogitPenalties, Sampler, SamplingParams, TokenLogprobs, backtrack_beams, beam_search, generate, perplexity, score  # noqa: F401
 from .generate import NgramDrafter, SpecDecodeGraph, SpecStats, SpeculativeParams  # noqa: F401
+from .guide import LogitGuide, TokenAutomaton  # noqa: F401
 from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4  # noqa: F401
 from .llama_lora import LlamaDecoderLayerWithLora, LlamaForCausalLMWithLora, LlamaModelWithLora  # noqa: F401

@@ -10,6 +10,8 @@ fork of a ``StaticBeamKvCacheInt4`` inside the replayed step.
 ``SpecDecodeGraph`` / ``generate(speculative=)`` spend a step's nearly free rows on speculative decoding: n-gram drafts, one verify forward
 over K + 1 positions per sequence, accept and commit on the device (ops.spec_draft_ngram, ops.spec_accept, ops.kv_step_rows_i4;
 DESIGN.md 4.17).
+``DecodeGraph(guide=)`` / ``generate(guide=)`` restrict every sequence's next token to what a token automaton (``e2e/guide.py``) allows in
+the state its own output has led to: ops.guide_advance and ops.guide_mask, two more launches of the replayed step.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ import torch
 
 from .. import ops
 from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, StaticBatchedKvCacheInt4, StaticBeamKvCacheInt4
+from .guide import LogitGuide, TokenAutomaton
 
 
 @dataclasses.dataclass(frozen=True)
@@ -178,10 +181,15 @@ class DecodeGraph:
 
     ``penalties`` (a ``LogitPenalties``; needs a sampler): None is the step above, launch for launch.  Otherwise the step counts the
     tokens of ``input_ids`` in ``penalties.state`` and penalises the logits into the static buffer ``penalised`` (ops.penalize, one
-    more launch), and ops.sample draws from that.  ``logits`` and the log-probabilities stay those of the raw logits."""
+    more launch), and ops.sample draws from that.  ``logits`` and the log-probabilities stay those of the raw logits.
+
+    ``guide`` (a ``LogitGuide``): None is the step above, launch for launch.  Otherwise the step first advances every sequence's
+    automaton state over ``input_ids`` (ops.guide_advance), and after the forward -- and the penalties, if any -- masks the row with the
+    state's allowed set (ops.guide_mask) into the static buffer ``guided``, or in place into ``penalised``; ops.sample or the argmax
+    reads the masked row.  ``logits`` and the log-probabilities stay those of the raw logits here too."""
 
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None,
-                 logprobs: int = None, penalties: LogitPenalties = None):
+                 logprobs: int = None, penalties: LogitPenalties = None, guide: LogitGuide = None):
         assert max_steps >= 1
         self.model, self.kv, self.max_steps = model, static_kv, int(max_steps)
         device = static_kv.data.device
@@ -200,6 +208,11 @@ class DecodeGraph:
                 raise ValueError("DecodeGraph: penalties need a sampler (temperature = 0 is greedy over the penalised row)")
             assert penalties.batch == batch and penalties.vocab == model.config.vocab_size
             self.penalised = torch.zeros((batch, penalties.state.size(1)), dtype=torch.float16, device=device)[:, :penalties.vocab]
+        self.guide, self.guided = guide, None
+        if guide is not None:
+            assert guide.batch == batch and guide.vocab == model.config.vocab_size
+            if penalties is None:
+                self.guided = torch.zeros((batch, -(-guide.vocab // 8) * 8), dtype=torch.float16, device=device)[:, :guide.vocab]
         self.logprobs = n = _check_logprobs(logprobs)
         self.token_logprobs = self.token_ranks = self.top_ids = self.top_logprobs = None
         if n is not None:
@@ -213,15 +226,19 @@ class DecodeGraph:
 
     @torch.no_grad()
     def _step(self):
+        if self.guide is not None:                         # the token fed in moves every sequence's automaton: one launch
+            self.guide.advance(self.input_ids)
         self.kv.step()
         logits, _ = self.model(self.input_ids, self._blen, None, self.kv)
+        row = logits
+        if self.penalties is not None:                     # the token fed in is counted, then the row is penalised: one launch
+            row = self.penalties.apply(logits, fed=self.input_ids, out=self.penalised)
+        if self.guide is not None:                         # what the state does not allow becomes -inf: one launch
+            row = self.guide.mask(row, out=self.guided if self.penalties is None else self.penalised)
         if self.sampler is None:
-            nxt = logits.argmax(dim=-1)
-        elif self.penalties is None:
-            nxt = self.sampler.sample(logits, step=self._counter, step_offset=1)
-        else:                                              # the token fed in is counted, then the row is penalised: one launch
-            pen = self.penalties.apply(logits, fed=self.input_ids, out=self.penalised)
-            nxt = self.sampler.sample(pen, step=self._counter, step_offset=1)
+            nxt = row.argmax(dim=-1)
+        else:
+            nxt = self.sampler.sample(row, step=self._counter, step_offset=1)
         self.tokens.index_copy_(0, self._counter, nxt.unsqueeze(0))
         if self.logprobs is not None:
             got = ops.logprob(logits, nxt, self.logprobs)
@@ -432,7 +449,8 @@ def _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beam
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool: KvPoolInt4, *, eos_token_id: int = None,
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
              sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None,
-             speculative: SpeculativeParams = None, drafter=None, return_spec_stats: bool = False):
+             speculative: SpeculativeParams = None, drafter=None, return_spec_stats: bool = False,
+             guide: Union[TokenAutomaton, Sequence[TokenAutomaton]] = None):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -464,7 +482,18 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     bit is never set by a correct run.  ``return_spec_stats=True`` appends a ``SpecStats`` (per sequence: drafts accepted, steps).
     Out of scope with it, refused with ``ValueError``: ``num_beams``, ``logprobs``, ``return_logits``, ``caches`` and the penalty fields
     of ``SamplingParams`` (their state is defined token by token); stopping at EOS stays a host-side cut.
-    ``speculative=None`` is the code above, launch for launch."""
+    ``speculative=None`` is the code above, launch for launch.
+    ``guide`` (one ``TokenAutomaton`` for every prompt, or a list with one automaton or None per prompt): guided decoding -- every new
+    token of a guided prompt is one its automaton allows in the state its earlier new tokens led to (the prompt is not walked).  The
+    first token is drawn from the prefill's last rows masked at the start states; the graph's first step then advances over it
+    (ops.guide_advance, ops.guide_mask: two launches per step, nothing on the host).  Automata built by ``from_sequences`` /
+    ``from_regex`` end in a state that allows only EOS, so after its EOS a guided row emits EOS until the cut.  The status word is read
+    once after the loop: a state outside the tables, or a token without an edge (neither occurs in a correct run), raises
+    ``RuntimeError``.  Combines with ``caches``, ``sampling`` (penalties first, then the mask), ``logprobs`` and ``return_logits`` (both
+    keep describing the raw logits); ``num_beams`` (beam rows change parents) and ``speculative`` (every verify row would need a state
+    of its own) are refused with ``ValueError``.  ``guide=None`` is the code above, launch for launch, with nothing allocated."""
+    if guide is not None and (num_beams is not None or speculative is not None):
+        raise ValueError(f"generate: guide does not combine with {'num_beams' if num_beams is not None else 'speculative'}")
     if speculative is not None:
         _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams)
     elif drafter is not None or return_spec_stats:
@@ -492,7 +521,14 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     if sampler is not None and any(q.penalises for q in ([sampling] if isinstance(sampling, SamplingParams) else sampling)):
         penalties = LogitPenalties(len(prompts), logits.size(-1), device, sampling)
         penalties.reset(prompts)
-    if sampler is None:
+    guides = None
+    if guide is not None and (isinstance(guide, TokenAutomaton) or any(g is not None for g in guide)):
+        guides = LogitGuide(len(prompts), logits.size(-1), device, guide)
+    if guides is not None:                                     # the start states' allowed sets, after the penalties
+        row = all_logits[0] if penalties is None else penalties.apply(all_logits[0])
+        row = guides.mask(row, out=None if penalties is None else row)
+        new = (row.argmax(dim=-1) if sampler is None else sampler.sample(row)).unsqueeze(0)
+    elif sampler is None:
         new = all_logits.argmax(dim=-1)                        # [1, batch]
     elif penalties is None:
         new = sampler.sample(all_logits[0]).unsqueeze(0)
@@ -517,7 +553,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
         static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
             dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp,
-                             penalties=penalties)
+                             penalties=penalties, guide=guides)
             new = torch.cat([new, dg.run(new[0])])
             if lp is not None:
                 rest = (dg.token_logprobs, dg.token_ranks, dg.top_ids, dg.top_logprobs)
@@ -526,6 +562,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
                 all_logits = torch.cat([all_logits, dg.logits])
         finally:
             static.close()
+    bits = 0 if guides is None else guides.status_bits()       # the one read of the guide's status word
     out = []
     for row in (rows if speculative is not None else new.t().tolist()):
         if eos_token_id is not None and eos_token_id in row:
@@ -534,6 +571,10 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     if caches is None:
         for c in seqs:
             c.release()
+    if bits:
+        raise RuntimeError("generate: the guide's status word is " + " | ".join(
+            name for name, bit in (("REJECTED", ops.GUIDE_REJECTED), ("BAD_STATE", ops.GUIDE_BAD_STATE)) if bits & bit)
+            + ": a token without an edge was emitted, or a state left the tables")
     res = (out, all_logits) if return_logits else (out,)
     if lp is not None:
         res = res + (TokenLogprobs(*lp),)

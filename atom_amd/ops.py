@@ -1351,3 +1351,83 @@ def spec_accept(targets: torch.Tensor, input_ids: torch.Tensor, n_out: torch.Ten
                                   steps.data_ptr(), done.data_ptr(), batch, Q - 1, tokens.size(1), hist.size(1),
                                   L.current_stream(targets.device))
     L.check(st, "atom_spec_accept")
+
+
+# ------------------------------------------------------------------------------------------------ guided decoding
+GUIDE_FREE, GUIDE_DEAD = L.GUIDE_FREE, L.GUIDE_DEAD
+GUIDE_REJECTED, GUIDE_BAD_STATE = L.GUIDE_REJECTED, L.GUIDE_BAD_STATE
+GUIDE_TILE = 2048              # elements per workgroup of atom_guide_mask_f16 (csrc/guide.hip kGuideTile)
+
+
+def _require_guide(name, t, dtype, shape=None):
+    if not t.is_cuda:
+        raise L.AtomHipError(f"{name} must live on the GPU: the guide ops have no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise TypeError(f"{name} must be a contiguous {dtype} tensor{'' if shape is None else ' of ' + str(list(shape))}, "
+                        f"got {t.dtype} {tuple(t.shape)}")
+
+
+def guide_mask(logits: torch.Tensor, state: torch.Tensor, mask: torch.Tensor, out: torch.Tensor = None,
+               status: torch.Tensor = None) -> torch.Tensor:
+    """NEW: the allowed set of every row's automaton state applied to ``logits`` (fp16 [batch, vocab], rows ``stride(0) >= vocab``
+    apart) -- ``atom_guide_mask_f16``, the contract of DESIGN.md 4.18.  ``state`` int32 [batch]: a row of ``mask``, ``GUIDE_FREE`` or
+    ``GUIDE_DEAD``; ``mask`` int32 [num_states, >= ceil(vocab / 32)] with contiguous rows, read as 32-bit words: token v is allowed in
+    state s iff bit ``v & 31`` of ``mask[s, v >> 5]`` is set.  An allowed element keeps its bits, every other becomes -inf; a FREE or
+    DEAD row is copied; any other state outside 0 .. num_states - 1 copies the row and sets ``GUIDE_BAD_STATE`` in ``status`` (int32
+    [1]; None: a word of its own that nobody reads).  All DEVICE tensors that the launch reads (a captured call follows buffers
+    changed in place).  Returns fp16 [batch, vocab] (``out`` if given; ``out`` may be ``logits``).  One launch; nothing is read back,
+    nothing synchronises."""
+    if not logits.is_cuda:
+        raise L.AtomHipError("logits must live on the GPU: the guide ops have no CPU fallback")
+    if logits.dtype != torch.float16:
+        raise TypeError(f"logits must be float16, got {logits.dtype}")
+    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
+    batch, vocab = logits.shape
+    _require_guide("state", state, torch.int32, (batch,))
+    if not (mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2 and mask.size(0) >= 1 and 32 * mask.size(1) >= vocab
+            and (mask.size(1) == 1 or mask.stride(1) == 1)):
+        raise TypeError(f"mask must be an int32 tensor of [num_states, >= {-(-vocab // 32)}] with contiguous rows on the GPU")
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    _require_guide("status", status, torch.int32, (1,))
+    if out is None:
+        out = torch.empty((batch, vocab), dtype=torch.float16, device=logits.device)
+    elif not (out.is_cuda and out.dtype == torch.float16 and out.shape == (batch, vocab) and (vocab == 1 or out.stride(1) == 1)):
+        raise TypeError(f"out must be a float16 tensor of [{batch}, {vocab}] with contiguous rows on the GPU")
+    st = L.lib().atom_guide_mask_f16(logits.data_ptr(), _row_stride(logits), batch, vocab, state.data_ptr(), mask.data_ptr(),
+                                     _row_stride(mask), mask.size(0), out.data_ptr(), _row_stride(out), status.data_ptr(),
+                                     L.current_stream(logits.device))
+    L.check(st, "atom_guide_mask_f16")
+    return out
+
+
+def guide_advance(state: torch.Tensor, tokens: torch.Tensor, indptr: torch.Tensor, edge_tok: torch.Tensor, edge_next: torch.Tensor,
+                  status: torch.Tensor = None) -> torch.Tensor:
+    """NEW: one step of every sequence's automaton -- ``atom_guide_advance``, the contract of DESIGN.md 4.18.  ``state`` int32 [batch]
+    is updated in place over ``tokens`` int64 [batch] (compared as int64); the edges are CSR: ``indptr`` int32 [num_states + 1],
+    ``edge_tok`` int32 [num_edges] ascending inside a state's range, ``edge_next`` int32 [num_edges].  FREE and DEAD stay; a token
+    without an edge makes the state ``GUIDE_DEAD`` and sets ``GUIDE_REJECTED`` in ``status`` (int32 [1]; None: a word of its own that
+    nobody reads); a state or a target outside 0 .. num_states - 1 makes it DEAD and sets ``GUIDE_BAD_STATE``.  All DEVICE tensors.
+    Returns ``state``.  One launch; nothing is read back, nothing synchronises."""
+    if not state.is_cuda:
+        raise L.AtomHipError("state must live on the GPU: the guide ops have no CPU fallback")
+    if state.dim() != 1 or state.numel() < 1:
+        raise ValueError(f"state must be [batch], got {tuple(state.shape)}")
+    batch = state.numel()
+    _require_guide("state", state, torch.int32, (batch,))
+    _require_guide("tokens", tokens, torch.int64, (batch,))
+    if indptr.dim() != 1 or indptr.numel() < 2 or edge_tok.dim() != 1:
+        raise ValueError(f"indptr must be [num_states + 1] and edge_tok [num_edges], got {tuple(indptr.shape)}, {tuple(edge_tok.shape)}")
+    _require_guide("indptr", indptr, torch.int32)
+    _require_guide("edge_tok", edge_tok, torch.int32)
+    _require_guide("edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=state.device)
+    _require_guide("status", status, torch.int32, (1,))
+    num_edges = edge_tok.numel()
+    st = L.lib().atom_guide_advance(state.data_ptr(), tokens.data_ptr(), batch, indptr.data_ptr(),
+                                    edge_tok.data_ptr() if num_edges else None, edge_next.data_ptr() if num_edges else None,
+                                    indptr.numel() - 1, num_edges, status.data_ptr(), L.current_stream(state.device))
+    L.check(st, "atom_guide_advance")
+    return state

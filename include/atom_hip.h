@@ -876,6 +876,62 @@ int atom_spec_accept(const int64_t *targets, int64_t *input_ids, int32_t *n_out,
                      int32_t *hist_len, int32_t *adds, int64_t *draw, int32_t *accepted, int32_t *steps, int32_t *done, int64_t batch,
                      int K, int64_t max_new, int64_t hist_cap, void *stream);
 
+/*
+ * Guided decoding: which tokens a sequence may emit next, as a function of what it has emitted -- a deterministic automaton over token
+ * ids, its allowed sets applied to the logits and its states stepped on the device -- csrc/guide.hip, rules in csrc/guide_math.h, the
+ * contract in DESIGN.md 4.18.  No reference counterpart.  The masked row feeds atom_sample_f16 (which never draws -inf) or an argmax.
+ * The automaton has num_states states; several automata serve one batch stacked into one table, a state being a global index.
+ *   edges, CSR: indptr int32 [num_states + 1]; edge_tok int32 [num_edges], strictly ascending inside indptr[s] .. indptr[s + 1];
+ *   edge_next int32 [num_edges], the state the edge leads to.
+ *   mask uint32 [num_states, mask_ld], mask_ld >= ceil(vocab / 32): token v is allowed in state s iff
+ *   (mask[s * mask_ld + (v >> 5)] >> (v & 31)) & 1.  The caller derives it from the edges.
+ *   state int32 [batch]: a state, ATOM_GUIDE_FREE (unconstrained) or ATOM_GUIDE_DEAD (the sequence left its language: unconstrained
+ *   from then on).  status int32 [1]: the launches only ever set bits in it.
+ *   All DEVICE arrays, read by the launch: a captured launch follows buffers that are changed in place.
+ */
+#define ATOM_GUIDE_FREE (-1)
+#define ATOM_GUIDE_DEAD (-2)
+#define ATOM_GUIDE_REJECTED 1
+#define ATOM_GUIDE_BAD_STATE 2
+/*
+ * The mask.  logits fp16 [batch, vocab], row stride ld >= vocab; out fp16 [batch, vocab], row stride out_ld >= vocab.  out may equal
+ * logits (in place, then out_ld == ld); otherwise the two must not overlap.  Row b, s = state[b]:
+ *   1. 0 <= s < num_states: out[b, v] is logits[b, v] bit for bit (NaN payloads, -0) where v is allowed in s, 0xFC00 (-inf) elsewhere.
+ *   2. s == ATOM_GUIDE_FREE or ATOM_GUIDE_DEAD: the row is copied bit for bit.
+ *   3. Any other s: the row is copied and ATOM_GUIDE_BAD_STATE is set.  s is compared before it is ever used as an index.
+ *   4. Columns vocab .. out_ld - 1 are never written; mask bits at positions >= vocab and mask words >= ceil(vocab / 32) of a row are
+ *      never looked at.
+ *   5. The result is a function of the row, its state and its mask row alone, whatever the grid and the batch.
+ * One launch, a grid of (2048-element tile, row) workgroups, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer; ATOM_ERR_SHAPE for batch < 1, batch > 65535, vocab < 1,
+ * vocab > 262144, ld / out_ld / 32 * mask_ld < vocab, num_states < 1, num_states * mask_ld beyond int32, or out == logits with
+ * out_ld != ld; ATOM_ERR_ALIGN for a pointer off its element size (2 bytes for logits / out, 4 for state / mask / status).  When logits
+ * and out are 16-byte aligned with leading dimensions that are multiples of 8, they are accessed 16 bytes at a time; the mask is read by
+ * the byte (the eight bits of a thread's eight elements) and needs no more than its element's alignment.
+ */
+int atom_guide_mask_f16(const void *logits, int64_t ld, int64_t batch, int64_t vocab, const int32_t *state, const uint32_t *mask,
+                        int64_t mask_ld, int64_t num_states, void *out, int64_t out_ld, int32_t *status, void *stream);
+
+/*
+ * The step.  tokens int64 [batch]: the token every sequence has just emitted.  Sequence b, s = state[b], t = tokens[b] (compared as
+ * int64: 2^32 + 5 does not match edge token 5):
+ *   1. s == ATOM_GUIDE_FREE stays FREE, s == ATOM_GUIDE_DEAD stays DEAD.
+ *   2. 0 <= s < num_states: lo = indptr[s], hi = indptr[s + 1], both clamped into 0 .. num_edges, hi raised to lo if below it; t is
+ *      looked up in edge_tok[lo .. hi) by binary search.
+ *        found at e, 0 <= edge_next[e] < num_states:   state[b] = edge_next[e]
+ *        found at e, edge_next[e] outside that range:  state[b] = ATOM_GUIDE_DEAD, ATOM_GUIDE_BAD_STATE is set
+ *        not found (an empty range included):          state[b] = ATOM_GUIDE_DEAD, ATOM_GUIDE_REJECTED is set
+ *   3. Any other s: state[b] = ATOM_GUIDE_DEAD, ATOM_GUIDE_BAD_STATE is set.
+ * One thread per sequence, state updated in place.  No index outside its checked range is dereferenced: a bad table or token is a
+ * status bit, never a fault.  (Edge tokens that are not ascending make the search miss edges; they cannot make it leave the range.)
+ * One launch, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer (edge_tok / edge_next may be null when num_edges == 0);
+ * ATOM_ERR_SHAPE for batch < 1, batch > 65535, num_states < 1, num_edges < 0, either beyond int32; ATOM_ERR_ALIGN for a pointer off
+ * its element size (8 bytes for tokens, 4 for the others).
+ */
+int atom_guide_advance(int32_t *state, const int64_t *tokens, int64_t batch, const int32_t *indptr, const int32_t *edge_tok,
+                       const int32_t *edge_next, int64_t num_states, int64_t num_edges, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
