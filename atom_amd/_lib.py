@@ -111,6 +111,7 @@ SIGNATURES = {
     "atom_spec_accept": (_int, [_vp] * 12 + [_i64, _int, _i64, _i64, _vp]),
     "atom_guide_mask_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "atom_guide_advance": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "atom_guide_walk_rows": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp]),
 }
 
 _lib = None

@@ -10,6 +10,10 @@
 //
 // Advance: one launch, one thread per sequence: a binary search of tokens[b] in the sorted edge tokens of state[b], the state
 // rewritten in place.  Every index is clamped into its array before it is used (guide_math.h advance).
+//
+// Walk rows (atom_guide_walk_rows): one launch, one thread per sequence as the advance: the commit of the last
+// speculative step (one element of the thread's own row states), then Q chained searches over the step's input row, the row states
+// and the forced drafts written with plain stores.  guide_math.h walk.
 #include "common.h"
 #include "guide_math.h"
 
@@ -88,6 +92,24 @@ __global__ __launch_bounds__(kGuideAdvThreads) void guide_advance_kernel(int32_t
   if (bits) atomicOr(status, bits);
 }
 
+// one thread per sequence: the commit of the last step, then the walk over this step's rows.  Everything a thread reads or writes is
+// its own sequence's: state[b], adds[b], row_state[b][.], input_ids[b][.]; the tables are read-only.
+__global__ __launch_bounds__(kGuideAdvThreads) void guide_walk_rows_kernel(int32_t *state, const int32_t *adds, int32_t *row_state,
+                                                                            int64_t *input_ids, int64_t ids_ld, int batch, int rows,
+                                                                            const int32_t *indptr, const int32_t *edge_tok,
+                                                                            const int32_t *edge_next, int64_t num_states, int64_t num_edges,
+                                                                            int32_t force, int32_t *status) {
+  const int b = blockIdx.x * kGuideAdvThreads + threadIdx.x;
+  if (b >= batch) return;
+  int32_t bits = 0;
+  const int32_t s = state[b];
+  int32_t *row = row_state + (int64_t)b * rows;
+  int64_t *ids = input_ids ? input_ids + (int64_t)b * ids_ld : nullptr;
+  const int32_t s1 = gm::walk(s, adds[b], row, ids, row, rows, indptr, edge_tok, edge_next, num_states, num_edges, force != 0, bits);
+  if (s1 != s) state[b] = s1;
+  if (bits) atomicOr(status, bits);
+}
+
 }  // namespace atom
 
 using namespace atom;
@@ -122,6 +144,23 @@ int atom_guide_advance(int32_t *state, const int64_t *tokens, int64_t batch, con
   const unsigned blocks = (unsigned)((batch + kGuideAdvThreads - 1) / kGuideAdvThreads);
   hipLaunchKernelGGL(guide_advance_kernel, dim3(blocks), dim3(kGuideAdvThreads), 0, reinterpret_cast<hipStream_t>(stream), state, tokens,
                      (int)batch, indptr, edge_tok, edge_next, num_states, num_edges, status);
+  return check_launch();
+}
+
+int atom_guide_walk_rows(int32_t *state, const int32_t *adds, int32_t *row_state, int64_t *input_ids, int64_t ids_ld, int64_t batch,
+                         int64_t rows, const int32_t *indptr, const int32_t *edge_tok, const int32_t *edge_next, int64_t num_states,
+                         int64_t num_edges, int32_t force, int32_t *status, void *stream) {
+  if (!state || !adds || !row_state || !indptr || !status || (num_edges > 0 && (!edge_tok || !edge_next))) return ATOM_ERR_INVALID_ARG;
+  if (batch < 1 || batch > kGuideMaxBatch || rows < 1 || rows > guide::kMaxWalkRows || ids_ld < rows || num_states < 1 ||
+      num_states >= INT32_MAX || num_edges < 0 || num_edges > INT32_MAX)
+    return ATOM_ERR_SHAPE;
+  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
+  if (off(state, 3u) || off(adds, 3u) || off(row_state, 3u) || off(input_ids, 7u) || off(indptr, 3u) || off(edge_tok, 3u) ||
+      off(edge_next, 3u) || off(status, 3u))
+    return ATOM_ERR_ALIGN;
+  const unsigned blocks = (unsigned)((batch + kGuideAdvThreads - 1) / kGuideAdvThreads);
+  hipLaunchKernelGGL(guide_walk_rows_kernel, dim3(blocks), dim3(kGuideAdvThreads), 0, reinterpret_cast<hipStream_t>(stream), state, adds,
+                     row_state, input_ids, ids_ld, (int)batch, (int)rows, indptr, edge_tok, edge_next, num_states, num_edges, force, status);
   return check_launch();
 }
 

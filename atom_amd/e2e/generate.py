@@ -12,6 +12,8 @@ over K + 1 positions per sequence, accept and commit on the device (ops.spec_dra
 DESIGN.md 4.17).
 ``DecodeGraph(guide=)`` / ``generate(guide=)`` restrict every sequence's next token to what a token automaton (``e2e/guide.py``) allows in
 the state its own output has led to: ops.guide_advance and ops.guide_mask, two more launches of the replayed step.
+``SpecDecodeGraph(guide=)`` / ``generate(guide=, speculative=SpeculativeParams(guided=True))`` do both at once: ops.guide_walk_rows gives
+every verify row a state of its own and writes the drafts a state forces, ops.guide_mask masks the batch * (K + 1) rows.
 """
 from __future__ import annotations
 
@@ -278,11 +280,15 @@ class SpeculativeParams:
     """Speculative decoding: every step feeds each sequence its last token and ``num_draft_tokens`` (K, 1 .. 8)
     guessed ones, scores the K + 1 positions in one forward and keeps the longest prefix of guesses the model agrees with, so a step
     emits 1 .. K + 1 tokens.  The shipped drafter looks the sequence's last ``ngram_max`` .. ``ngram_min`` tokens (1 .. 8) up in its own
-    history.  ``poll_every``: the loop reads its 4-byte ``done`` word every so many steps -- its only synchronisation."""
+    history.  ``poll_every``: the loop reads its 4-byte ``done`` word every so many steps -- its only synchronisation.
+    ``guided=True`` lets ``generate`` take ``speculative`` together with ``guide`` (DESIGN.md 4.19; without a guide it changes nothing);
+    ``force_drafts`` then overwrites a draft that follows an automaton state with a single allowed token by that token."""
     num_draft_tokens: int = 4
     ngram_max: int = 3
     ngram_min: int = 1
     poll_every: int = 8
+    guided: bool = False
+    force_drafts: bool = True
 
     def __post_init__(self):
         if not 1 <= int(self.num_draft_tokens) <= ops.SPEC_MAX_DRAFT:
@@ -328,10 +334,15 @@ class SpecDecodeGraph:
     ``n_out`` / ``budget`` / ``adds`` int32 [batch], ``draw`` int64 [batch], ``accepted`` / ``steps`` int32 [batch], ``done`` int32 [1].
     ``start`` fills them from the prompts and the first token; ``step()`` never synchronises; ``run()`` replays until ``done``.
     The cache must hold ``max_new + K`` reserved tokens per sequence (see ``generate``).  ``sampler``: a ``Sampler`` (or
-    ``SamplingParams``) of ``batch`` rows; its four buffers are expanded Q-fold ONCE here, so a later ``sampler.set`` is not followed."""
+    ``SamplingParams``) of ``batch`` rows; its four buffers are expanded Q-fold ONCE here, so a later ``sampler.set`` is not followed.
+    ``guide`` (a ``LogitGuide`` whose ``state`` holds the states BEFORE the first tokens): None is the step above,
+    launch for launch, with nothing allocated.  Otherwise ``guide.walk_rows`` runs between 2 and 3 -- the last step's ``adds`` committed
+    into ``guide.state``, the automaton state behind every row, and with ``params.force_drafts`` the drafts a state forces written over
+    the drafter's -- and ``guide.mask_rows`` between 3 and 4 masks the ``batch * Q`` rows, each with its own state, into the static
+    buffer ``guided``, which the argmax or ops.sample reads; ``commit()`` also commits the last step's states."""
 
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_new: int, *, params: SpeculativeParams = SpeculativeParams(),
-                 drafter=None, sampler=None):
+                 drafter=None, sampler=None, guide: LogitGuide = None):
         assert max_new >= 2
         self.model, self.kv, self.max_new, self.params = model, static_kv, int(max_new), params
         device = static_kv.data.device
@@ -357,6 +368,11 @@ class SpecDecodeGraph:
         if self.sampler is not None:
             s = self.sampler
             self._sample_rows = tuple(t.repeat_interleave(Q) for t in (s.temperature, s.top_k, s.top_p, s.seeds))
+        self.guide, self.guided = guide, None
+        if guide is not None:
+            assert guide.batch == batch and guide.vocab == model.config.vocab_size
+            guide.rows(Q)
+            self.guided = torch.zeros((batch * Q, -(-guide.vocab // 8) * 8), dtype=torch.float16, device=device)[:, :guide.vocab]
         self._graph = None
         self.steps_done = 0
 
@@ -390,7 +406,11 @@ class SpecDecodeGraph:
         Q = self.Q
         self.kv.step_rows(self.adds, lookahead=Q)
         self.drafter.propose(self.hist, self.hist_len, self.n_out, self.input_ids[:, 1:])
+        if self.guide is not None:                         # last step's commit, every row's state, the forced drafts: one launch
+            self.guide.walk_rows(self.adds, self.input_ids, force=bool(self.params.force_drafts))
         logits, _ = self.model(self.input_ids.view(-1), self._blen, self.kv, None)
+        if self.guide is not None:                         # every row masked with its own state: one launch
+            logits = self.guide.mask_rows(logits, out=self.guided)
         if self.sampler is None:
             targets = logits.argmax(dim=-1)
         else:
@@ -417,6 +437,8 @@ class SpecDecodeGraph:
         """After the last step: its accepted tokens become part of the sequences (``step_rows`` without look-ahead; the count is
         zeroed so that a second call commits nothing).  ``static_kv.sync_host()`` / ``close()`` then read prompt + tokens fed back."""
         self.kv.step_rows(self.adds, lookahead=0)
+        if self.guide is not None:                         # the last step's accepted tokens move the committed automaton states
+            self.guide.walk_rows(self.adds, None)
         self.adds.zero_()
 
     def run(self) -> torch.Tensor:
@@ -490,10 +512,14 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     ``from_regex`` end in a state that allows only EOS, so after its EOS a guided row emits EOS until the cut.  The status word is read
     once after the loop: a state outside the tables, or a token without an edge (neither occurs in a correct run), raises
     ``RuntimeError``.  Combines with ``caches``, ``sampling`` (penalties first, then the mask), ``logprobs`` and ``return_logits`` (both
-    keep describing the raw logits); ``num_beams`` (beam rows change parents) and ``speculative`` (every verify row would need a state
-    of its own) are refused with ``ValueError``.  ``guide=None`` is the code above, launch for launch, with nothing allocated."""
-    if guide is not None and (num_beams is not None or speculative is not None):
-        raise ValueError(f"generate: guide does not combine with {'num_beams' if num_beams is not None else 'speculative'}")
+    keep describing the raw logits); ``num_beams`` (beam rows change parents) is refused with ``ValueError``, and so is ``speculative``
+    unless it is ``SpeculativeParams(guided=True)``: then every verify row is masked with a state of its own (ops.guide_walk_rows, and
+    ops.guide_mask over the ``batch * (K + 1)`` rows: two launches per step), a draft that follows a state with a
+    single allowed token is replaced by that token (``force_drafts``), and what ``speculative`` refuses stays refused.
+    ``guide=None`` is the code above, launch for launch, with nothing allocated."""
+    if guide is not None and (num_beams is not None or (speculative is not None and not speculative.guided)):
+        raise ValueError("generate: guide does not combine with " + (
+            "num_beams" if num_beams is not None else "speculative unless it is SpeculativeParams(guided=True)"))
     if speculative is not None:
         _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams)
     elif drafter is not None or return_spec_stats:
@@ -541,7 +567,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
         if max_new_tokens > 1:
             static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens + int(speculative.num_draft_tokens))
             try:
-                sg = SpecDecodeGraph(model, static, max_new_tokens, params=speculative, drafter=drafter, sampler=sampler)
+                sg = SpecDecodeGraph(model, static, max_new_tokens, params=speculative, drafter=drafter, sampler=sampler,
+                                     guide=guides)
                 sg.start(prompts, new[0])
                 toks, counts = sg.run().tolist(), sg.n_out.tolist()
                 rows = [row[:n] for row, n in zip(toks, counts)]

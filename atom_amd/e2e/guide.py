@@ -1,7 +1,8 @@
 """Guided decoding: ``TokenAutomaton`` -- a deterministic automaton over token ids, built from explicit edges, from a list of token
 sequences (a "choice") or from a regular expression over the tokens' strings -- and ``LogitGuide``, the automata of a batch stacked
 into device tables at fixed addresses with one state per sequence, masked and stepped by ops.guide_mask / ops.guide_advance inside the
-replayed decode step.  Building an automaton is host work done once, offline; nothing here reads a token back from
+replayed decode step, and by ops.guide_walk_rows with one state per verify row inside the replayed speculative step
+(DESIGN.md 4.19).  Building an automaton is host work done once, offline; nothing here reads a token back from
 the device while generating."""
 from __future__ import annotations
 
@@ -512,6 +513,7 @@ class LogitGuide:
         self.start = to(np.array(starts, dtype=np.int32))
         self.state = self.start.clone()
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self.row_state = None                                  # int32 [batch, Q] once rows(Q) is called: the verify rows' states
 
     def reset(self):
         """every sequence back to its start state (FREE for None), the status word cleared; device copies, nothing synchronises"""
@@ -525,6 +527,32 @@ class LogitGuide:
     def advance(self, tokens: torch.Tensor) -> torch.Tensor:
         """every sequence's state stepped over ``tokens`` int64 [batch], in place (ops.guide_advance, one launch)"""
         return ops.guide_advance(self.state, tokens, self.indptr, self.edge_tok, self.edge_next, status=self.status)
+
+    def rows(self, Q: int) -> torch.Tensor:
+        """``row_state`` int32 [batch, Q]: one state per verify row of a speculative step, allocated once at a fixed
+        address; a later call must ask for the same Q"""
+        Q = int(Q)
+        if not 1 <= Q <= ops.GUIDE_MAX_ROWS:
+            raise ValueError(f"guide: rows per sequence must be 1 .. {ops.GUIDE_MAX_ROWS}, got {Q}")
+        if self.row_state is None:
+            self.row_state = torch.zeros((self.batch, Q), dtype=torch.int32, device=self.state.device)
+        if self.row_state.size(1) != Q:
+            raise ValueError(f"guide: row states were allocated for {self.row_state.size(1)} rows per sequence, not {Q}")
+        return self.row_state
+
+    def walk_rows(self, adds: torch.Tensor, input_ids: torch.Tensor, force: bool = True) -> torch.Tensor:
+        """the last step's ``adds`` committed into ``state``, then ``row_state`` walked over ``input_ids`` int64 [batch, Q] with forced
+        drafts written into it (ops.guide_walk_rows, one launch); ``input_ids=None``: the commit alone.  Needs ``rows(Q)`` first."""
+        if self.row_state is None:
+            raise RuntimeError("guide: walk_rows needs rows(Q) first")
+        return ops.guide_walk_rows(self.state, adds, self.row_state, input_ids, self.indptr, self.edge_tok, self.edge_next, force=force,
+                                   status=self.status)
+
+    def mask_rows(self, logits: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """``logits`` fp16 [batch * Q, vocab], every row masked with its own ``row_state`` (ops.guide_mask over all rows, one launch)"""
+        if self.row_state is None:
+            raise RuntimeError("guide: mask_rows needs rows(Q) first")
+        return ops.guide_mask(logits, self.row_state.view(-1), self.mask_bits, out=out, status=self.status)
 
     def status_bits(self) -> int:
         """the status word (``ops.GUIDE_REJECTED`` | ``ops.GUIDE_BAD_STATE``): the one call here that synchronises"""

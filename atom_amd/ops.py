@@ -1431,3 +1431,47 @@ def guide_advance(state: torch.Tensor, tokens: torch.Tensor, indptr: torch.Tenso
                                     indptr.numel() - 1, num_edges, status.data_ptr(), L.current_stream(state.device))
     L.check(st, "atom_guide_advance")
     return state
+
+
+GUIDE_MAX_ROWS = 9             # the verify rows per sequence atom_guide_walk_rows takes (guide_math.h kMaxWalkRows)
+
+
+def guide_walk_rows(state: torch.Tensor, adds: torch.Tensor, row_state: torch.Tensor, input_ids: torch.Tensor, indptr: torch.Tensor,
+                    edge_tok: torch.Tensor, edge_next: torch.Tensor, *, force: bool = True, status: torch.Tensor = None) -> torch.Tensor:
+    """NEW: the automaton state behind every verify row of a speculative step -- ``atom_guide_walk_rows``, the contract of DESIGN.md
+    4.19.  ``state`` int32 [batch]: the committed state (the one before ``input_ids[:, 0]``), updated in place by the commit of the
+    last step: ``adds`` int32 [batch] rows of it were committed (``ops.spec_accept``'s ``adds``), ``row_state`` int32 [batch, Q] held
+    its row states and receives this step's: ``row_state[b, j]`` is the state row j's logits are masked with.  ``input_ids`` int64
+    [batch, Q] with contiguous rows (a view of a wider buffer is fine): column 0 the last emitted token, the rest the drafts; with
+    ``force`` a draft that follows a state with a single edge is overwritten by that edge's token.  A draft without an edge makes the
+    rows from it on ``GUIDE_DEAD`` and sets no bit; ``GUIDE_REJECTED`` is set by the commit alone.  ``input_ids=None``: the commit
+    alone.  The tables as ``guide_advance``.  All DEVICE tensors.  Returns ``row_state``.  One launch; nothing is read back."""
+    if not state.is_cuda:
+        raise L.AtomHipError("state must live on the GPU: the guide ops have no CPU fallback")
+    if state.dim() != 1 or state.numel() < 1 or row_state.dim() != 2 or not 1 <= row_state.size(1) <= GUIDE_MAX_ROWS:
+        raise ValueError(f"state must be [batch] and row_state [batch, 1 .. {GUIDE_MAX_ROWS}], got {tuple(state.shape)}, {tuple(row_state.shape)}")
+    batch, Q = state.numel(), row_state.size(1)
+    _require_guide("state", state, torch.int32, (batch,))
+    _require_guide("adds", adds, torch.int32, (batch,))
+    _require_guide("row_state", row_state, torch.int32, (batch, Q))
+    ids_ld = Q
+    if input_ids is not None:
+        if not (input_ids.is_cuda and input_ids.dtype == torch.int64 and tuple(input_ids.shape) == (batch, Q)
+                and (Q == 1 or input_ids.stride(1) == 1) and (batch == 1 or input_ids.stride(0) >= Q)):
+            raise TypeError(f"input_ids must be an int64 tensor of [{batch}, {Q}] with contiguous rows on the GPU")
+        ids_ld = _row_stride(input_ids)
+    if indptr.dim() != 1 or indptr.numel() < 2 or edge_tok.dim() != 1:
+        raise ValueError(f"indptr must be [num_states + 1] and edge_tok [num_edges], got {tuple(indptr.shape)}, {tuple(edge_tok.shape)}")
+    _require_guide("indptr", indptr, torch.int32)
+    _require_guide("edge_tok", edge_tok, torch.int32)
+    _require_guide("edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=state.device)
+    _require_guide("status", status, torch.int32, (1,))
+    num_edges = edge_tok.numel()
+    st = L.lib().atom_guide_walk_rows(state.data_ptr(), adds.data_ptr(), row_state.data_ptr(),
+                                      None if input_ids is None else input_ids.data_ptr(), ids_ld, batch, Q, indptr.data_ptr(),
+                                      edge_tok.data_ptr() if num_edges else None, edge_next.data_ptr() if num_edges else None,
+                                      indptr.numel() - 1, num_edges, 1 if force else 0, status.data_ptr(), L.current_stream(state.device))
+    L.check(st, "atom_guide_walk_rows")
+    return row_state

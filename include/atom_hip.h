@@ -932,6 +932,37 @@ int atom_guide_mask_f16(const void *logits, int64_t ld, int64_t batch, int64_t v
 int atom_guide_advance(int32_t *state, const int64_t *tokens, int64_t batch, const int32_t *indptr, const int32_t *edge_tok,
                        const int32_t *edge_next, int64_t num_states, int64_t num_edges, int32_t *status, void *stream);
 
+/*
+ * The verify rows of a guided speculative step: the automaton state behind each of a sequence's rows = Q = K + 1 input
+ * tokens, the commit of the step before folded in, and drafts that a state forces written over what the drafter proposed.
+ *   state int32 [batch]: the committed state, the one BEFORE input_ids[b][0].  adds int32 [batch]: the rows the last step committed
+ *   (atom_spec_accept's adds; 0 before the first step).  row_state int32 [batch, rows], contiguous: on entry the last step's row
+ *   states, on return this step's.  input_ids int64 [batch, rows], row stride ids_ld >= rows: column 0 the last emitted token, columns
+ *   1 .. rows - 1 the drafts.  force: 0 leaves every draft as it is.
+ * Sequence b, a = adds[b]:
+ *   1. Commit.  s = row_state[b][a - 1] if 1 <= a <= rows; s = state[b] if a == 0; any other a: s = state[b] and
+ *      ATOM_GUIDE_BAD_STATE is set.  If state[b] != ATOM_GUIDE_DEAD and s == ATOM_GUIDE_DEAD, ATOM_GUIDE_REJECTED is set: a token
+ *      without an edge has been emitted.  This is the only place the entry sets that bit.  state[b] = s (written only if it differs).
+ *   2. Walk.  r = s; for j = 0 .. rows - 1:
+ *        a. if force, j >= 1, 0 <= r < num_states and the range indptr[r] .. indptr[r + 1] (clamped as atom_guide_advance clamps it)
+ *           holds exactly one edge e: input_ids[b][j] = edge_tok[e].  No other element of input_ids is written.
+ *        b. r = the state atom_guide_advance gives for (r, input_ids[b][j]), except that a token without an edge gives
+ *           ATOM_GUIDE_DEAD and sets NO bit: a wrong draft is not an error, its rows are discarded by atom_spec_accept.  FREE and DEAD
+ *           stay; a state or an edge target outside the table gives DEAD and ATOM_GUIDE_BAD_STATE.
+ *        c. row_state[b][j] = r: row j's logits predict the token after input_ids[b][j], so r is the state atom_guide_mask_f16 masks
+ *           that row with (its state argument is row_state, one state per row of the batch * rows logit rows).
+ *   3. input_ids == NULL is the commit alone (after the last step): rule 1 runs, row_state is left as it is.
+ * One thread per sequence; a thread reads and writes its own sequence's elements only, and reads row_state[b][a - 1] before it writes
+ * the row, so folding the commit of step n into the walk of step n + 1 needs no second buffer.  No index outside its checked range is
+ * dereferenced.  One launch, no workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer (input_ids may be null; edge_tok / edge_next may be null
+ * when num_edges == 0); ATOM_ERR_SHAPE for batch < 1, batch > 65535, rows < 1, rows > 9, ids_ld < rows, num_states < 1,
+ * num_edges < 0, either beyond int32; ATOM_ERR_ALIGN for a pointer off its element size (8 bytes for input_ids, 4 for the others).
+ */
+int atom_guide_walk_rows(int32_t *state, const int32_t *adds, int32_t *row_state, int64_t *input_ids, int64_t ids_ld, int64_t batch,
+                         int64_t rows, const int32_t *indptr, const int32_t *edge_tok, const int32_t *edge_next, int64_t num_states,
+                         int64_t num_edges, int32_t force, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
