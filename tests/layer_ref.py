@@ -20,6 +20,10 @@ HIP ops -- and recomputes EVERY stage from the trace's own output of the stage b
 compound), compares with the stage's bound and returns the failures.  ``forward(..., wrong=name)`` applies one deliberate wiring
 error; tests/test_layer_ref_cpu.py shows that ``check`` reports each of them, on the inputs the GPU tests use.
 
+Both come in two halves that the other decoder layers reuse (tests/variant_ref.py: Mixtral, LoRA): the attention half, norm1 ..
+residual1 and norm2 (``attention_half``, ``check_attention_half``), and the dense-MLP half, gate .. out (``mlp_half``,
+``check_mlp_half``); ``model_forward`` / ``check_model`` take the layer-level pair as a parameter.
+
 Trace formats.  A quantiser stage is the oracle's dict: q4 int8 [T, K - 128], q8 int8 [T, 128], s4 fp16 [T, G], s8 fp16 [T].  ``k`` /
 ``v``: dict(codes uint8 [T, kv_heads * 64], sz fp16 [T, kv_heads, 2] = (scale, zero)).  ``cache``: dict(buf, param), the WHOLE pool
 after the call.  Every other stage is an fp16 array [T, features].
@@ -222,11 +226,12 @@ def attention(req, q, pool, layer, theta, *, scale=None, swap=False, head_modulo
 
 
 # ---------------------------------------------------------------------------------------------------- the layer, free-running
-def forward(req, lay, pool, x, wrong=None):
-    """One decoder layer.  ``lay``: dict(w = {projection: the oracle's packed-weight dict}, norm1_w, norm1_idx, norm2_w, norm2_idx,
-    attn_idx, eps, rope_theta, layer_idx); ``pool``: (buf, param) from before the call (not modified); ``x`` fp16 [T, hidden].
-    Returns the trace.  ``wrong``: one name of WRONG (a model-level name changes nothing here)."""
-    assert wrong is None or wrong in WRONG
+ATTN_STAGES = LAYER_STAGES[:LAYER_STAGES.index("gate")]          # the attention half: norm1 .. residual1, norm2
+MLP_STAGES = LAYER_STAGES[len(ATTN_STAGES):]                     # the dense-MLP half: gate, up, act, out
+
+
+def attention_half(req, lay, pool, x, wrong=None):
+    """norm1 .. residual1, norm2 of one decoder layer (what every variant of the layer shares); arguments as ``forward``"""
     x = np.asarray(x, dtype=f16)
     assert x.shape[0] == req.rows
     W, nkv, hidden = lay["w"], req.kv_heads, x.shape[1]
@@ -247,13 +252,28 @@ def forward(req, lay, pool, x, wrong=None):
     aq = tr["attn_q"] = O.reorder_quant(tr["attn"], idx, "kernel", 1.0)
     tr["o"] = gemm(aq, W["o"]).astype(f16)
     tr["residual1"] = (tr["o"].astype(f32) + x.astype(f32)).astype(f16)
-    n2 = tr["norm2"] = O.rmsnorm_reorder_quant(tr["residual1"], lay["norm2_w"], lay["eps"], lay["norm2_idx"], "kernel", 1.0)
+    tr["norm2"] = O.rmsnorm_reorder_quant(tr["residual1"], lay["norm2_w"], lay["eps"], lay["norm2_idx"], "kernel", 1.0)
+    return tr
+
+
+def mlp_half(tr, lay, x, wrong=None):
+    """gate, up, act, out of the dense MLP on the trace's norm2 / residual1, added to ``tr``"""
+    W, n2 = lay["w"], tr["norm2"]
+    is_ = lambda name: wrong == name
     g, u = ("up", "gate") if is_("gate_up_swapped") else ("gate", "up")
     tr["gate"], tr["up"] = gemm(n2, W[g]).astype(f16), gemm(n2, W[u]).astype(f16)
     act = tr["act"] = O.silu_mul_quant(tr["gate"], tr["up"], "kernel", 1.0)
-    res = x if is_("second_residual_from_layer_input") else tr["residual1"]
+    res = np.asarray(x, dtype=f16) if is_("second_residual_from_layer_input") else tr["residual1"]
     tr["out"] = (gemm(act, W["down"]).astype(f16).astype(f32) + res.astype(f32)).astype(f16)
     return tr
+
+
+def forward(req, lay, pool, x, wrong=None):
+    """One decoder layer.  ``lay``: dict(w = {projection: the oracle's packed-weight dict}, norm1_w, norm1_idx, norm2_w, norm2_idx,
+    attn_idx, eps, rope_theta, layer_idx); ``pool``: (buf, param) from before the call (not modified); ``x`` fp16 [T, hidden].
+    Returns the trace.  ``wrong``: one name of WRONG (a model-level name changes nothing here)."""
+    assert wrong is None or wrong in WRONG
+    return mlp_half(attention_half(req, lay, pool, x, wrong), lay, x, wrong)
 
 
 # ---------------------------------------------------------------------------------------------------- the checker
@@ -332,12 +352,8 @@ def _check_attn(req, got, ref):
     return ok, "; ".join(msgs)
 
 
-def check(trace, inputs, report=None):
-    """Every stage of ``trace`` against its restatement on the trace's own previous stage.  ``inputs``: dict(req, lay, pool, x) as
-    ``forward`` takes them.  Returns [(stage, message)], empty when all is well.  ``report``: a list that receives one line per stage
-    with the measured figure."""
-    req, lay, pool, x = inputs["req"], inputs["lay"], inputs["pool"], np.asarray(inputs["x"], dtype=f16)
-    W, steps = lay["w"], x.shape[1] // 128
+def reporter(report):
+    """(fails, put): ``put(stage, (ok, message))`` files a failure under ``fails`` and one line per stage under ``report`` (if given)"""
     fails = []
 
     def put(stage, res):
@@ -346,15 +362,31 @@ def check(trace, inputs, report=None):
             fails.append((stage, msg))
         if report is not None:
             report.append(f"{stage}: {'ok' if ok else 'FAIL'}: {msg}")
+    return fails, put
 
-    missing = [s for s in LAYER_STAGES if s not in trace]
-    if missing:
-        return [(s, "stage absent from the trace") for s in missing]
+
+def absent(trace, stages):
+    """[(stage, message)] for the stages a trace lacks: a stage cannot pass by being absent"""
+    return [(s, "stage absent from the trace") for s in stages if s not in trace]
+
+
+def check_attention_half(trace, inputs, put):
+    """norm1 .. residual1, norm2 of ``trace``, each against its restatement on the trace's own previous stage"""
+    req, lay, pool, x = inputs["req"], inputs["lay"], inputs["pool"], np.asarray(inputs["x"], dtype=f16)
+    W, steps = lay["w"], x.shape[1] // 128
     put("norm1", _quant_exact(trace["norm1"], O.rmsnorm_reorder_quant(x, lay["norm1_w"], lay["eps"], lay["norm1_idx"], "kernel", 1.0)))
     n1 = trace["norm1"]
     put("q", _check_gemm(trace["q"], gemm(n1, W["q"])))
     for name in ("k", "v"):
         put(name, _check_o4(trace[name], gemm(n1, W[name]), gemm_abs(n1, W[name]), steps))
+    check_attention_core(trace, inputs, put)
+    check_attention_tail(trace, inputs, put)
+
+
+def check_attention_core(trace, inputs, put):
+    """cache, attn, attn_q: the pool against the append of the observed k / v codes, the attention of the observed q over that pool, the
+    reorder quantiser of the observed attention output (whatever produced q and the k / v codes)"""
+    req, lay, pool = inputs["req"], inputs["lay"], inputs["pool"]
     want = write_cache(req, pool, trace["k"], trace["v"], lay["layer_idx"])
     same = np.array_equal(trace["cache"]["buf"], want[0]), _bits_equal(trace["cache"]["param"], want[1])
     put("cache", (all(same), "the pool against the append of the observed codes at the described slots: "
@@ -362,11 +394,21 @@ def check(trace, inputs, report=None):
                   f"{int((np.ascontiguousarray(trace['cache']['param']).view(np.uint16) != want[1].view(np.uint16)).sum())} (scale, zero) halves"))
     put("attn", _check_attn(req, trace["attn"], attention(req, trace["q"], want, lay["layer_idx"], lay["rope_theta"])))
     put("attn_q", _quant_exact(trace["attn_q"], O.reorder_quant(trace["attn"], lay["attn_idx"], "kernel", 1.0)))
-    put("o", _check_gemm(trace["o"], gemm(trace["attn_q"], W["o"])))
+
+
+def check_attention_tail(trace, inputs, put):
+    """o, residual1, norm2"""
+    lay, x = inputs["lay"], np.asarray(inputs["x"], dtype=f16)
+    put("o", _check_gemm(trace["o"], gemm(trace["attn_q"], lay["w"]["o"])))
     r1 = (np.asarray(trace["o"], dtype=f16).astype(f32) + x.astype(f32)).astype(f16)
     put("residual1", (_bits_equal(trace["residual1"], r1), "against the fp16 sum of the layer input and o_proj's output"))
     put("norm2", _quant_exact(trace["norm2"], O.rmsnorm_reorder_quant(trace["residual1"], lay["norm2_w"], lay["eps"], lay["norm2_idx"],
                                                                       "kernel", 1.0)))
+
+
+def check_mlp_half(trace, inputs, put):
+    """gate, up, act, out of the dense MLP"""
+    W = inputs["lay"]["w"]
     for name in ("gate", "up"):
         put(name, _check_gemm(trace[name], gemm(trace["norm2"], W[name])))
     put("act", _quant_close(trace["act"], O.silu_mul_quant(trace["gate"], trace["up"], "kernel", 1.0)))
@@ -376,6 +418,18 @@ def check(trace, inputs, report=None):
     err = np.abs(np.asarray(trace["out"], dtype=f16).astype(f64) - ref).max()
     put("out", (bool(over.max() <= 0), f"{int((over > 0).sum())} elements outside the bound, max|err| {err:.4g} (GEMM part of the bound "
                 f"{gemm_bound(D):.4g})"))
+
+
+def check(trace, inputs, report=None):
+    """Every stage of ``trace`` against its restatement on the trace's own previous stage.  ``inputs``: dict(req, lay, pool, x) as
+    ``forward`` takes them.  Returns [(stage, message)], empty when all is well.  ``report``: a list that receives one line per stage
+    with the measured figure."""
+    missing = absent(trace, LAYER_STAGES)
+    if missing:
+        return missing
+    fails, put = reporter(report)
+    check_attention_half(trace, inputs, put)
+    check_mlp_half(trace, inputs, put)
     return fails
 
 
@@ -403,13 +457,14 @@ def _check_logits(got, xn, head):
     return bool(over.max() <= 0), f"{int((over > 0).sum())} logits outside the bound, largest err - bound {over.max():.4g}"
 
 
-def model_forward(req, mdl, pool, ids, wrong=None):
+def model_forward(req, mdl, pool, ids, wrong=None, layer_forward=None):
     """``mdl``: dict(embed fp16 [V, hidden], layers [lay ...], norm_w, eps, head fp16 [V, hidden]).  Trace: embed, layers (each with its
-    observed input under "x"), final_norm, logits."""
+    observed input under "x"), final_norm, logits.  ``layer_forward``: the layer (``forward`` unless given; a variant's has its signature)."""
+    layer_forward = layer_forward or forward
     tr = {"embed": np.asarray(mdl["embed"], dtype=f16)[np.asarray(ids, dtype=np.int64)], "layers": []}
     h = tr["embed"]
     for lay in mdl["layers"]:
-        t = forward(req, lay, pool, h, wrong)
+        t = layer_forward(req, lay, pool, h, wrong)
         t["x"] = h
         tr["layers"].append(t)
         pool, h = (t["cache"]["buf"], t["cache"]["param"]), t["out"]
@@ -420,8 +475,10 @@ def model_forward(req, mdl, pool, ids, wrong=None):
     return tr
 
 
-def check_model(trace, inputs, report=None):
-    """``inputs``: dict(req, mdl, pool, ids).  Every layer teacher-forced on its observed input and the pool the layer before left."""
+def check_model(trace, inputs, report=None, layer_check=None):
+    """``inputs``: dict(req, mdl, pool, ids).  Every layer teacher-forced on its observed input and the pool the layer before left.
+    ``layer_check``: the layer's checker (``check`` unless given; a variant's has its signature)."""
+    layer_check = layer_check or check
     req, mdl, pool = inputs["req"], inputs["mdl"], inputs["pool"]
     fails = []
     want = np.asarray(mdl["embed"], dtype=f16)[np.asarray(inputs["ids"], dtype=np.int64)]
@@ -434,7 +491,7 @@ def check_model(trace, inputs, report=None):
         if not _bits_equal(t["x"], h):
             fails.append((f"layer{i}.x", "the layer's input is not the output of the stage before it"))
         rep = None if report is None else []
-        fails += [(f"layer{i}.{s}", m) for s, m in check(t, dict(req=req, lay=lay, pool=pool, x=t["x"]), rep)]
+        fails += [(f"layer{i}.{s}", m) for s, m in layer_check(t, dict(req=req, lay=lay, pool=pool, x=t["x"]), rep)]
         if report is not None:
             report += [f"layer{i}.{line}" for line in rep]
         pool, h = (t["cache"]["buf"], t["cache"]["param"]), t["out"]
