@@ -28,6 +28,7 @@
 // The stale tail of a copied page is harmless: attention reads up to last_page_offset.
 #include "common.h"
 #include "beam_math.h"
+#include "vocab_row.h"
 #include "kv_attn.h"
 
 namespace atom {
@@ -198,10 +199,10 @@ int atom_beam_select(const int64_t *top_ids, const float *top_lp, const float *c
   if (groups < 1 || groups > 0x7fffffff / (beam::kMaxBeams * beam::kMaxCand)) return ATOM_ERR_SHAPE;
   if (w_out < 1 || w_out > beam::kMaxBeams || (w_in != 1 && w_in != w_out) || C < w_out || C > beam::kMaxCand) return ATOM_ERR_SHAPE;
   for (const void *q : {(const void *)top_ids, (const void *)token})
-    if (reinterpret_cast<uintptr_t>(q) & 7u) return ATOM_ERR_ALIGN;
+    if (off_by(q, 7u)) return ATOM_ERR_ALIGN;
   for (const void *q : {(const void *)top_lp, (const void *)cum, (const void *)finished, (const void *)length, (const void *)parent,
                         (const void *)cum_out, (const void *)finished_out, (const void *)length_out})
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
+    if (off_by(q, 3u)) return ATOM_ERR_ALIGN;
   BeamSelectParams p{top_ids, top_lp, cum, finished, length, parent, token, cum_out, finished_out, length_out, w_in, w_out, C, eos};
   hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)groups), dim3(kBeamThreads), 0, reinterpret_cast<hipStream_t>(stream), p);
   return check_launch();
@@ -219,7 +220,7 @@ int atom_kv_beam_fork_i4(void *kv_data, void *kv_param, const int32_t *table_in,
   if (!aligned16(kv_param)) return ATOM_ERR_ALIGN;
   for (const void *q : {(const void *)table_in, (const void *)table_out, (const void *)spare_in, (const void *)spare_out,
                         (const void *)row_pages, (const void *)lens, (const void *)state, (const void *)parent})
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
+    if (off_by(q, 3u)) return ATOM_ERR_ALIGN;
   // the launch gathers from rows that other workgroups own: it must not write what it reads
   if (overlap(table_in, table_out, (int64_t)batch * cap * 4) || overlap(spare_in, spare_out, (int64_t)batch * 4)) return ATOM_ERR_INVALID_ARG;
   const int64_t slots = (int64_t)num_layers * 2 * num_heads * page_size;          // (layer, K/V, head, token) per page

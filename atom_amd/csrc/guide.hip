@@ -16,6 +16,7 @@
 // and the forced drafts written with plain stores.  guide_math.h walk.
 #include "common.h"
 #include "guide_math.h"
+#include "vocab_row.h"
 
 namespace atom {
 
@@ -53,6 +54,7 @@ __global__ __launch_bounds__(kGuideThreads) void guide_mask_kernel(GuideMaskPara
   uint32_t lg[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) lg[c] = 0;
+  // load8 / store8 of vocab_row.h written out: through the helpers this kernel compiles to other code (the masks of the 16-byte form are kept)
   if (VEC && n == 8) {
     const v4u x = *reinterpret_cast<const v4u *>(lrow + e0);
 #pragma unroll
@@ -123,11 +125,10 @@ int atom_guide_mask_f16(const void *logits, int64_t ld, int64_t batch, int64_t v
       mask_ld < (vocab + 31) / 32 || num_states < 1 || num_states > INT32_MAX || mask_ld > INT32_MAX || num_states * mask_ld > INT32_MAX ||
       (out == logits && out_ld != ld))
     return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
-  if (off(logits, 1u) || off(out, 1u) || off(state, 3u) || off(mask, 3u) || off(status, 3u)) return ATOM_ERR_ALIGN;
+  if (off_by(logits, 1u) || off_by(out, 1u) || off_by(state, 3u) || off_by(mask, 3u) || off_by(status, 3u)) return ATOM_ERR_ALIGN;
   GuideMaskParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, state, mask, mask_ld, num_states, static_cast<uint16_t *>(out), out_ld, status};
   // every row of both buffers starts on 16 bytes (the mask is read by the byte: it needs no more than its element's alignment)
-  const bool vec = aligned16(logits) && (ld % 8) == 0 && aligned16(out) && (out_ld % 8) == 0;
+  const bool vec = rows_aligned16(logits, ld) && rows_aligned16(out, out_ld);
   const dim3 grid((unsigned)((vocab + kGuideTile - 1) / kGuideTile), (unsigned)batch);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (vec) hipLaunchKernelGGL((guide_mask_kernel<true>), grid, dim3(kGuideThreads), 0, s, p);
@@ -139,8 +140,9 @@ int atom_guide_advance(int32_t *state, const int64_t *tokens, int64_t batch, con
                        const int32_t *edge_next, int64_t num_states, int64_t num_edges, int32_t *status, void *stream) {
   if (!state || !tokens || !indptr || !status || (num_edges > 0 && (!edge_tok || !edge_next))) return ATOM_ERR_INVALID_ARG;
   if (batch < 1 || batch > kGuideMaxBatch || num_states < 1 || num_states >= INT32_MAX || num_edges < 0 || num_edges > INT32_MAX) return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
-  if (off(state, 3u) || off(tokens, 7u) || off(indptr, 3u) || off(edge_tok, 3u) || off(edge_next, 3u) || off(status, 3u)) return ATOM_ERR_ALIGN;
+  if (off_by(state, 3u) || off_by(tokens, 7u) || off_by(indptr, 3u) || off_by(edge_tok, 3u) || off_by(edge_next, 3u) ||
+      off_by(status, 3u))
+    return ATOM_ERR_ALIGN;
   const unsigned blocks = (unsigned)((batch + kGuideAdvThreads - 1) / kGuideAdvThreads);
   hipLaunchKernelGGL(guide_advance_kernel, dim3(blocks), dim3(kGuideAdvThreads), 0, reinterpret_cast<hipStream_t>(stream), state, tokens,
                      (int)batch, indptr, edge_tok, edge_next, num_states, num_edges, status);
@@ -154,9 +156,8 @@ int atom_guide_walk_rows(int32_t *state, const int32_t *adds, int32_t *row_state
   if (batch < 1 || batch > kGuideMaxBatch || rows < 1 || rows > guide::kMaxWalkRows || ids_ld < rows || num_states < 1 ||
       num_states >= INT32_MAX || num_edges < 0 || num_edges > INT32_MAX)
     return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
-  if (off(state, 3u) || off(adds, 3u) || off(row_state, 3u) || off(input_ids, 7u) || off(indptr, 3u) || off(edge_tok, 3u) ||
-      off(edge_next, 3u) || off(status, 3u))
+  if (off_by(state, 3u) || off_by(adds, 3u) || off_by(row_state, 3u) || off_by(input_ids, 7u) || off_by(indptr, 3u) ||
+      off_by(edge_tok, 3u) || off_by(edge_next, 3u) || off_by(status, 3u))
     return ATOM_ERR_ALIGN;
   const unsigned blocks = (unsigned)((batch + kGuideAdvThreads - 1) / kGuideAdvThreads);
   hipLaunchKernelGGL(guide_walk_rows_kernel, dim3(blocks), dim3(kGuideAdvThreads), 0, reinterpret_cast<hipStream_t>(stream), state, adds,

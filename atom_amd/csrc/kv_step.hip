@@ -26,6 +26,7 @@
 // ones and the rest is overwritten; there is no rollback and no negative count.
 #include "common.h"
 #include "kv_attn.h"
+#include "vocab_row.h"
 
 namespace atom {
 
@@ -147,7 +148,7 @@ static int kv_step(KvStepParams p, bool rows, hipStream_t stream) {
   if ((int64_t)p.cap * p.P > 0x7fffffff || (int64_t)p.batch * p.cap > 0x7fffffff) return ATOM_ERR_SHAPE;
   for (const void *q : {(const void *)p.table, (const void *)p.rows, (const void *)p.lens, (const void *)p.indptr, (const void *)p.indices,
                         (const void *)p.lpo, (const void *)p.state, (const void *)p.adds})
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return ATOM_ERR_ALIGN;
+    if (off_by(q, 3u)) return ATOM_ERR_ALIGN;
   const dim3 grid((unsigned)((p.batch + kStepRows - 1) / kStepRows), (unsigned)step_slices(p.batch, p.cap));
   if (rows) hipLaunchKernelGGL(kv_step_kernel<true>, grid, dim3(kStepThreads), 0, stream, p);
   else hipLaunchKernelGGL(kv_step_kernel<false>, grid, dim3(kStepThreads), 0, stream, p);

@@ -15,6 +15,7 @@
 // Safety: a target is compared with 0 and vocab before it is used as an index; a top-n index is an element position below vocab.
 #include "common.h"
 #include "sample_math.h"
+#include "vocab_row.h"
 
 #include <type_traits>
 
@@ -48,29 +49,6 @@ struct LogprobShared {
   unsigned long long top[kLogprobMaxTop];
 };
 
-// canonical keys of the 8 elements from e0 on (0 where there is none): one 16-byte load where the row allows it and all 8 exist
-template <bool VEC>
-__device__ __forceinline__ void logprob_load_slab(const uint16_t *row, int vocab, int e0, uint32_t *d) {
-  d[0] = d[1] = d[2] = d[3] = 0;
-  if (e0 >= vocab) return;
-  if (VEC && e0 + 8 <= vocab) {
-    const v4u x = *reinterpret_cast<const v4u *>(row + e0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d[i] = sm::canon_key(x[i] & 0xFFFFu) | (sm::canon_key(x[i] >> 16) << 16);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (e0 + c < vocab) d[c >> 1] |= sm::canon_key(row[e0 + c]) << ((c & 1) * 16);
-  }
-}
-
-__device__ __forceinline__ uint32_t logprob_key_at(const uint32_t *d, int c) { return (d[c >> 1] >> ((c & 1) * 16)) & 0xFFFFu; }
-
-__device__ __forceinline__ uint64_t logprob_shfl_xor_u64(uint64_t x, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)x, d, 64), hi = __shfl_xor((uint32_t)(x >> 32), d, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 template <int NQ, bool VEC>
 __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams p) {
   __shared__ LogprobShared S;
@@ -90,7 +68,7 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
 #pragma unroll 4
       for (int q = 0; q < nslab; ++q) {                        // unrolled: four slabs' loads in flight, not one
         uint32_t d[4];
-        logprob_load_slab<VEC>(row, vocab, (q * kLogprobThreads + tid) * 8, d);
+        load_slab<VEC>(row, vocab, (q * kLogprobThreads + tid) * 8, d);
         f((q * kLogprobThreads + tid) * 8, d);
       }
     }
@@ -99,12 +77,12 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
   // ---- pass A: the maximum key
   if constexpr (NQ > 0) {
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) logprob_load_slab<VEC>(row, vocab, (q * kLogprobThreads + tid) * 8, &v[q * 4]);
+    for (int q = 0; q < NQ; ++q) load_slab<VEC>(row, vocab, (q * kLogprobThreads + tid) * 8, &v[q * 4]);
   }
   uint32_t mx = 0;
   slabs([&](int, const uint32_t *d) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) mx = max(mx, logprob_key_at(d, c));
+    for (int c = 0; c < 8; ++c) mx = max(mx, key_at(d, c));
   });
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, d, 64));
@@ -130,7 +108,7 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
     slabs([&](int e0, const uint32_t *d) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const uint32_t key = logprob_key_at(d, c);
+        const uint32_t key = key_at(d, c);
         if (key != 0) {
           if constexpr (decltype(with_z)::value) z += sm::weight(sm::key_value(key), mval, 1.0f);
           if constexpr (decltype(with_rank)::value) cnt += (key > kt || (key == kt && e0 + c < t)) ? 1u : 0u;
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
   if (want_z || want_rank) {                                   // uniform over the workgroup
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-      z += logprob_shfl_xor_u64(z, d);
+      z += shfl_xor_u64(z, d);
       cnt += (uint32_t)__shfl_xor(cnt, d, 64);
     }
     if (lane == 0) { S.red_z[wave] = z; S.red_cnt[wave] = cnt; }
@@ -172,7 +150,7 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
     slabs([&](int e0, const uint32_t *d) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const uint32_t key = logprob_key_at(d, c);
+        const uint32_t key = key_at(d, c);
         const uint64_t comp = ((uint64_t)key << 32) | (uint32_t)~(uint32_t)(e0 + c);
         if (key != 0 && comp < bound && comp > best) best = comp;
       }
@@ -184,7 +162,7 @@ __global__ __launch_bounds__(kLogprobThreads) void logprob_kernel(LogprobParams 
     uint64_t best = mine;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-      const uint64_t o = logprob_shfl_xor_u64(best, d);
+      const uint64_t o = shfl_xor_u64(best, d);
       best = o > best ? o : best;
     }
     if (lane == 0) S.red_best[j & 1][wave] = best;
@@ -227,11 +205,10 @@ int atom_logprob_f16(const void *logits, int64_t ld, int64_t rows, int64_t vocab
   if (top_n == 0 && (!targets || (!logprob && !rank))) return ATOM_ERR_INVALID_ARG;   // nothing to do
   if (rows < 1 || rows > 0x7fffffff || vocab < 1 || vocab > sample::kMaxVocab || ld < vocab || top_n < 0 || top_n > kLogprobMaxTop)
     return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
-  if (off(logits, 1u) || off(targets, 7u) || off(logprob, 3u) || off(rank, 3u) || off(top_ids, 7u) || off(top_logprobs, 3u))
+  if (off_by(logits, 1u) || off_by(targets, 7u) || off_by(logprob, 3u) || off_by(rank, 3u) || off_by(top_ids, 7u) || off_by(top_logprobs, 3u))
     return ATOM_ERR_ALIGN;
   LogprobParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, targets, logprob, rank, (int)top_n, top_ids, top_logprobs};
-  const bool vec = aligned16(logits) && (ld % 8) == 0;         // every row starts on 16 bytes
+  const bool vec = rows_aligned16(logits, ld);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (vocab <= kLogprobRegSlabs * kLogprobSlab) return launch_logprob<kLogprobRegSlabs>(p, vec, (int)rows, s);
   return launch_logprob<0>(p, vec, (int)rows, s);

@@ -15,6 +15,7 @@
 // read from device memory becomes a global address.
 #include "common.h"
 #include "penalty_math.h"
+#include "vocab_row.h"
 
 namespace atom {
 
@@ -39,34 +40,6 @@ struct PenalizeParams {
   uint16_t *out;
   int64_t out_ld;
 };
-
-// n (1 .. 8) 16-bit words from src, one per dword of d: one 16-byte load where the row allows it and all 8 exist
-template <bool VEC>
-__device__ __forceinline__ void load8(const uint16_t *src, int n, uint32_t *d) {
-  if (VEC && n == 8) {
-    const v4u x = *reinterpret_cast<const v4u *>(src);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { d[2 * i] = x[i] & 0xFFFFu; d[2 * i + 1] = x[i] >> 16; }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (c < n) d[c] = src[c];
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store8(uint16_t *dst, int n, const uint32_t *d) {
-  if (VEC && n == 8) {
-    v4u x;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x[i] = (d[2 * i] & 0xFFFFu) | (d[2 * i + 1] << 16);
-    *reinterpret_cast<v4u *>(dst) = x;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (c < n) dst[c] = (uint16_t)d[c];
-  }
-}
 
 template <bool BIAS, bool VEC>
 __global__ __launch_bounds__(kPenThreads) void penalize_kernel(PenalizeParams p) {
@@ -177,14 +150,12 @@ int atom_penalize_f16(const void *logits, int64_t ld, int64_t batch, int64_t voc
   if (batch < 1 || batch > kPenMaxBatch || vocab < 1 || vocab > penalty::kMaxVocab || ld < vocab || out_ld < vocab ||
       (state && state_ld < vocab) || max_bias < 0 || max_bias > penalty::kMaxBias || (out == logits && out_ld != ld))
     return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
-  if (off(logits, 1u) || off(out, 1u) || off(state, 1u) || off(fed, 7u) || off(rep, 3u) || off(pres, 3u) || off(freq, 3u) ||
-      (max_bias > 0 && (off(bias_ids, 3u) || off(bias_vals, 3u))))
+  if (off_by(logits, 1u) || off_by(out, 1u) || off_by(state, 1u) || off_by(fed, 7u) || off_by(rep, 3u) || off_by(pres, 3u) || off_by(freq, 3u) ||
+      (max_bias > 0 && (off_by(bias_ids, 3u) || off_by(bias_vals, 3u))))
     return ATOM_ERR_ALIGN;
   PenalizeParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, reinterpret_cast<uint16_t *>(state), state_ld, fed, rep, pres, freq,
                    bias_ids, bias_vals, (int)max_bias, static_cast<uint16_t *>(out), out_ld};
-  // every row of every buffer starts on 16 bytes
-  const bool vec = aligned16(logits) && (ld % 8) == 0 && aligned16(out) && (out_ld % 8) == 0 && (!state || (aligned16(state) && (state_ld % 8) == 0));
+  const bool vec = rows_aligned16(logits, ld) && rows_aligned16(out, out_ld) && rows_aligned16(state, state_ld);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   return max_bias > 0 ? launch_penalize<true>(p, vec, (int)batch, s) : launch_penalize<false>(p, vec, (int)batch, s);
 }

@@ -23,6 +23,7 @@
 // compared and multiplied, never used as an address.
 #include "common.h"
 #include "sample_math.h"
+#include "vocab_row.h"
 
 namespace atom {
 
@@ -69,29 +70,6 @@ struct Prefix {
   uint32_t take, count;
   uint64_t sum;
 };
-
-// canonical keys of the 8 elements from e0 on (0 where there is none): one 16-byte load where the row allows it and all 8 exist
-template <bool VEC>
-__device__ __forceinline__ void load_slab(const uint16_t *row, int vocab, int e0, uint32_t *d) {
-  d[0] = d[1] = d[2] = d[3] = 0;
-  if (e0 >= vocab) return;
-  if (VEC && e0 + 8 <= vocab) {
-    const v4u x = *reinterpret_cast<const v4u *>(row + e0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d[i] = sm::canon_key(x[i] & 0xFFFFu) | (sm::canon_key(x[i] >> 16) << 16);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-      if (e0 + c < vocab) d[c >> 1] |= sm::canon_key(row[e0 + c]) << ((c & 1) * 16);
-  }
-}
-
-__device__ __forceinline__ uint32_t key_at(const uint32_t *d, int c) { return (d[c >> 1] >> ((c & 1) * 16)) & 0xFFFFu; }
-
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t x, int d) {
-  const uint32_t lo = __shfl_up((uint32_t)x, d, 64), hi = __shfl_up((uint32_t)(x >> 32), d, 64);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // inclusive scan of (c, w) over threads 0 .. 255 (the others pass zeros through); every thread of the workgroup calls it
 __device__ __forceinline__ void scan256(uint32_t &c, uint64_t &w, SampleShared &S) {
@@ -390,11 +368,10 @@ static int sample_f16(const void *logits, int64_t ld, int64_t batch, int64_t voc
                       int64_t *tokens, void *stream) {
   if (!logits || !tokens) return ATOM_ERR_INVALID_ARG;
   if (batch < 1 || batch > 0x7fffffff || vocab < 1 || vocab > sample::kMaxVocab || ld < vocab) return ATOM_ERR_SHAPE;
-  const auto off = [](const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; };
-  if (off(logits, 1u) || off(temperature, 3u) || off(top_k, 3u) || off(top_p, 3u) || off(seeds, 7u) || off(step, 7u) || off(tokens, 7u))
+  if (off_by(logits, 1u) || off_by(temperature, 3u) || off_by(top_k, 3u) || off_by(top_p, 3u) || off_by(seeds, 7u) || off_by(step, 7u) || off_by(tokens, 7u))
     return ATOM_ERR_ALIGN;
   SampleParams p{static_cast<const uint16_t *>(logits), ld, (int)vocab, temperature, top_k, top_p, seeds, step, step_offset, tokens, rows_per_seq};
-  const bool vec = aligned16(logits) && (ld % 8) == 0;         // every row starts on 16 bytes
+  const bool vec = rows_aligned16(logits, ld);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (vocab <= 4 * kSampleSlab) return launch_sample<4, 0>(p, vec, (int)batch, s);
   if (vocab <= (kSampleRegSlabs + kSampleLdsSlabs) * kSampleSlab) return launch_sample<kSampleRegSlabs, kSampleLdsSlabs>(p, vec, (int)batch, s);

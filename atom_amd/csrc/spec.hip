@@ -18,6 +18,7 @@
 // as an address.
 #include "common.h"
 #include "spec_math.h"
+#include "vocab_row.h"
 
 namespace atom {
 
@@ -132,8 +133,6 @@ __global__ __launch_bounds__(kAcceptThreads) void spec_accept_kernel(SpecAcceptP
     p.done[0] = all;
   }
 }
-
-static bool off_by(const void *q, unsigned mask) { return (reinterpret_cast<uintptr_t>(q) & mask) != 0; }
 
 }  // namespace atom
 

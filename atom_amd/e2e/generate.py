@@ -70,6 +70,19 @@ def _check_logprobs(logprobs):
     return None if logprobs is None else int(logprobs)
 
 
+def _params_list(params, batch: int = None) -> list:
+    """One ``SamplingParams`` or one per sequence, as a list; with ``batch``: one entry per sequence, checked."""
+    ps = [params] * (1 if batch is None else batch) if isinstance(params, SamplingParams) else list(params)
+    if batch is not None and (len(ps) != batch or not all(isinstance(q, SamplingParams) for q in ps)):
+        raise ValueError(f"sampling: one SamplingParams, or one per sequence ({batch})")
+    return ps
+
+
+def _static_rows(rows: int, vocab: int, device) -> torch.Tensor:
+    """A static fp16 [rows, vocab] buffer whose rows start on 16 bytes: a view of vocab rounded up to 8 columns"""
+    return torch.zeros((rows, -(-vocab // 8) * 8), dtype=torch.float16, device=device)[:, :vocab]
+
+
 class Sampler:
     """The per-sequence sampling parameters as four ``[batch]`` device buffers at FIXED addresses (``temperature`` float32, ``top_k``
     int32, ``top_p`` float32, ``seeds`` int64), so a captured ``ops.sample`` follows ``set``."""
@@ -84,9 +97,7 @@ class Sampler:
 
     def set(self, params: Union[SamplingParams, Sequence[SamplingParams]]):
         """One ``SamplingParams`` for all sequences or one per sequence, copied into the buffers in place."""
-        ps = [params] * self.batch if isinstance(params, SamplingParams) else list(params)
-        if len(ps) != self.batch or not all(isinstance(q, SamplingParams) for q in ps):
-            raise ValueError(f"sampling: one SamplingParams, or one per sequence ({self.batch})")
+        ps = _params_list(params, self.batch)
         seeds = [int(q.seed) & (2 ** 64 - 1) for q in ps]
         self.temperature.copy_(torch.tensor([float(q.temperature) for q in ps], dtype=torch.float32))
         self.top_k.copy_(torch.tensor([max(min(int(q.top_k), 2 ** 31 - 1), -1) for q in ps], dtype=torch.int32))
@@ -109,8 +120,7 @@ class LogitPenalties:
                  max_bias: int = None):
         self.batch, self.vocab = int(batch), int(vocab)
         if max_bias is None:
-            ps = [params] if isinstance(params, SamplingParams) else list(params)
-            max_bias = max([len(q.logit_bias or ()) for q in ps if isinstance(q, SamplingParams)] or [0])
+            max_bias = max([len(q.logit_bias or ()) for q in _params_list(params) if isinstance(q, SamplingParams)] or [0])
         if not 0 <= int(max_bias) <= ops.PENALTY_MAX_BIAS:
             raise ValueError(f"logit_bias: at most {ops.PENALTY_MAX_BIAS} entries per sequence, got {max_bias}")
         self.max_bias = int(max_bias)
@@ -124,9 +134,7 @@ class LogitPenalties:
 
     def set(self, params: Union[SamplingParams, Sequence[SamplingParams]]):
         """One ``SamplingParams`` for all sequences or one per sequence, copied into the buffers in place; the state is not touched."""
-        ps = [params] * self.batch if isinstance(params, SamplingParams) else list(params)
-        if len(ps) != self.batch or not all(isinstance(q, SamplingParams) for q in ps):
-            raise ValueError(f"sampling: one SamplingParams, or one per sequence ({self.batch})")
+        ps = _params_list(params, self.batch)
         ids = torch.full((self.batch, self.max_bias), -1, dtype=torch.int32)
         vals = torch.zeros((self.batch, self.max_bias), dtype=torch.float32)
         for b, q in enumerate(ps):
@@ -162,7 +170,57 @@ class LogitPenalties:
                             self.bias_ids if has_bias else None, self.bias_vals if has_bias else None, out=out)
 
 
-class DecodeGraph:
+def _as_sampler(sampler, batch: int, device):
+    """None, a ``Sampler`` of ``batch`` rows, or one built from ``SamplingParams`` (one, or one per sequence)"""
+    sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
+    assert sampler is None or sampler.batch == batch
+    return sampler
+
+
+def _choose_tokens(logits: torch.Tensor, sampler: Sampler, penalties: LogitPenalties, guide: LogitGuide, *, fed: torch.Tensor = None,
+                   penalised: torch.Tensor = None, guided: torch.Tensor = None, step: torch.Tensor = None, step_offset: int = 0):
+    """The next token of every row of the raw ``logits`` fp16 [batch, vocab], int64 [batch]: penalised (``penalties``: ``fed`` is counted
+    first, into the static buffer ``penalised`` if given), then masked (``guide``: in place in the penalised row, else into ``guided``
+    if given), then the argmax or, with ``sampler``, draw number ``step[0] + step_offset``.  A stage that is None adds no launch;
+    ``logits`` is left as it is (log-probabilities and returned logits describe it)."""
+    row = logits
+    if penalties is not None:                              # the token fed in is counted, then the row is penalised: one launch
+        row = penalties.apply(logits, fed=fed, out=penalised)
+    if guide is not None:                                  # what the state does not allow becomes -inf: one launch
+        row = guide.mask(row, out=guided if penalties is None else row)
+    if sampler is None:
+        return row.argmax(dim=-1)
+    return sampler.sample(row, step=step, step_offset=step_offset)
+
+
+class _StepReplay:
+    """A step of device work, ``_step()``, run up to ``max_steps`` times by graph replay.  The first ``step()`` runs eagerly: it builds
+    what a capture cannot -- the fused weight operands, the weight-scale pair tags, the workspace.  The second is captured on torch's
+    capture stream (one stream: a single chain of launches) and replayed; every later one is a replay.  ``steps_done`` counts on the
+    host; nothing reaches the host between two steps."""
+
+    def __init__(self, max_steps: int):
+        self.max_steps = int(max_steps)
+        self._graph = None
+        self.steps_done = 0
+
+    def step(self):
+        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
+        if self.steps_done >= self.max_steps:
+            raise RuntimeError(f"{type(self).__name__}: all {self.max_steps} steps are taken")
+        if self.steps_done == 0:
+            self._step()
+        else:
+            if self._graph is None:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
+                    self._step()
+                self._graph = graph
+            self._graph.replay()
+        self.steps_done += 1
+
+
+class DecodeGraph(_StepReplay):
     """One decode step over ``static_kv``, run up to ``max_steps`` times: greedy, or sampled with ``sampler`` (a ``Sampler``, or
     ``SamplingParams`` -- one, or one per sequence -- to build ``self.sampler`` from).  Step i (from 0) takes draw number i + 1 of
     every sequence; draw 0 belongs to the token the caller feeds in.  ``self.sampler.set(...)`` between steps changes the parameters
@@ -171,10 +229,9 @@ class DecodeGraph:
     Static buffers: ``input_ids`` int64 [batch] (the tokens the next step consumes), ``tokens`` int64 [max_steps, batch] (row i: the
     tokens step i produced) and, with ``keep_logits=True``, ``logits`` fp16 [max_steps, batch, vocab]; a device counter indexes the rows.
     A step is ``static_kv.step()`` (every sequence gains a slot, its page tables are rebuilt on the device), the model's forward for
-    one token per sequence, ``argmax`` (``sampler=None``) or ``ops.sample`` reading the device counter as its step.  The first
-    ``step()`` runs eagerly: it builds what a capture cannot -- the fused weight operands, the weight-scale pair tags, the workspace.  The second is captured on torch's capture stream (one stream: a single
-    chain of launches) and replayed; every later one is a replay.  ``steps_done`` counts on the host; the capacity check is the
-    cache's status word (``static_kv.sync_host()``), read after the loop.
+    one token per sequence, ``argmax`` (``sampler=None``) or ``ops.sample`` reading the device counter as its step.  ``step()`` runs it
+    eagerly, captures it and replays it as ``_StepReplay`` says; the capacity check is the cache's status word
+    (``static_kv.sync_host()``), read after the loop.
 
     ``logprobs``: None is the step above.  0 adds one ops.logprob after the argmax / ops.sample, on the same logits with the chosen
     tokens as targets, and records ``token_logprobs`` float32 / ``token_ranks`` int32 [max_steps, batch]; 1 .. 32 also records the
@@ -193,7 +250,8 @@ class DecodeGraph:
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_steps: int, *, keep_logits: bool = False, sampler=None,
                  logprobs: int = None, penalties: LogitPenalties = None, guide: LogitGuide = None):
         assert max_steps >= 1
-        self.model, self.kv, self.max_steps = model, static_kv, int(max_steps)
+        super().__init__(max_steps)
+        self.model, self.kv = model, static_kv
         device = static_kv.data.device
         self.batch = batch = static_kv.last_page_offset.numel()
         self.input_ids = torch.zeros(batch, dtype=torch.int64, device=device)
@@ -202,19 +260,18 @@ class DecodeGraph:
                        if keep_logits else None)
         self._counter = torch.zeros(1, dtype=torch.int64, device=device)
         self._blen = BatchLenInfo([], batch, device)
-        self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
-        assert self.sampler is None or self.sampler.batch == batch
+        self.sampler = _as_sampler(sampler, batch, device)
         self.penalties, self.penalised = penalties, None
         if penalties is not None:
             if self.sampler is None:
                 raise ValueError("DecodeGraph: penalties need a sampler (temperature = 0 is greedy over the penalised row)")
             assert penalties.batch == batch and penalties.vocab == model.config.vocab_size
-            self.penalised = torch.zeros((batch, penalties.state.size(1)), dtype=torch.float16, device=device)[:, :penalties.vocab]
+            self.penalised = _static_rows(batch, penalties.vocab, device)
         self.guide, self.guided = guide, None
         if guide is not None:
             assert guide.batch == batch and guide.vocab == model.config.vocab_size
             if penalties is None:
-                self.guided = torch.zeros((batch, -(-guide.vocab // 8) * 8), dtype=torch.float16, device=device)[:, :guide.vocab]
+                self.guided = _static_rows(batch, guide.vocab, device)
         self.logprobs = n = _check_logprobs(logprobs)
         self.token_logprobs = self.token_ranks = self.top_ids = self.top_logprobs = None
         if n is not None:
@@ -223,8 +280,6 @@ class DecodeGraph:
             if n > 0:
                 self.top_ids = torch.zeros((self.max_steps, batch, n), dtype=torch.int64, device=device)
                 self.top_logprobs = torch.zeros((self.max_steps, batch, n), dtype=torch.float32, device=device)
-        self._graph = None
-        self.steps_done = 0
 
     @torch.no_grad()
     def _step(self):
@@ -232,15 +287,8 @@ class DecodeGraph:
             self.guide.advance(self.input_ids)
         self.kv.step()
         logits, _ = self.model(self.input_ids, self._blen, None, self.kv)
-        row = logits
-        if self.penalties is not None:                     # the token fed in is counted, then the row is penalised: one launch
-            row = self.penalties.apply(logits, fed=self.input_ids, out=self.penalised)
-        if self.guide is not None:                         # what the state does not allow becomes -inf: one launch
-            row = self.guide.mask(row, out=self.guided if self.penalties is None else self.penalised)
-        if self.sampler is None:
-            nxt = row.argmax(dim=-1)
-        else:
-            nxt = self.sampler.sample(row, step=self._counter, step_offset=1)
+        nxt = _choose_tokens(logits, self.sampler, self.penalties, self.guide, fed=self.input_ids, penalised=self.penalised,
+                             guided=self.guided, step=self._counter, step_offset=1)
         self.tokens.index_copy_(0, self._counter, nxt.unsqueeze(0))
         if self.logprobs is not None:
             got = ops.logprob(logits, nxt, self.logprobs)
@@ -251,21 +299,6 @@ class DecodeGraph:
             self.logits.index_copy_(0, self._counter, logits.unsqueeze(0))
         self.input_ids.copy_(nxt)
         self._counter.add_(1)
-
-    def step(self):
-        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"DecodeGraph: all {self.max_steps} steps are taken")
-        if self.steps_done == 0:
-            self._step()
-        else:
-            if self._graph is None:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
-                    self._step()
-                self._graph = graph
-            self._graph.replay()
-        self.steps_done += 1
 
     def run(self, first_tokens: torch.Tensor) -> torch.Tensor:
         """Feed ``first_tokens`` [batch] and take every step that is left; returns ``tokens`` [max_steps, batch]."""
@@ -321,9 +354,9 @@ class NgramDrafter:
         ops.spec_draft_ngram(hist, hist_len, out, ngram_max=self.ngram_max, ngram_min=self.ngram_min)
 
 
-class SpecDecodeGraph:
+class SpecDecodeGraph(_StepReplay):
     """One speculative step over ``static_kv``, run until every sequence holds ``max_new`` tokens (its budget), as ``DecodeGraph`` runs
-    a decode step: the first ``step()`` eager, the second captured, the rest replays.  With Q = K + 1 a step is
+    a decode step (``_StepReplay``: eager, captured, replayed).  With Q = K + 1 a step is
       1. ``static_kv.step_rows(adds, lookahead=Q)``: the tokens the last step accepted are committed, Q tentative slots follow them;
       2. ``drafter.propose``: K drafts into columns 1 .. K of ``input_ids`` (column 0 is the last emitted token);
       3. the model's forward over the ``batch * Q`` rows as Q-token prefill requests on the static cache (the verify forward);
@@ -344,12 +377,12 @@ class SpecDecodeGraph:
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_new: int, *, params: SpeculativeParams = SpeculativeParams(),
                  drafter=None, sampler=None, guide: LogitGuide = None):
         assert max_new >= 2
+        super().__init__(int(max_new) - 1)                     # every step emits a token for every unfinished row: the all-rejected bound
         self.model, self.kv, self.max_new, self.params = model, static_kv, int(max_new), params
         device = static_kv.data.device
         self.batch = batch = static_kv.last_page_offset.numel()
         self.K = K = int(params.num_draft_tokens)
         self.Q = Q = K + 1
-        self.max_steps = self.max_new - 1                      # every step emits a token for every unfinished row: the all-rejected bound
         self.drafter = NgramDrafter(params.ngram_max, params.ngram_min) if drafter is None else drafter
         self.hist_cap = max(static_kv.seqlens) + self.max_new   # the longest prompt (the cache's lengths at construction) + every new token
         i32 = dict(dtype=torch.int32, device=device)
@@ -362,8 +395,7 @@ class SpecDecodeGraph:
         self.done = torch.zeros(1, **i32)
         self._targets = torch.zeros(batch * Q, dtype=torch.int64, device=device)
         self._blen = BatchLenInfo([Q] * batch, 0, device)
-        self.sampler = sampler if sampler is None or isinstance(sampler, Sampler) else Sampler(batch, device, sampler)
-        assert self.sampler is None or self.sampler.batch == batch
+        self.sampler = _as_sampler(sampler, batch, device)
         self._sample_rows = None
         if self.sampler is not None:
             s = self.sampler
@@ -372,9 +404,7 @@ class SpecDecodeGraph:
         if guide is not None:
             assert guide.batch == batch and guide.vocab == model.config.vocab_size
             guide.rows(Q)
-            self.guided = torch.zeros((batch * Q, -(-guide.vocab // 8) * 8), dtype=torch.float16, device=device)[:, :guide.vocab]
-        self._graph = None
-        self.steps_done = 0
+            self.guided = _static_rows(batch * Q, guide.vocab, device)
 
     def start(self, prompts: Sequence[Sequence[int]], first_tokens: torch.Tensor, budget: Sequence[int] = None):
         """The state after the prefill: ``hist`` = each prompt and its first new token (draw 0), one token emitted.  ``budget``: new
@@ -418,21 +448,6 @@ class SpecDecodeGraph:
         ops.spec_accept(targets.view(self.batch, Q), self.input_ids, self.n_out, self.budget, self.tokens, self.hist, self.hist_len,
                         self.adds, self.draw, self.accepted, self.steps, self.done)
 
-    def step(self):
-        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"SpecDecodeGraph: all {self.max_steps} steps are taken")
-        if self.steps_done == 0:
-            self._step()
-        else:
-            if self._graph is None:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
-                    self._step()
-                self._graph = graph
-            self._graph.replay()
-        self.steps_done += 1
-
     def commit(self):
         """After the last step: its accepted tokens become part of the sequences (``step_rows`` without look-ahead; the count is
         zeroed so that a second call commits nothing).  ``static_kv.sync_host()`` / ``close()`` then read prompt + tokens fed back."""
@@ -454,17 +469,42 @@ class SpecDecodeGraph:
         return self.tokens
 
 
-def _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams):
-    refused = [name for name, given in (("num_beams", num_beams is not None), ("logprobs", logprobs is not None),
-                                        ("return_logits", bool(return_logits)), ("caches", caches is not None)) if given]
-    if sampling is not None:
-        neutral = SamplingParams()
-        for q in ([sampling] if isinstance(sampling, SamplingParams) else sampling):
-            for field in ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"):
-                if isinstance(q, SamplingParams) and q.penalises and getattr(q, field) != getattr(neutral, field) and field not in refused:
-                    refused.append(field)
-    if refused:
-        raise ValueError(f"generate: speculative does not combine with {', '.join(refused)}")
+# What the features of ``generate`` refuse, in the order the checks fire and a message names them.  "penalties": the penalty fields of
+# ``SamplingParams`` that are set, in the order the prompts set them.  Of the two that ``guide`` refuses a message names the first.
+_UNGUIDED = "speculative unless it is SpeculativeParams(guided=True)"
+_REFUSES = (("guide", ("num_beams", _UNGUIDED)),
+            ("speculative", ("num_beams", "logprobs", "return_logits", "caches", "penalties")),
+            ("num_beams", ("sampling", "logprobs", "return_logits", "caches")))
+
+
+def _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide):
+    """Raises ``ValueError`` for the first entry of ``_REFUSES`` that applies (and for a drafter or statistics without ``speculative``)."""
+    named = {"guide": guide is not None, "speculative": speculative is not None, "num_beams": num_beams is not None,
+             "sampling": sampling is not None, "logprobs": logprobs is not None, "return_logits": bool(return_logits),
+             "caches": caches is not None, _UNGUIDED: speculative is not None and not speculative.guided}
+    named = {name: [name] * given for name, given in named.items()}          # what a message lists for each name: itself, if given
+    used, neutral = named.setdefault("penalties", []), SamplingParams()
+    for q in ([] if sampling is None else _params_list(sampling)):
+        for field in ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"):
+            if isinstance(q, SamplingParams) and q.penalises and getattr(q, field) != getattr(neutral, field) and field not in used:
+                used.append(field)
+    for feature, others in _REFUSES:
+        refused = [name for other in others for name in named[other]] if named[feature] else []
+        if refused:
+            raise ValueError(f"generate: {feature} does not combine with {', '.join(refused[:1] if feature == 'guide' else refused)}")
+        if feature == "speculative" and not named[feature] and (drafter is not None or return_spec_stats):
+            raise ValueError("generate: drafter and return_spec_stats need speculative")
+
+
+def _prefill(model, prompts: Sequence[Sequence[int]], seqs: Sequence[KvCacheInt4], device):
+    """The eager prefill of ``prompts`` into ``seqs`` (one cache each, acquired here; releasing them stays with the caller): one forward
+    over all of them.  Returns the logits fp16 [tokens, vocab] and the row of each prompt's last token (int64 [batch], on the host)."""
+    lens = [len(p) for p in prompts]
+    for c, n in zip(seqs, lens):
+        c.acquire(n)
+    ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=device)
+    logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
+    return logits, torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1)
 
 
 @torch.no_grad()
@@ -517,49 +557,26 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     ops.guide_mask over the ``batch * (K + 1)`` rows: two launches per step), a draft that follows a state with a
     single allowed token is replaced by that token (``force_drafts``), and what ``speculative`` refuses stays refused.
     ``guide=None`` is the code above, launch for launch, with nothing allocated."""
-    if guide is not None and (num_beams is not None or (speculative is not None and not speculative.guided)):
-        raise ValueError("generate: guide does not combine with " + (
-            "num_beams" if num_beams is not None else "speculative unless it is SpeculativeParams(guided=True)"))
-    if speculative is not None:
-        _refuse_with_speculative(caches, return_logits, sampling, logprobs, num_beams)
-    elif drafter is not None or return_spec_stats:
-        raise ValueError("generate: drafter and return_spec_stats need speculative")
+    _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide)
     if num_beams is not None:
-        refused = [name for name, given in (("sampling", sampling is not None), ("logprobs", logprobs is not None),
-                                            ("return_logits", bool(return_logits)), ("caches", caches is not None)) if given]
-        if refused:
-            raise ValueError(f"generate: num_beams does not combine with {', '.join(refused)}")
         return [hyps[0].tokens for hyps in beam_search(model, prompts, max_new_tokens, pool, num_beams, eos_token_id=eos_token_id)]
     n_lp = _check_logprobs(logprobs)
     assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
     device = pool.buf.device
     seqs = [KvCacheInt4(pool, 0) for _ in prompts] if caches is None else list(caches)
     assert len(seqs) == len(prompts)
-    lens = [len(p) for p in prompts]
-    for c, n in zip(seqs, lens):
-        c.acquire(n)
-    ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=device)
-    logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
-    last = torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1).to(device)
-    all_logits = logits.index_select(0, last).unsqueeze(0)
+    logits, last = _prefill(model, prompts, seqs, device)
+    all_logits = logits.index_select(0, last.to(device)).unsqueeze(0)
     sampler = None if sampling is None else Sampler(len(prompts), device, sampling)
     penalties = None
-    if sampler is not None and any(q.penalises for q in ([sampling] if isinstance(sampling, SamplingParams) else sampling)):
+    if sampler is not None and any(q.penalises for q in _params_list(sampling)):
         penalties = LogitPenalties(len(prompts), logits.size(-1), device, sampling)
         penalties.reset(prompts)
     guides = None
     if guide is not None and (isinstance(guide, TokenAutomaton) or any(g is not None for g in guide)):
         guides = LogitGuide(len(prompts), logits.size(-1), device, guide)
-    if guides is not None:                                     # the start states' allowed sets, after the penalties
-        row = all_logits[0] if penalties is None else penalties.apply(all_logits[0])
-        row = guides.mask(row, out=None if penalties is None else row)
-        new = (row.argmax(dim=-1) if sampler is None else sampler.sample(row)).unsqueeze(0)
-    elif sampler is None:
-        new = all_logits.argmax(dim=-1)                        # [1, batch]
-    elif penalties is None:
-        new = sampler.sample(all_logits[0]).unsqueeze(0)
-    else:                                                      # nothing is generated yet: the prompt flags alone
-        new = sampler.sample(penalties.apply(all_logits[0])).unsqueeze(0)
+    # draw 0; nothing is generated yet: the penalties see the prompt flags alone, the guide's mask is that of the start states
+    new = _choose_tokens(all_logits[0], sampler, penalties, guides).unsqueeze(0)     # [1, batch]
     lp = None if n_lp is None else [x if x is None else x.unsqueeze(0) for x in ops.logprob(all_logits[0], new[0], n_lp)]
     stats = None
     if speculative is not None:
@@ -641,9 +658,9 @@ def backtrack_beams(parents, tokens, cum, num_beams: int, eos_token_id=None, len
     return out
 
 
-class BeamDecodeGraph:
-    """One beam-search step over a ``StaticBeamKvCacheInt4``, run up to ``max_steps`` times, as ``DecodeGraph`` runs a decode step: the
-    first ``step()`` eager, the second captured, the rest replays; nothing reaches the host in between.  A step is ``kv.step()``, the
+class BeamDecodeGraph(_StepReplay):
+    """One beam-search step over a ``StaticBeamKvCacheInt4``, run up to ``max_steps`` times, as ``DecodeGraph`` runs a decode step
+    (``_StepReplay``: eager, captured, replayed; nothing reaches the host in between).  A step is ``kv.step()``, the
     model's forward on groups * num_beams rows, ``ops.logprob(top_n=num_beams)``, ``ops.beam_select`` (the beams' state ``cum`` float32 /
     ``finished`` int32 / ``length`` int32 [rows] is updated in place), the winners' ``parents`` int32 / ``tokens`` int64 recorded in row
     i of [max_steps, rows] at the device counter, ``kv.fork(parent)`` and the tokens written back as the next input.  The caller sets
@@ -651,7 +668,8 @@ class BeamDecodeGraph:
 
     def __init__(self, model, beam_kv: StaticBeamKvCacheInt4, max_steps: int, *, eos_token_id: int = None):
         assert max_steps >= 1
-        self.model, self.kv, self.max_steps = model, beam_kv, int(max_steps)
+        super().__init__(max_steps)
+        self.model, self.kv = model, beam_kv
         self.eos = -1 if eos_token_id is None else int(eos_token_id)
         device = beam_kv.data.device
         self.num_beams = W = beam_kv.num_beams
@@ -670,8 +688,6 @@ class BeamDecodeGraph:
                      torch.zeros((batch, W), dtype=torch.float32, device=device))
         self._counter = torch.zeros(1, dtype=torch.int64, device=device)
         self._blen = BatchLenInfo([], batch, device)
-        self._graph = None
-        self.steps_done = 0
 
     @torch.no_grad()
     def _step(self):
@@ -685,21 +701,6 @@ class BeamDecodeGraph:
         self.kv.fork(self._parent)
         self.input_ids.copy_(self._token)
         self._counter.add_(1)
-
-    def step(self):
-        """The next step: eager the first time, captured and replayed the second, replayed afterwards.  Asynchronous."""
-        if self.steps_done >= self.max_steps:
-            raise RuntimeError(f"BeamDecodeGraph: all {self.max_steps} steps are taken")
-        if self.steps_done == 0:
-            self._step()
-        else:
-            if self._graph is None:
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):              # a capture records the launches and runs none of them
-                    self._step()
-                self._graph = graph
-            self._graph.replay()
-        self.steps_done += 1
 
     def run(self, first_tokens: torch.Tensor, cum: torch.Tensor, finished: torch.Tensor, length: torch.Tensor):
         """Feed the winners of the step after the prefill ([rows] each) and take every step that is left; returns ``(parents, tokens)``."""
@@ -733,17 +734,12 @@ def beam_search(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, po
         raise ValueError(f"num_return must be 1 .. num_beams, got {num_return}")
     assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
     device, G = pool.buf.device, len(prompts)
-    lens = [len(p) for p in prompts]
     seqs = [KvCacheInt4(pool, 0) for _ in prompts]
     try:
-        for c, n in zip(seqs, lens):
-            c.acquire(n)
-        ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=device)
-        logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
+        logits, last = _prefill(model, prompts, seqs, device)
         if W > logits.size(-1):
             raise ValueError(f"{W} beams over a vocabulary of {logits.size(-1)}")
-        last = torch.tensor(lens, dtype=torch.int64).cumsum(0).sub_(1).to(device)
-        _, _, top_ids, top_lp = ops.logprob(logits.index_select(0, last), None, W)
+        _, _, top_ids, top_lp = ops.logprob(logits.index_select(0, last.to(device)), None, W)
         zi = torch.zeros(G, dtype=torch.int32, device=device)
         parent, token, cum, finished, length = ops.beam_select(top_ids, top_lp, torch.zeros(G, dtype=torch.float32, device=device), zi, zi,
                                                                eos_token_id, W, w_in=1)
@@ -777,10 +773,7 @@ def score(model, sequences: Sequence[Sequence[int]], pool: KvPoolInt4, *, top_n:
     lens = [len(s) for s in sequences]
     seqs = [KvCacheInt4(pool, 0) for _ in sequences]
     try:
-        for c, n in zip(seqs, lens):
-            c.acquire(n)
-        ids = torch.tensor([t for s in sequences for t in s], dtype=torch.int64, device=device)
-        logits, _ = model(ids, BatchLenInfo(lens, 0, device), BatchedKvCacheInt4(seqs), None)
+        logits, _ = _prefill(model, sequences, seqs, device)
         targets = torch.tensor([t for s in sequences for t in list(s[1:]) + [-1]], dtype=torch.int64, device=device)
         got = ops.logprob(logits, targets, top_n)
     finally:

@@ -1034,6 +1034,32 @@ def kv_quant_u4(k: torch.Tensor):
     return packed, params
 
 
+# ------------------------------------------------------------------------------------------------ vocabulary rows
+def _row_stride(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
+
+
+def _logits_rows(logits: torch.Tensor, op_has: str, rows: str = "batch"):
+    """The ``logits`` argument of sample, logprob, penalize and guide_mask: fp16 [rows, vocab] with contiguous rows on the GPU.
+    Returns (rows, vocab, row stride)."""
+    if not logits.is_cuda:
+        raise L.AtomHipError(f"logits must live on the GPU: {op_has} no CPU fallback")
+    if logits.dtype != torch.float16:
+        raise TypeError(f"logits must be float16, got {logits.dtype}")
+    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [{rows}, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
+    return logits.size(0), logits.size(1), _row_stride(logits)
+
+
+def _require_dev(ops_name, name, t, dtype, shape=None):
+    """``t`` on the GPU, contiguous, of ``dtype`` (and ``shape``); ``ops_name``: the op family the message names"""
+    if not t.is_cuda:
+        raise L.AtomHipError(f"{name} must live on the GPU: the {ops_name} ops have no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise TypeError(f"{name} must be a contiguous {dtype} tensor{'' if shape is None else ' of ' + str(list(shape))}, "
+                        f"got {t.dtype} {tuple(t.shape)}")
+
+
 # ------------------------------------------------------------------------------------------------ sampling
 _SAMPLE_PARAMS = (("temperature", torch.float32), ("top_k", torch.int32), ("top_p", torch.float32), ("seeds", torch.int64))
 
@@ -1051,14 +1077,7 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor = None, top_k: torch.
     ``rows_per_seq`` (the verify rows of speculative decoding, ``atom_sample_rows_f16``): the rows are ``batch / rows_per_seq``
     sequences of that many consecutive rows, ``step`` is int64 ``[batch / rows_per_seq]`` and row r draws number
     ``step[r // rows_per_seq] + r % rows_per_seq + step_offset``; the four parameter tensors stay per ROW."""
-    if not logits.is_cuda:
-        raise L.AtomHipError("logits must live on the GPU: the sampler has no CPU fallback")
-    if logits.dtype != torch.float16:
-        raise TypeError(f"logits must be float16, got {logits.dtype}")
-    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
-    batch, vocab = logits.shape
-    ld = logits.stride(0) if batch > 1 else max(logits.stride(0), vocab)
+    batch, vocab, ld = _logits_rows(logits, "the sampler has")
     given = dict(temperature=temperature, top_k=top_k, top_p=top_p, seeds=seeds)
     for name, dtype in _SAMPLE_PARAMS:
         t = given[name]
@@ -1101,14 +1120,7 @@ def logprob(logits: torch.Tensor, targets: torch.Tensor = None, top_n: int = 0, 
     int64 and float32 [rows, top_n]; None for what was not asked (no ``targets``: the first two; ``top_n = 0``: the last two).  A
     target outside 0 .. vocab - 1 is ignored: log-probability 0, rank -1.  ``out``: a tuple of four preallocated buffers (None where
     nothing is asked) for capture.  One launch; nothing is read back, nothing synchronises."""
-    if not logits.is_cuda:
-        raise L.AtomHipError("logits must live on the GPU: the log-probability op has no CPU fallback")
-    if logits.dtype != torch.float16:
-        raise TypeError(f"logits must be float16, got {logits.dtype}")
-    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [rows, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
-    rows, vocab = logits.shape
-    ld = logits.stride(0) if rows > 1 else max(logits.stride(0), vocab)
+    rows, vocab, ld = _logits_rows(logits, "the log-probability op has", rows="rows")
     top_n = int(top_n)
     if not 0 <= top_n <= LOGPROB_MAX_TOP:
         raise ValueError(f"top_n must be 0 .. {LOGPROB_MAX_TOP}, got {top_n}")
@@ -1141,10 +1153,6 @@ PENALTY_MAX_BIAS = 512
 PENALTY_TILE = 2048            # elements per workgroup of atom_penalize_f16 (csrc/penalize.hip kPenTile)
 
 
-def _row_stride(t: torch.Tensor) -> int:
-    return t.stride(0) if t.size(0) > 1 else max(t.stride(0), t.size(1))
-
-
 def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor = None, repetition: torch.Tensor = None,
              presence: torch.Tensor = None, frequency: torch.Tensor = None, bias_ids: torch.Tensor = None,
              bias_vals: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
@@ -1157,13 +1165,7 @@ def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor
     reads (a captured call follows buffers changed in place); None: no state, nothing fed, neutral, no bias.  Rows whose parameters
     change nothing and elements that are neither seen nor biased are copied bit for bit.  Returns fp16 [batch, vocab] (``out`` if
     given; ``out`` may be ``logits``).  One launch; nothing is read back, nothing synchronises."""
-    if not logits.is_cuda:
-        raise L.AtomHipError("logits must live on the GPU: the penalty op has no CPU fallback")
-    if logits.dtype != torch.float16:
-        raise TypeError(f"logits must be float16, got {logits.dtype}")
-    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
-    batch, vocab = logits.shape
+    batch, vocab, ld = _logits_rows(logits, "the penalty op has")
     for name, t in (("repetition", repetition), ("presence", presence), ("frequency", frequency)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == (batch,) and t.is_contiguous()):
             raise TypeError(f"{name} must be a contiguous float32 tensor of [{batch}] on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
@@ -1193,7 +1195,7 @@ def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor
         out = torch.empty((batch, vocab), dtype=torch.float16, device=logits.device)
     elif not (out.is_cuda and out.dtype == torch.float16 and out.shape == (batch, vocab) and (vocab == 1 or out.stride(1) == 1)):
         raise TypeError(f"out must be a float16 tensor of [{batch}, {vocab}] with contiguous rows on the GPU")
-    st = L.lib().atom_penalize_f16(logits.data_ptr(), _row_stride(logits), batch, vocab, L.ptr(state), state_ld, L.ptr(fed),
+    st = L.lib().atom_penalize_f16(logits.data_ptr(), ld, batch, vocab, L.ptr(state), state_ld, L.ptr(fed),
                                    L.ptr(repetition), L.ptr(presence), L.ptr(frequency), L.ptr(bias_ids) if max_bias else None,
                                    L.ptr(bias_vals) if max_bias else None, max_bias, out.data_ptr(), _row_stride(out),
                                    L.current_stream(logits.device))
@@ -1281,13 +1283,6 @@ SPEC_MAX_DRAFT = 8
 SPEC_MAX_NGRAM = 8
 
 
-def _require_spec(name, t, dtype, shape):
-    if not t.is_cuda:
-        raise L.AtomHipError(f"{name} must live on the GPU: the speculative-decoding ops have no CPU fallback")
-    if not (t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise TypeError(f"{name} must be a contiguous {dtype} tensor of {list(shape)}, got {t.dtype} {tuple(t.shape)}")
-
-
 def spec_draft_ngram(hist: torch.Tensor, hist_len: torch.Tensor, out: torch.Tensor, *, ngram_max: int = 3, ngram_min: int = 1):
     """NEW: K draft tokens per sequence by n-gram lookup in the sequence's own history -- ``atom_spec_draft_ngram``, the contract of
     DESIGN.md 4.17.  ``hist`` int32 [batch, hist_cap] holds the prompt and every emitted token, ``hist_len`` int32 [batch] how many;
@@ -1301,7 +1296,7 @@ def spec_draft_ngram(hist: torch.Tensor, hist_len: torch.Tensor, out: torch.Tens
     if hist.dtype != torch.int32 or hist.dim() != 2 or hist.size(0) < 1 or hist.size(1) < 1 or not hist.is_contiguous():
         raise TypeError(f"hist must be a contiguous int32 tensor of [batch, hist_cap], got {hist.dtype} {tuple(hist.shape)}")
     batch, hist_cap = hist.shape
-    _require_spec("hist_len", hist_len, torch.int32, (batch,))
+    _require_dev("speculative-decoding", "hist_len", hist_len, torch.int32, (batch,))
     if out.dtype != torch.int64 or out.dim() != 2 or out.size(0) != batch or (out.size(1) > 1 and out.stride(1) != 1):
         raise TypeError(f"out must be an int64 tensor of [{batch}, K] with contiguous rows, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
     K = out.size(1)
@@ -1336,16 +1331,16 @@ def spec_accept(targets: torch.Tensor, input_ids: torch.Tensor, n_out: torch.Ten
     batch, Q = targets.shape
     if not 1 <= Q - 1 <= SPEC_MAX_DRAFT:
         raise ValueError(f"K (targets' columns - 1) must be 1 .. {SPEC_MAX_DRAFT}, got {Q - 1}")
-    _require_spec("input_ids", input_ids, torch.int64, (batch, Q))
+    _require_dev("speculative-decoding", "input_ids", input_ids, torch.int64, (batch, Q))
     for name, t in (("tokens", tokens), ("hist", hist)):
         if t.dim() != 2 or t.size(1) < 1:
             raise TypeError(f"{name} must be [batch, n], got {tuple(t.shape)}")
-    _require_spec("tokens", tokens, torch.int64, (batch, tokens.size(1)))
-    _require_spec("hist", hist, torch.int32, (batch, hist.size(1)))
+    _require_dev("speculative-decoding", "tokens", tokens, torch.int64, (batch, tokens.size(1)))
+    _require_dev("speculative-decoding", "hist", hist, torch.int32, (batch, hist.size(1)))
     for name, t in (("n_out", n_out), ("budget", budget), ("hist_len", hist_len), ("adds", adds), ("accepted", accepted), ("steps", steps)):
-        _require_spec(name, t, torch.int32, (batch,))
-    _require_spec("draw", draw, torch.int64, (batch,))
-    _require_spec("done", done, torch.int32, (1,))
+        _require_dev("speculative-decoding", name, t, torch.int32, (batch,))
+    _require_dev("speculative-decoding", "draw", draw, torch.int64, (batch,))
+    _require_dev("speculative-decoding", "done", done, torch.int32, (1,))
     st = L.lib().atom_spec_accept(targets.data_ptr(), input_ids.data_ptr(), n_out.data_ptr(), budget.data_ptr(), tokens.data_ptr(),
                                   hist.data_ptr(), hist_len.data_ptr(), adds.data_ptr(), draw.data_ptr(), accepted.data_ptr(),
                                   steps.data_ptr(), done.data_ptr(), batch, Q - 1, tokens.size(1), hist.size(1),
@@ -1359,14 +1354,6 @@ GUIDE_REJECTED, GUIDE_BAD_STATE = L.GUIDE_REJECTED, L.GUIDE_BAD_STATE
 GUIDE_TILE = 2048              # elements per workgroup of atom_guide_mask_f16 (csrc/guide.hip kGuideTile)
 
 
-def _require_guide(name, t, dtype, shape=None):
-    if not t.is_cuda:
-        raise L.AtomHipError(f"{name} must live on the GPU: the guide ops have no CPU fallback")
-    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise TypeError(f"{name} must be a contiguous {dtype} tensor{'' if shape is None else ' of ' + str(list(shape))}, "
-                        f"got {t.dtype} {tuple(t.shape)}")
-
-
 def guide_mask(logits: torch.Tensor, state: torch.Tensor, mask: torch.Tensor, out: torch.Tensor = None,
                status: torch.Tensor = None) -> torch.Tensor:
     """NEW: the allowed set of every row's automaton state applied to ``logits`` (fp16 [batch, vocab], rows ``stride(0) >= vocab``
@@ -1377,25 +1364,19 @@ def guide_mask(logits: torch.Tensor, state: torch.Tensor, mask: torch.Tensor, ou
     [1]; None: a word of its own that nobody reads).  All DEVICE tensors that the launch reads (a captured call follows buffers
     changed in place).  Returns fp16 [batch, vocab] (``out`` if given; ``out`` may be ``logits``).  One launch; nothing is read back,
     nothing synchronises."""
-    if not logits.is_cuda:
-        raise L.AtomHipError("logits must live on the GPU: the guide ops have no CPU fallback")
-    if logits.dtype != torch.float16:
-        raise TypeError(f"logits must be float16, got {logits.dtype}")
-    if logits.dim() != 2 or logits.size(0) < 1 or logits.size(1) < 1 or (logits.size(1) > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [batch, vocab] with contiguous rows, got {tuple(logits.shape)} strides {logits.stride()}")
-    batch, vocab = logits.shape
-    _require_guide("state", state, torch.int32, (batch,))
+    batch, vocab, ld = _logits_rows(logits, "the guide ops have")
+    _require_dev("guide", "state", state, torch.int32, (batch,))
     if not (mask.is_cuda and mask.dtype == torch.int32 and mask.dim() == 2 and mask.size(0) >= 1 and 32 * mask.size(1) >= vocab
             and (mask.size(1) == 1 or mask.stride(1) == 1)):
         raise TypeError(f"mask must be an int32 tensor of [num_states, >= {-(-vocab // 32)}] with contiguous rows on the GPU")
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    _require_guide("status", status, torch.int32, (1,))
+    _require_dev("guide", "status", status, torch.int32, (1,))
     if out is None:
         out = torch.empty((batch, vocab), dtype=torch.float16, device=logits.device)
     elif not (out.is_cuda and out.dtype == torch.float16 and out.shape == (batch, vocab) and (vocab == 1 or out.stride(1) == 1)):
         raise TypeError(f"out must be a float16 tensor of [{batch}, {vocab}] with contiguous rows on the GPU")
-    st = L.lib().atom_guide_mask_f16(logits.data_ptr(), _row_stride(logits), batch, vocab, state.data_ptr(), mask.data_ptr(),
+    st = L.lib().atom_guide_mask_f16(logits.data_ptr(), ld, batch, vocab, state.data_ptr(), mask.data_ptr(),
                                      _row_stride(mask), mask.size(0), out.data_ptr(), _row_stride(out), status.data_ptr(),
                                      L.current_stream(logits.device))
     L.check(st, "atom_guide_mask_f16")
@@ -1415,16 +1396,16 @@ def guide_advance(state: torch.Tensor, tokens: torch.Tensor, indptr: torch.Tenso
     if state.dim() != 1 or state.numel() < 1:
         raise ValueError(f"state must be [batch], got {tuple(state.shape)}")
     batch = state.numel()
-    _require_guide("state", state, torch.int32, (batch,))
-    _require_guide("tokens", tokens, torch.int64, (batch,))
+    _require_dev("guide", "state", state, torch.int32, (batch,))
+    _require_dev("guide", "tokens", tokens, torch.int64, (batch,))
     if indptr.dim() != 1 or indptr.numel() < 2 or edge_tok.dim() != 1:
         raise ValueError(f"indptr must be [num_states + 1] and edge_tok [num_edges], got {tuple(indptr.shape)}, {tuple(edge_tok.shape)}")
-    _require_guide("indptr", indptr, torch.int32)
-    _require_guide("edge_tok", edge_tok, torch.int32)
-    _require_guide("edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
+    _require_dev("guide", "indptr", indptr, torch.int32)
+    _require_dev("guide", "edge_tok", edge_tok, torch.int32)
+    _require_dev("guide", "edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=state.device)
-    _require_guide("status", status, torch.int32, (1,))
+    _require_dev("guide", "status", status, torch.int32, (1,))
     num_edges = edge_tok.numel()
     st = L.lib().atom_guide_advance(state.data_ptr(), tokens.data_ptr(), batch, indptr.data_ptr(),
                                     edge_tok.data_ptr() if num_edges else None, edge_next.data_ptr() if num_edges else None,
@@ -1451,9 +1432,9 @@ def guide_walk_rows(state: torch.Tensor, adds: torch.Tensor, row_state: torch.Te
     if state.dim() != 1 or state.numel() < 1 or row_state.dim() != 2 or not 1 <= row_state.size(1) <= GUIDE_MAX_ROWS:
         raise ValueError(f"state must be [batch] and row_state [batch, 1 .. {GUIDE_MAX_ROWS}], got {tuple(state.shape)}, {tuple(row_state.shape)}")
     batch, Q = state.numel(), row_state.size(1)
-    _require_guide("state", state, torch.int32, (batch,))
-    _require_guide("adds", adds, torch.int32, (batch,))
-    _require_guide("row_state", row_state, torch.int32, (batch, Q))
+    _require_dev("guide", "state", state, torch.int32, (batch,))
+    _require_dev("guide", "adds", adds, torch.int32, (batch,))
+    _require_dev("guide", "row_state", row_state, torch.int32, (batch, Q))
     ids_ld = Q
     if input_ids is not None:
         if not (input_ids.is_cuda and input_ids.dtype == torch.int64 and tuple(input_ids.shape) == (batch, Q)
@@ -1462,12 +1443,12 @@ def guide_walk_rows(state: torch.Tensor, adds: torch.Tensor, row_state: torch.Te
         ids_ld = _row_stride(input_ids)
     if indptr.dim() != 1 or indptr.numel() < 2 or edge_tok.dim() != 1:
         raise ValueError(f"indptr must be [num_states + 1] and edge_tok [num_edges], got {tuple(indptr.shape)}, {tuple(edge_tok.shape)}")
-    _require_guide("indptr", indptr, torch.int32)
-    _require_guide("edge_tok", edge_tok, torch.int32)
-    _require_guide("edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
+    _require_dev("guide", "indptr", indptr, torch.int32)
+    _require_dev("guide", "edge_tok", edge_tok, torch.int32)
+    _require_dev("guide", "edge_next", edge_next, torch.int32, tuple(edge_tok.shape))
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=state.device)
-    _require_guide("status", status, torch.int32, (1,))
+    _require_dev("guide", "status", status, torch.int32, (1,))
     num_edges = edge_tok.numel()
     st = L.lib().atom_guide_walk_rows(state.data_ptr(), adds.data_ptr(), row_state.data_ptr(),
                                       None if input_ids is None else input_ids.data_ptr(), ids_ld, batch, Q, indptr.data_ptr(),
