@@ -103,6 +103,7 @@ SIGNATURES = {
     "atom_sample_f16": (_int, [_vp, _i64, _i64, _i64] + [_vp] * 5 + [_i64, _vp, _vp]),
     "atom_logprob_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "atom_penalize_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _i64, _vp]),
+    "atom_penalize_rows_f16": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64, _vp, _i64, _vp]),
     "atom_beam_select": (_int, [_vp] * 5 + [_i64, _int, _int, _int, _i64] + [_vp] * 6),
     "atom_kv_beam_fork_i4": (_int, [_vp] * 10 + [_int, _int, _int, _i64] + [_int] * 4 + [_vp]),
     "atom_kv_step_rows_i4": (_int, [_vp] * 7 + [_int] * 3 + [_vp, _int, _vp]),

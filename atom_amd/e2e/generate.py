@@ -14,6 +14,8 @@ DESIGN.md 4.17).
 the state its own output has led to: ops.guide_advance and ops.guide_mask, two more launches of the replayed step.
 ``SpecDecodeGraph(guide=)`` / ``generate(guide=, speculative=SpeculativeParams(guided=True))`` do both at once: ops.guide_walk_rows gives
 every verify row a state of its own and writes the drafts a state forces, ops.guide_mask masks the batch * (K + 1) rows.
+``SpecDecodeGraph(penalties=)`` / ``generate(sampling=, speculative=SpeculativeParams(penalised=True))`` penalise every verify row as if
+the drafts in front of it had been emitted and count what a step emitted on the device: ops.penalize_rows, one launch.
 """
 from __future__ import annotations
 
@@ -169,6 +171,20 @@ class LogitPenalties:
         return ops.penalize(logits, self.state, fed, self.repetition, self.presence, self.frequency,
                             self.bias_ids if has_bias else None, self.bias_vals if has_bias else None, out=out)
 
+    def apply_rows(self, logits: torch.Tensor, input_ids: torch.Tensor, commit_tokens: torch.Tensor, commit_counts: torch.Tensor,
+                   out: torch.Tensor = None) -> torch.Tensor:
+        """The verify rows ``logits`` fp16 [batch * Q, vocab] of a speculative step penalised (ops.penalize_rows, one launch): the
+        first ``commit_counts[b]`` of ``commit_tokens[b]`` are counted into ``state`` first, row j of a sequence then sees the drafts
+        ``input_ids[b, 1 .. j]`` counted as well; the drafts leave ``state`` as it is."""
+        has_bias = self.max_bias > 0
+        return ops.penalize_rows(logits, self.state, input_ids, commit_tokens, commit_counts, self.repetition, self.presence,
+                                 self.frequency, self.bias_ids if has_bias else None, self.bias_vals if has_bias else None, out=out)
+
+    def commit(self, tokens: torch.Tensor, counts: torch.Tensor):
+        """Counts the first ``counts[b]`` (int32 [batch]) of ``tokens[b]`` (int64 [batch, n]) into ``state`` and does nothing else
+        (ops.penalize_rows without logits, one launch)."""
+        ops.penalize_rows(None, self.state[:, :self.vocab], None, tokens, counts)
+
 
 def _as_sampler(sampler, batch: int, device):
     """None, a ``Sampler`` of ``batch`` rows, or one built from ``SamplingParams`` (one, or one per sequence)"""
@@ -315,15 +331,22 @@ class SpeculativeParams:
     emits 1 .. K + 1 tokens.  The shipped drafter looks the sequence's last ``ngram_max`` .. ``ngram_min`` tokens (1 .. 8) up in its own
     history.  ``poll_every``: the loop reads its 4-byte ``done`` word every so many steps -- its only synchronisation.
     ``guided=True`` lets ``generate`` take ``speculative`` together with ``guide`` (DESIGN.md 4.19; without a guide it changes nothing);
-    ``force_drafts`` then overwrites a draft that follows an automaton state with a single allowed token by that token."""
+    ``force_drafts`` then overwrites a draft that follows an automaton state with a single allowed token by that token.
+    ``penalised=True`` lets ``generate`` take ``speculative`` together with the penalty fields of ``SamplingParams`` (DESIGN.md 4.20;
+    without such a field it changes nothing): every verify row is penalised as if the drafts in front of it had been emitted.
+    ``penalised`` is the last argument of the constructor and an attribute that ``==``, ``hash`` and ``repr`` include, but an init-only
+    one: the six fields above, their order and ``dataclasses.astuple`` are what callers of earlier versions unpack, and stay as they
+    were (``dataclasses.replace`` therefore wants ``penalised=`` passed again)."""
     num_draft_tokens: int = 4
     ngram_max: int = 3
     ngram_min: int = 1
     poll_every: int = 8
     guided: bool = False
     force_drafts: bool = True
+    penalised: dataclasses.InitVar[bool] = False
 
-    def __post_init__(self):
+    def __post_init__(self, penalised=False):
+        object.__setattr__(self, "penalised", bool(penalised))                # frozen: the one attribute that is not a field
         if not 1 <= int(self.num_draft_tokens) <= ops.SPEC_MAX_DRAFT:
             raise ValueError(f"num_draft_tokens must be 1 .. {ops.SPEC_MAX_DRAFT}, got {self.num_draft_tokens}")
         if not 1 <= int(self.ngram_min) <= int(self.ngram_max) <= ops.SPEC_MAX_NGRAM:
@@ -331,6 +354,18 @@ class SpeculativeParams:
                              f"got {self.ngram_min} .. {self.ngram_max}")
         if int(self.poll_every) < 1:
             raise ValueError(f"poll_every must be positive, got {self.poll_every}")
+
+    def _key(self):
+        return dataclasses.astuple(self) + (self.penalised,)
+
+    def __eq__(self, other):
+        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}({', '.join(f'{f.name}={getattr(self, f.name)!r}' for f in dataclasses.fields(self))}, penalised={self.penalised!r})"
 
 
 @dataclasses.dataclass(frozen=True)
@@ -372,10 +407,16 @@ class SpecDecodeGraph(_StepReplay):
     launch for launch, with nothing allocated.  Otherwise ``guide.walk_rows`` runs between 2 and 3 -- the last step's ``adds`` committed
     into ``guide.state``, the automaton state behind every row, and with ``params.force_drafts`` the drafts a state forces written over
     the drafter's -- and ``guide.mask_rows`` between 3 and 4 masks the ``batch * Q`` rows, each with its own state, into the static
-    buffer ``guided``, which the argmax or ops.sample reads; ``commit()`` also commits the last step's states."""
+    buffer ``guided``, which the argmax or ops.sample reads; ``commit()`` also commits the last step's states.
+    ``penalties`` (a ``LogitPenalties`` whose ``state`` holds the prompt flags alone; needs a sampler): None is the step
+    above, launch for launch, with nothing allocated.  Otherwise ``start`` counts the first tokens, and ``penalties.apply_rows`` runs
+    between 3 and 4 (ops.penalize_rows, one launch): the tokens the last step emitted -- the first ``adds`` of its ``_targets`` -- are
+    counted into ``penalties.state``, then row j is penalised with drafts 1 .. j counted on top, into the static buffer ``penalised``;
+    the guide's mask, if any, then runs in place there (no ``guided`` buffer), and ops.sample reads it.  ``commit()`` also counts the
+    last step's tokens."""
 
     def __init__(self, model, static_kv: StaticBatchedKvCacheInt4, max_new: int, *, params: SpeculativeParams = SpeculativeParams(),
-                 drafter=None, sampler=None, guide: LogitGuide = None):
+                 drafter=None, sampler=None, guide: LogitGuide = None, penalties: LogitPenalties = None):
         assert max_new >= 2
         super().__init__(int(max_new) - 1)                     # every step emits a token for every unfinished row: the all-rejected bound
         self.model, self.kv, self.max_new, self.params = model, static_kv, int(max_new), params
@@ -400,11 +441,18 @@ class SpecDecodeGraph(_StepReplay):
         if self.sampler is not None:
             s = self.sampler
             self._sample_rows = tuple(t.repeat_interleave(Q) for t in (s.temperature, s.top_k, s.top_p, s.seeds))
+        self.penalties, self.penalised = penalties, None
+        if penalties is not None:
+            if self.sampler is None:
+                raise ValueError("SpecDecodeGraph: penalties need a sampler (temperature = 0 is greedy over the penalised row)")
+            assert penalties.batch == batch and penalties.vocab == model.config.vocab_size
+            self.penalised = _static_rows(batch * Q, penalties.vocab, device)
         self.guide, self.guided = guide, None
         if guide is not None:
             assert guide.batch == batch and guide.vocab == model.config.vocab_size
             guide.rows(Q)
-            self.guided = _static_rows(batch * Q, guide.vocab, device)
+            if penalties is None:
+                self.guided = _static_rows(batch * Q, guide.vocab, device)
 
     def start(self, prompts: Sequence[Sequence[int]], first_tokens: torch.Tensor, budget: Sequence[int] = None):
         """The state after the prefill: ``hist`` = each prompt and its first new token (draw 0), one token emitted.  ``budget``: new
@@ -430,6 +478,9 @@ class SpecDecodeGraph(_StepReplay):
         self.budget.copy_(torch.tensor(budget, dtype=torch.int32))
         for t in (self.adds, self.accepted, self.steps, self.done):
             t.zero_()
+        if self.penalties is not None:                     # the first tokens are counted here; the first step commits nothing more
+            self.penalties.commit(first.unsqueeze(1), torch.ones_like(self.adds))
+            self._targets.zero_()
 
     @torch.no_grad()
     def _step(self):
@@ -439,8 +490,10 @@ class SpecDecodeGraph(_StepReplay):
         if self.guide is not None:                         # last step's commit, every row's state, the forced drafts: one launch
             self.guide.walk_rows(self.adds, self.input_ids, force=bool(self.params.force_drafts))
         logits, _ = self.model(self.input_ids.view(-1), self._blen, self.kv, None)
+        if self.penalties is not None:                     # the last step's tokens counted, every row under its own drafts: one launch
+            logits = self.penalties.apply_rows(logits, self.input_ids, self._targets.view(self.batch, Q), self.adds, out=self.penalised)
         if self.guide is not None:                         # every row masked with its own state: one launch
-            logits = self.guide.mask_rows(logits, out=self.guided)
+            logits = self.guide.mask_rows(logits, out=self.guided if self.penalties is None else logits)
         if self.sampler is None:
             targets = logits.argmax(dim=-1)
         else:
@@ -454,6 +507,8 @@ class SpecDecodeGraph(_StepReplay):
         self.kv.step_rows(self.adds, lookahead=0)
         if self.guide is not None:                         # the last step's accepted tokens move the committed automaton states
             self.guide.walk_rows(self.adds, None)
+        if self.penalties is not None:                     # and the counts of the penalty state
+            self.penalties.commit(self._targets.view(self.batch, self.Q), self.adds)
         self.adds.zero_()
 
     def run(self) -> torch.Tensor:
@@ -470,10 +525,12 @@ class SpecDecodeGraph(_StepReplay):
 
 
 # What the features of ``generate`` refuse, in the order the checks fire and a message names them.  "penalties": the penalty fields of
-# ``SamplingParams`` that are set, in the order the prompts set them.  Of the two that ``guide`` refuses a message names the first.
+# ``SamplingParams`` that are set, in the order the prompts set them (none of them under ``SpeculativeParams(penalised=True)``).  Of the
+# two that ``guide`` refuses a message names the first.
 _UNGUIDED = "speculative unless it is SpeculativeParams(guided=True)"
+_UNPENALISED = "penalties unless it is SpeculativeParams(penalised=True)"     # a message lists the fields themselves, as "penalties" does
 _REFUSES = (("guide", ("num_beams", _UNGUIDED)),
-            ("speculative", ("num_beams", "logprobs", "return_logits", "caches", "penalties")),
+            ("speculative", ("num_beams", "logprobs", "return_logits", "caches", _UNPENALISED)),
             ("num_beams", ("sampling", "logprobs", "return_logits", "caches")))
 
 
@@ -488,6 +545,7 @@ def _check_combination(caches, return_logits, sampling, logprobs, num_beams, spe
         for field in ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias"):
             if isinstance(q, SamplingParams) and q.penalises and getattr(q, field) != getattr(neutral, field) and field not in used:
                 used.append(field)
+    named[_UNPENALISED] = [] if speculative is not None and speculative.penalised else used
     for feature, others in _REFUSES:
         refused = [name for other in others for name in named[other]] if named[feature] else []
         if refused:
@@ -542,8 +600,11 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     ``max_new_tokens - 1`` tokens fed back, and every step -- those a finished sequence idles through included -- addresses K + 1
     tentative slots behind the committed ones, so ``prompt + max_new_tokens - 1 + K + 1`` is the furthest slot and the cache's overflow
     bit is never set by a correct run.  ``return_spec_stats=True`` appends a ``SpecStats`` (per sequence: drafts accepted, steps).
-    Out of scope with it, refused with ``ValueError``: ``num_beams``, ``logprobs``, ``return_logits``, ``caches`` and the penalty fields
-    of ``SamplingParams`` (their state is defined token by token); stopping at EOS stays a host-side cut.
+    Out of scope with it, refused with ``ValueError``: ``num_beams``, ``logprobs``, ``return_logits``, ``caches`` and, unless it is
+    ``SpeculativeParams(penalised=True)``, the penalty fields of ``SamplingParams``; stopping at EOS stays a host-side cut.  With
+    ``penalised=True`` every verify row is penalised as if the drafts in front of it had been emitted (ops.penalize_rows, one launch per
+    step, which also counts the tokens the step before emitted): row j sees the state non-speculative decoding has at
+    that position, rejected drafts leave no trace.  It combines with ``guided=True``: penalties first, then the mask.
     ``speculative=None`` is the code above, launch for launch.
     ``guide`` (one ``TokenAutomaton`` for every prompt, or a list with one automaton or None per prompt): guided decoding -- every new
     token of a guided prompt is one its automaton allows in the state its earlier new tokens led to (the prompt is not walked).  The
@@ -585,7 +646,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
             static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens + int(speculative.num_draft_tokens))
             try:
                 sg = SpecDecodeGraph(model, static, max_new_tokens, params=speculative, drafter=drafter, sampler=sampler,
-                                     guide=guides)
+                                     guide=guides, penalties=penalties if speculative.penalised else None)
                 sg.start(prompts, new[0])
                 toks, counts = sg.run().tolist(), sg.n_out.tolist()
                 rows = [row[:n] for row, n in zip(toks, counts)]

@@ -1203,6 +1203,82 @@ def penalize(logits: torch.Tensor, state: torch.Tensor = None, fed: torch.Tensor
     return out
 
 
+PENALTY_MAX_ROWS = 9           # the verify rows per sequence atom_penalize_rows_f16 takes (csrc/penalize.hip kPenMaxRows)
+
+
+def penalize_rows(logits: torch.Tensor, state: torch.Tensor, input_ids: torch.Tensor = None, commit_tokens: torch.Tensor = None,
+                  commit_counts: torch.Tensor = None, repetition: torch.Tensor = None, presence: torch.Tensor = None,
+                  frequency: torch.Tensor = None, bias_ids: torch.Tensor = None, bias_vals: torch.Tensor = None,
+                  out: torch.Tensor = None) -> torch.Tensor:
+    """NEW: ``ops.penalize`` for the verify rows of speculative decoding -- ``atom_penalize_rows_f16``, the contract of DESIGN.md 4.20.
+    ``logits`` fp16 [batch * rows, vocab] holds ``rows = input_ids.size(1)`` (1 .. 9) consecutive rows per sequence, ``state`` int16
+    [batch, >= vocab] one row per SEQUENCE.  The launch first counts the pending tokens ``commit_tokens[b, :commit_counts[b]]`` (int64
+    [batch, n] with contiguous rows, int32 [batch]; the count is clamped to 0 .. min(n, 9), a token outside 0 .. vocab - 1 counts nothing)
+    into ``state`` -- the tokens the step before emitted -- and then penalises row j of sequence b as ``ops.penalize`` would under
+    that state with the drafts ``input_ids[b, 1 .. j]`` (int64 [batch, rows] with contiguous rows) counted as well.  Column 0, the last
+    emitted token, is not counted here, and drafts never reach ``state``.  ``repetition``, ``presence``, ``frequency`` float32 [batch] and
+    ``bias_ids`` / ``bias_vals`` [batch, max_bias] are per sequence.  All DEVICE tensors that the launch reads (a captured call follows
+    buffers changed in place).  ``logits=None`` (then ``out`` and ``input_ids`` are None too) counts the pending tokens and does nothing
+    else -- the vocabulary is then ``state.size(1)`` -- and returns None.  Otherwise returns fp16 [batch * rows, vocab] (``out`` if given; ``out`` may be ``logits``).  One launch;
+    nothing is read back, nothing synchronises."""
+    if state is None or not (state.is_cuda and state.dtype == torch.int16 and state.dim() == 2 and state.size(0) >= 1
+                             and (state.size(1) == 1 or state.stride(1) == 1)):
+        raise TypeError("state must be an int16 tensor of [batch, >= vocab] with contiguous rows on the GPU")
+    batch, state_ld = state.size(0), _row_stride(state)
+    rows, vocab, ld, ids_ld = 1, state.size(1), 0, 0
+    if logits is None:
+        if out is not None or input_ids is not None:
+            raise ValueError("logits=None counts the pending tokens alone: out and input_ids must be None too")
+        if commit_tokens is None:
+            raise ValueError("nothing to do: no logits and no pending tokens")
+    else:
+        total, vocab, ld = _logits_rows(logits, "the penalty op has", rows="batch * rows")
+        if input_ids is None or not (input_ids.is_cuda and input_ids.dtype == torch.int64 and input_ids.dim() == 2
+                                     and input_ids.size(0) == batch and (input_ids.size(1) == 1 or input_ids.stride(1) == 1)):
+            raise TypeError(f"input_ids must be an int64 tensor of [{batch}, rows] with contiguous rows on the GPU")
+        rows, ids_ld = input_ids.size(1), _row_stride(input_ids)
+        if not 1 <= rows <= PENALTY_MAX_ROWS or total != batch * rows:
+            raise ValueError(f"input_ids must give 1 .. {PENALTY_MAX_ROWS} rows per sequence and logits batch * rows rows, "
+                             f"got {tuple(input_ids.shape)} for {total} rows of logits and {batch} rows of state")
+        if state.size(1) < vocab:
+            raise TypeError(f"state must be an int16 tensor of [{batch}, >= {vocab}] with contiguous rows on the GPU")
+    for name, t in (("repetition", repetition), ("presence", presence), ("frequency", frequency)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.shape == (batch,) and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous float32 tensor of [{batch}] on the GPU, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    commit_ld = 0
+    if (commit_tokens is None) != (commit_counts is None):
+        raise ValueError("commit_tokens and commit_counts come together")
+    if commit_tokens is not None:
+        if not (commit_tokens.is_cuda and commit_tokens.dtype == torch.int64 and commit_tokens.dim() == 2 and commit_tokens.size(0) == batch
+                and commit_tokens.size(1) >= 1 and (commit_tokens.size(1) == 1 or commit_tokens.stride(1) == 1)):
+            raise TypeError(f"commit_tokens must be an int64 tensor of [{batch}, n >= 1] with contiguous rows on the GPU")
+        if not (commit_counts.is_cuda and commit_counts.dtype == torch.int32 and commit_counts.shape == (batch,) and commit_counts.is_contiguous()):
+            raise TypeError(f"commit_counts must be a contiguous int32 tensor of [{batch}] on the GPU")
+        commit_ld = _row_stride(commit_tokens)
+    max_bias = 0
+    if (bias_ids is None) != (bias_vals is None):
+        raise ValueError("bias_ids and bias_vals come together")
+    if bias_ids is not None:
+        max_bias = bias_ids.size(1) if bias_ids.dim() == 2 else -1
+        if not (bias_ids.is_cuda and bias_vals.is_cuda and bias_ids.dtype == torch.int32 and bias_vals.dtype == torch.float32
+                and bias_ids.dim() == 2 and bias_ids.size(0) == batch and bias_vals.shape == bias_ids.shape
+                and bias_ids.is_contiguous() and bias_vals.is_contiguous()):
+            raise TypeError(f"bias_ids int32 and bias_vals float32 must be contiguous [{batch}, max_bias] tensors on the GPU")
+        if max_bias > PENALTY_MAX_BIAS:
+            raise ValueError(f"at most {PENALTY_MAX_BIAS} bias entries per row, got {max_bias}")
+    if logits is not None:
+        if out is None:
+            out = torch.empty((batch * rows, vocab), dtype=torch.float16, device=logits.device)
+        elif not (out.is_cuda and out.dtype == torch.float16 and out.shape == (batch * rows, vocab) and (vocab == 1 or out.stride(1) == 1)):
+            raise TypeError(f"out must be a float16 tensor of [{batch * rows}, {vocab}] with contiguous rows on the GPU")
+    st = L.lib().atom_penalize_rows_f16(L.ptr(logits), ld, batch, rows, vocab, state.data_ptr(), state_ld, L.ptr(input_ids), ids_ld,
+                                        L.ptr(commit_tokens), commit_ld, L.ptr(commit_counts), L.ptr(repetition), L.ptr(presence),
+                                        L.ptr(frequency), L.ptr(bias_ids) if max_bias else None, L.ptr(bias_vals) if max_bias else None,
+                                        max_bias, L.ptr(out), 0 if out is None else _row_stride(out), L.current_stream(state.device))
+    L.check(st, "atom_penalize_rows_f16")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ beam search
 BEAM_MAX_BEAMS = 16
 

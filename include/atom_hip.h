@@ -767,6 +767,43 @@ int atom_penalize_f16(const void *logits, int64_t ld, int64_t batch, int64_t voc
                       int64_t max_bias, void *out, int64_t out_ld, void *stream);
 
 /*
+ * The same penalties on the verify rows of speculative decoding -- csrc/penalize.hip, the arithmetic of csrc/penalty_math.h unchanged,
+ * the contract in DESIGN.md 4.20.  No reference counterpart.  A verify step scores rows = K + 1 rows per sequence; row j is penalised as
+ * if drafts 1 .. j had been emitted, rejected drafts leave no trace, and the tokens the step before emitted are counted first.
+ *   logits fp16 [batch * rows, vocab], rows ld apart (row b * rows + j is row j of sequence b); out likewise, out_ld apart; out may
+ *   equal logits (then out_ld == ld).  state int16 [batch, state_ld >= vocab]: one row per SEQUENCE, the words of atom_penalize_f16.
+ *   input_ids int64 [batch, rows], ids_ld apart: column 0 is the last emitted token, columns 1 .. rows - 1 the drafts.
+ *   commit_tokens int64 [batch, >= commit_ld], commit_ld apart, and commit_counts int32 [batch]: the tokens to count first; both NULL:
+ *   none.  rep, pres, freq float [batch] or NULL and bias_ids / bias_vals [batch, max_bias]: per SEQUENCE, as atom_penalize_f16 reads
+ *   them per row.  All DEVICE arrays, read by the launch: a captured launch follows buffers that are changed in place.
+ * Sequence b:
+ *   1. Commit: c = commit_counts[b] clamped to 0 .. min(commit_ld, 9).  For i = 0 .. c - 1 in order, a commit_tokens[b][i] inside
+ *      0 .. vocab - 1 has its state word counted up (saturating, the sign bit kept), once per occurrence: duplicates count twice.
+ *      Any other value counts nothing.  Only these words of state are written, each only if it changes, whatever the sequence's
+ *      parameters are.
+ *   2. Rows: w_0 is the committed state row; for j >= 1, w_j is w_(j-1) with the word of input_ids[b][j] counted up, if that draft lies
+ *      inside 0 .. vocab - 1.  Column 0 is NOT counted here: the step that emitted it committed it.  Drafts never reach state.
+ *   3. Row (b, j) of out is, bit for bit, what atom_penalize_f16 writes for that row of logits under a state row w_j with fed = NULL and
+ *      the parameters and bias list of sequence b: the neutral copy, the copy of what is neither seen nor biased, 0x7E00 for a
+ *      computed NaN.
+ *   4. logits == NULL and out == NULL: rule 1 alone (rows, input_ids, the parameters and the bias list are not read).
+ *   Pending tokens, drafts and bias ids are compared with element positions, never used as addresses.
+ * One launch, a grid of (2048-element tile, sequence) workgroups: the workgroup is the only one that touches its tile of the state, which
+ * it reads once.  No workspace, nothing read back: capturable.
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for exactly one of logits / out null, exactly one of commit_tokens /
+ * commit_counts null, nothing to do (neither logits nor pending tokens), a null state, a null input_ids when logits are given, or
+ * max_bias > 0 with a null bias array; ATOM_ERR_SHAPE for batch outside 1 .. 65535, rows outside 1 .. 9, batch * rows beyond int32, vocab
+ * outside 1 .. 262144, state_ld < vocab, commit_ld < 1 with pending tokens, max_bias outside 0 .. 512 and, when logits are given, ld /
+ * out_ld < vocab, ids_ld < rows, or out == logits with out_ld != ld; ATOM_ERR_ALIGN for a pointer off its element size (2 bytes for
+ * logits / out / state, 4 for commit_counts / rep / pres / freq / bias_ids / bias_vals, 8 for input_ids / commit_tokens).  When logits,
+ * out and state are 16-byte aligned with leading dimensions that are multiples of 8, they are accessed 16 bytes at a time.
+ */
+int atom_penalize_rows_f16(const void *logits, int64_t ld, int64_t batch, int64_t rows, int64_t vocab, int16_t *state, int64_t state_ld,
+                           const int64_t *input_ids, int64_t ids_ld, const int64_t *commit_tokens, int64_t commit_ld,
+                           const int32_t *commit_counts, const float *rep, const float *pres, const float *freq, const int32_t *bias_ids,
+                           const float *bias_vals, int64_t max_bias, void *out, int64_t out_ld, void *stream);
+
+/*
  * Beam search, the selection step: per prompt group, the next w_out beams out of the candidates of its w_in rows -- csrc/beam.hip,
  * arithmetic in csrc/beam_math.h, the contract in DESIGN.md 4.16.  No reference counterpart.  The candidates are the top-n of
  * atom_logprob_f16: the best w_out of all w_in x vocab continuations lie within the union of each row's best w_out.
