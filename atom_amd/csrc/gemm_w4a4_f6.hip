@@ -1389,11 +1389,14 @@ struct QRegs {
   float sb[2][PAIR ? 4 : 8];   // weight scales of feature-block pair h: [h][2 r + (fb & 1)]; PAIR (channels 2 j, 2 j + 1 share theirs): [h][r]
   QSa sa[4];            // token scales, ring by token block % 4
   // SA2 (the headline instantiation): no scale ring -- the products of pair slots 4 q .. 4 q + 3 ("group" q) come from one scale_tile4,
-  // made behind the de-quantisation of slot 4 q - 1 (the old tile's last reader), first read one slot later.  Its operands, one dword each:
+  // made behind the de-quantisation of slot 4 q - 2 and first read two slots later (see st).  Its operands, one dword each:
   float sbq[2];         //   the weight scale of pair l % 16 of feature-block pair h: [0] h = (l / 16) % 2 (groups 0-2: slots (tb, 0), (tb, 1),
                         //   (tb + 1, 0), (tb + 1, 1)), [1] h = l / 32 (group 3: slots (6, 0), (7, 0), (6, 1), (7, 1))
   float saq;            //   the scale of token l % 16 of token block 2 q + l / 32 (group 3: 6 + (l / 16) % 2) of the NEXT tile
-  v16f_t st;            //   the tile: register 4 b + r = slot 4 q + b, channel pair 4 (l / 16) + r
+  v16f_t st[2];         //   the tile of group q in st[q % 2]: register 4 b + r = slot 4 q + b, channel pair 4 (l / 16) + r.  Two of them, so
+                        //   that a tile is issued TWO slots ahead of its first reader (behind the de-quantisation of slot 4 q - 2, while
+                        //   slot 4 q - 1 still reads the other one): an 8-pass MFMA read one slot behind its issue holds up the two
+                        //   BF6 MFMAs of that slot on the matrix pipe.  -DATOM_Q_NO_ST2: one slot ahead, in st[0] alone.
   v4f_t acc[2][2];
   // lane byte addresses in LDS, [set][piece]: set 0 serves stage slots 0 and 1 (+ instruction offset), set 1 = + 2 stages for
   // slot 2.  All opaque to the compiler: it would otherwise re-derive one from another with a v_add per use, or merge two 8-byte
@@ -1409,6 +1412,12 @@ struct QRegs {
 // SL = 0..2: compile-time stage slot; SL < 0: the slot's byte offset arrives at run time in `ro` (the two keeper-prefetch steps
 // at the end of the K loop, executed once: one code body each instead of one per slot)
 template <int SL> __device__ __forceinline__ constexpr int q_set() { return SL == 2 ? 1 : 0; }
+#ifdef ATOM_Q_NO_ST2                         // A/B builds (tools/ab_build.sh)
+constexpr bool kQSt2 = false;
+#else
+constexpr bool kQSt2 = true;
+#endif
+__device__ __forceinline__ constexpr int q_st(int slot) { return kQSt2 ? (slot >> 2) & 1 : 0; }   // the tile register set of a pair slot
 template <class C, int SL> __device__ __forceinline__ constexpr int q_imm() { return SL == 1 ? QC<C>::STAGE : 0; }
 
 // A load from a lane's LDS byte address + a compile-time offset, for a kernel whose `lds` array starts at LDS byte 0 (the q kernel: no
@@ -1555,7 +1564,10 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
       if constexpr (!SA2) R.sa[(tb + 2) & 3] = q_scale<C, SL>(lds, R, p_row(tb + 2) * PITCH, ro);
     }
     // SA2: the token scales of the next tile, two slots ahead of it (the previous tile was issued in slot i - 2)
-    if constexpr (SA2) { if ((i & 3) == 2 && i < 14) R.saq = q_scale_q<C, SL>(R, (i + 2) >> 2, ro); }
+    if constexpr (SA2) {
+      constexpr int AT = kQSt2 ? 1 : 2;
+      if ((i & 3) == AT && i < 12 + AT) R.saq = q_scale_q<C, SL>(R, (i + 4 - AT) >> 2, ro);
+    }
     if (!LAST) {
       if (i == 12) {                                         // next step's block 0 (buffer 2: free since slot 1)
         R.bf[2] = q_frag<C, NX, SA2>(lds, R.aA, p_row(0) * PITCH, rn);
@@ -1581,7 +1593,7 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
       }
       // SA2: the next step's group 0 in slot 14; the weight scales of the next stage behind their last tiles of this one (slots 8 and 12)
       if constexpr (SA2) {
-        if (i == 14) R.saq = q_scale_q<C, NX>(R, 0, rn);
+        if (i == (kQSt2 ? 13 : 14)) R.saq = q_scale_q<C, NX>(R, 0, rn);
         if (i == 10) R.sbq[0] = q_load_sbq<C, NX>(R, 0, rn);
         if (i == 13) R.sbq[1] = q_load_sbq<C, NX>(R, 1, rn);
       }
@@ -1594,13 +1606,19 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
     // ---- de-quantisation of the previous slot's pair (slot 15 of the previous step for i == 0)
     {
       const int j = (i + 15) & 15, dtb = p_tb(j), dh = p_h(j);
-      if constexpr (SA2) deq_pair_t(R.acc[j & 1][0], R.acc[j & 1][1], R.st, j & 3, c[2 * dh][dtb], c[2 * dh + 1][dtb]);
+      if constexpr (SA2) deq_pair_t(R.acc[j & 1][0], R.acc[j & 1][1], R.st[q_st(j)], j & 3, c[2 * dh][dtb], c[2 * dh + 1][dtb]);
       else deq_pair<PAIR>(R.acc[j & 1][0], R.acc[j & 1][1], R.tscale(dtb), R.sb[dh], c[2 * dh][dtb], c[2 * dh + 1][dtb]);
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (SA2) {
-      // the scale tile of slots i .. i + 3: its predecessor's last reader (slot i - 1) has just issued, its first one runs a slot from here
-      if ((i & 3) == 0) { R.st = scale_tile4(R.sbq[i == 12], R.saq); __builtin_amdgcn_sched_barrier(0); }
+      // the scale tile of slots i + 1 .. i + 4 (slot 15: of the next step's group 0, from the next stage's scales) into the set whose
+      // last reader (slot i - 1) has just issued; its first reader runs two slots from here.  (The last int4 step makes one nobody reads.)
+      if constexpr (kQSt2) {
+        if ((i & 3) == 3) { R.st[q_st(i + 1)] = scale_tile4(R.sbq[i == 11], R.saq); __builtin_amdgcn_sched_barrier(0); }
+      } else {
+        // ... of slots i .. i + 3: its predecessor's last reader (slot i - 1) has just issued, its first one runs a slot from here
+        if ((i & 3) == 0) { R.st[0] = scale_tile4(R.sbq[i == 12], R.saq); __builtin_amdgcn_sched_barrier(0); }
+      }
     } else {
       // weight scales: pair 0's registers die with slot 13's de-quantisation (done in slot 14) and take the next stage's values;
       // pair 1's die with the carried pair (slot 15, done in the next step's slot 0) and take the current stage's
@@ -1861,7 +1879,8 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
       R.saq = q_scale_q<C, 0>(R, 0, 0);
       R.sbq[0] = q_load_sbq<C, 0>(R, 0, 0);
       R.sbq[1] = q_load_sbq<C, 0>(R, 1, 0);
-      R.st = scale_tile4(R.sbq[1], 0.f);                    // the "carried pair" of the first step (block 3): zeros x 0 x its weight scales
+      R.st[q_st(15)] = scale_tile4(R.sbq[1], 0.f);          // the "carried pair" of the first step (block 3): zeros x 0 x its weight scales
+      if constexpr (kQSt2) R.st[0] = scale_tile4(R.sbq[0], R.saq);   // ... and the first step's group 0, which later steps get from slot 15
     } else {
       R.sa[0] = q_scale<C, 0>(lds, R, p_row(0) * PITCH, 0);
       R.sa[1] = q_scale<C, 0>(lds, R, p_row(1) * PITCH, 0);
@@ -1937,7 +1956,7 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
                   (s % 3) * Q::STAGE, ((s + 1) % 3) * Q::STAGE, s + 1 == G);
   }
   // the carried pair (slot 15) of the last int4 step
-  if constexpr (SA2) deq_pair_t(R.acc[1][0], R.acc[1][1], R.st, 3, c[2][7], c[3][7]);
+  if constexpr (SA2) deq_pair_t(R.acc[1][0], R.acc[1][1], R.st[q_st(15)], 3, c[2][7], c[3][7]);
   else deq_pair<PAIR>(R.acc[1][0], R.acc[1][1], R.tscale(7), R.sb[1], c[2][7], c[3][7]);
   // keeper half 0 was published by the last mid-step barrier; half 1 was issued behind it: ONE step over both once it has landed
   kstamp(4);
