@@ -92,6 +92,10 @@ SIGNATURES = {
     "atom_batch_decode_gqa_i4": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_batch_prefill_gqa_i4_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 6),
     "atom_batch_prefill_gqa_i4": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    # the parents' lists with (rope_table, attn_scale) behind rope_scale
+    "atom_batch_decode_gqa_i4_rope": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_prefill_gqa_i4_rope": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_decode_append_i4_rope": (_int, [_vp] * 9 + [_int] * 6 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_kv_step_i4": (_int, [_vp] * 7 + [_int] * 4 + [_vp]),
     "atom_moe_max_tiles": (_i64, [_i64, _int]),
     "atom_moe_route_topk": (_int, [_vp, _i64, _int, _int] + [_vp] * 9),

@@ -124,6 +124,19 @@ static int check_kv(const void *kv_data, const void *kv_param, const int32_t *in
   return ATOM_OK;
 }
 
+// the two arguments of the _rope entry points: a per-pair frequency table (NULL: the theta path) and a factor on the logits
+static int check_rope_table(const float *rope_table, float attn_scale) {
+  if (!(attn_scale > 0.f)) return ATOM_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(rope_table) & 3u) return ATOM_ERR_ALIGN;
+  return ATOM_OK;
+}
+
+// kv_i4.hip: the MHA decode op with the _rope arguments (no C entry point of its own: atom_batch_decode_gqa_i4_rope forwards to it)
+int batch_decode_rope(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                      const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim,
+                      float rope_theta, float rope_scale, const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 static size_t partial_state_bytes(int64_t rows_times_heads, int splits) {
   return (size_t)rows_times_heads * splits * (kHeadDim + 2) * sizeof(float);
 }

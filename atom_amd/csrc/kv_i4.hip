@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kv_attn.h"
+#include "rope_math.h"
 
 namespace atom {
 
@@ -143,7 +144,9 @@ struct DecodeParams {
   int splits;
   float sm_scale, log2_theta, rope_inv_scale;
   const float *k32, *v32;   // optional (atom_batch_decode_append_i4): the step's k / v projections as FP32 sums [B, N * 128] -- quantised and
-};                          // appended as the last token by the wave that attends to it
+                            // appended as the last token by the wave that attends to it
+  const float *rope_table;  // TABLE kernels only: float[64], revolutions per position of pair i (the _rope entry points)
+};
 
 // 8 packed u4 (nibble e at bits 4e) -> 4 half2 registers holding 1024 + nibble: m[k] = {1024 + n_k, 1024 + n_(k+4)}.
 // (x >> 4k) & 0x000F000F | 0x64006400 is one v_and_or_b32 (plus one shift for k > 0): 7 instructions per 8 elements,
@@ -219,7 +222,9 @@ constexpr int kWgmWaves = 12;
 #define ATOM_DECODE_KINNER 4
 #endif
 constexpr int kInner = ATOM_DECODE_KINNER;
-template <bool WGM, int INNER = 1>
+// TABLE (the _rope entry points): the frequency of pair i is p.rope_table[i] as loaded, and the first relative position's angle is formed
+// exactly (rope_math.h); log2_theta / rope_inv_scale are not read.  The 16-position step (16 f: exact) and the tile loop are the same.
+template <bool WGM, int INNER = 1, bool TABLE = false>
 __global__ __launch_bounds__(WGM ? 64 * kWgmWaves : 64 * INNER, 3) void batch_decode_kernel(DecodeParams p) {
   const int lane = threadIdx.x & 63;
   const int t = lane >> 2, u = lane & 3;
@@ -228,6 +233,10 @@ __global__ __launch_bounds__(WGM ? 64 * kWgmWaves : 64 * INNER, 3) void batch_de
     const void *a0 = p.kv.indptr, *a1 = p.kv.indices, *a2 = p.kv.last_page_offset, *a3 = p.q, *a4 = p.kv.data, *a5 = p.kv.param, *a6 = p.k32, *a7 = p.v32;
     asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(a5), "s"(a6), "s"(a7));
   }
+  // TABLE: the frequency of pair `lane`, requested before everything else -- vector loads return in order, so behind the tile ring's
+  // loads it would hold the whole prologue (rotating q) until the first tiles have landed
+  float table_fr = 0.f;
+  if constexpr (TABLE) table_fr = p.rope_table[lane];
   const int N = p.kv.N, P = p.kv.P;
   int pair = blockIdx.x, sp = blockIdx.y, lp = 0;       // (sequence, head) pair, KV split, pair within the workgroup
   if constexpr (!WGM && INNER > 1) sp = (int)blockIdx.y * INNER + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -341,8 +350,11 @@ __global__ __launch_bounds__(WGM ? 64 * kWgmWaves : 64 * INNER, 3) void batch_de
   const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   {
     // decode.cuh:535-539: freq = rope_inv_scale * theta^(-2 (i mod 64) / 128); here in revolutions
-    const float fr = p.rope_inv_scale * 0.15915494309189535f *
-                     __builtin_amdgcn_exp2f(-p.log2_theta * (float)(2 * lane) * (1.0f / kHeadDim));
+    float fr;
+    if constexpr (TABLE)
+      fr = table_fr;
+    else
+      fr = p.rope_inv_scale * 0.15915494309189535f * __builtin_amdgcn_exp2f(-p.log2_theta * (float)(2 * lane) * (1.0f / kHeadDim));
     float s16, c16;
     sincos_rev(16.0f * fr, s16, c16);
     rope_fr[wv][lane] = fr;
@@ -364,7 +376,10 @@ __global__ __launch_bounds__(WGM ? 64 * kWgmWaves : 64 * INNER, 3) void batch_de
     for (int i = 0; i < 16; ++i) {
       const float fr = rope_fr[wv][16 * u + i];
       float s, c;
-      sincos_rev(delta * fr, s, c);
+      if constexpr (TABLE)
+        rope_sincos_exact(delta, fr, s, c);
+      else
+        sincos_rev(delta * fr, s, c);
       const float q1 = (float)h1[i], q2 = (float)h2p[i];
       A[i] = v2f{q1 * c - q2 * s, q2 * c + q1 * s};
       SC[i] = rope_sc[wv][16 * u + i];
@@ -688,7 +703,8 @@ size_t atom_batch_decode_i4_workspace_bytes(int batch, int num_heads, int page_s
 static int batch_decode_impl(void *o, const void *q, const float *k32, const float *v32, const void *kv_data, const void *kv_param,
                              const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int batch,
                              int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
-                             float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+                             float rope_scale, const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                             size_t workspace_bytes, void *stream) {
   const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
                           num_heads, page_size, head_dim);
   if (st != ATOM_OK) return st;
@@ -700,16 +716,25 @@ static int batch_decode_impl(void *o, const void *q, const float *k32, const flo
   // o == NULL: the split partial states stay in the workspace un-merged (atom_batch_decode_i4_splits() of them; the consumer merges:
   // atom_gemm_w4a4_multi_merge_q) -- only meaningful when the KV range IS split
   if (!o && pl.splits < 2) return ATOM_ERR_INVALID_ARG;
+  if (const int rs = check_rope_table(rope_table, attn_scale)) return rs;   // (the _rope entries' own faults: behind every older one)
   const int ppw = pl.wgm ? kWgmWaves / pl.total : 1;    // (sequence, head) pairs per workgroup
   DecodeParams p{kv_params(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_heads, page_size),
                  make_fastdiv((unsigned)num_heads), make_fastdiv((unsigned)pl.total), make_fastdiv((unsigned)(page_size >> 4)),
                  make_fastdiv((unsigned)page_size), ppw,
                  (const half_t *)q, (half_t *)o, (float *)workspace, pl.total,
-                 1.0f / sqrtf((float)kHeadDim), log2f(rope_theta), 1.0f / rope_scale, k32, v32};
+                 1.0f / sqrtf((float)kHeadDim) * attn_scale, log2f(rope_theta), 1.0f / rope_scale, k32, v32, rope_table};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)pairs, (unsigned)pl.splits);
-  if (pl.wgm)
-    hipLaunchKernelGGL(batch_decode_kernel<true>, dim3((unsigned)((pairs + ppw - 1) / ppw)), dim3(64 * kWgmWaves), 0, s, p);
+  const dim3 wgrid((unsigned)((pairs + ppw - 1) / ppw));
+  if (rope_table) {                                       // the same plan, the TABLE instantiation of the same kernel
+    if (pl.wgm)
+      hipLaunchKernelGGL((batch_decode_kernel<true, 1, true>), wgrid, dim3(64 * kWgmWaves), 0, s, p);
+    else if (pl.inner == kInner)
+      hipLaunchKernelGGL((batch_decode_kernel<false, kInner, true>), grid, dim3(64 * kInner), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_decode_kernel<false, 1, true>), grid, dim3(64), 0, s, p);
+  } else if (pl.wgm)
+    hipLaunchKernelGGL(batch_decode_kernel<true>, wgrid, dim3(64 * kWgmWaves), 0, s, p);
   else if (pl.inner == kInner)
     hipLaunchKernelGGL((batch_decode_kernel<false, kInner>), grid, dim3(64 * kInner), 0, s, p);
   else
@@ -728,7 +753,8 @@ int atom_batch_decode_i4(void *o, const void *q, const void *kv_data, const void
                          int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
                          int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
   return batch_decode_impl(o, q, nullptr, nullptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
-                           num_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace, workspace_bytes, stream);
+                           num_heads, page_size, head_dim, rope_theta, rope_scale, nullptr, 1.0f, max_pages_per_seq, workspace,
+                           workspace_bytes, stream);
 }
 
 int atom_batch_decode_append_i4(void *o, const void *q, const void *k_f32, const void *v_f32, void *kv_data, void *kv_param,
@@ -738,8 +764,30 @@ int atom_batch_decode_append_i4(void *o, const void *q, const void *k_f32, const
   if (!k_f32 || !v_f32) return ATOM_ERR_INVALID_ARG;
   if (!aligned16(k_f32) || !aligned16(v_f32)) return ATOM_ERR_ALIGN;
   return batch_decode_impl(o, q, (const float *)k_f32, (const float *)v_f32, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset,
-                           batch, num_layers, layer_idx, num_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq,
-                           workspace, workspace_bytes, stream);
+                           batch, num_layers, layer_idx, num_heads, page_size, head_dim, rope_theta, rope_scale, nullptr, 1.0f,
+                           max_pages_per_seq, workspace, workspace_bytes, stream);
+}
+
+int atom_batch_decode_append_i4_rope(void *o, const void *q, const void *k_f32, const void *v_f32, void *kv_data, void *kv_param,
+                                     const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int batch,
+                                     int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
+                                     float rope_scale, const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+  if (!k_f32 || !v_f32) return ATOM_ERR_INVALID_ARG;
+  if (!aligned16(k_f32) || !aligned16(v_f32)) return ATOM_ERR_ALIGN;
+  return batch_decode_impl(o, q, (const float *)k_f32, (const float *)v_f32, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset,
+                           batch, num_layers, layer_idx, num_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
+                           max_pages_per_seq, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
+
+// atom_batch_decode_i4 with a table and a scale: what atom_batch_decode_gqa_i4_rope forwards to at num_qo_heads == num_kv_heads (kv_attn.h)
+int atom::batch_decode_rope(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                            const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                            int num_heads, int page_size, int head_dim, float rope_theta, float rope_scale, const float *rope_table,
+                            float attn_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+  return batch_decode_impl(o, q, nullptr, nullptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx,
+                           num_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq, workspace,
+                           workspace_bytes, stream);
+}

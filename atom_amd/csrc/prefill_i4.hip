@@ -39,8 +39,10 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
 #include "kv_attn.h"
+#include "rope_math.h"
 
 namespace atom {
 
@@ -65,6 +67,7 @@ struct PrefillParams {
   int splits;
   float qk_scale, log2_theta, rope_inv_scale;
   int G, Nq;         // GQA kernel only: query heads per K/V head, query heads (N * G); qo_indptr NULL = one query per sequence
+  const float *rope_table;   // kTable kernels only: float[64], revolutions per position of pair i (the _rope entry points)
 };
 
 // sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
@@ -86,7 +89,10 @@ __device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * 
 
 // GQA: a block's rows are (query, head of the group) pairs, query-major -- row r of (sequence b, K/V head h) is query r / G of query head
 // h G + r % G -- so every staged tile serves the whole group.  The MHA instantiation is the kernel with G = 1 (the same code).
-template <bool kGqa>
+// kTable (the _rope entry points): the frequency of pair i is p.rope_table[i] as loaded; log2_theta / rope_inv_scale are not read.  The
+// query's angle is formed exactly (rope_math.h), and so is a key's from position kRopeExactFrom on: the staging is VALU-bound, so the
+// choice is made per key tile (workgroup-uniform) and is a template argument of the staging code.
+template <bool kGqa, bool kTable = false>
 __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
   __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
   __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
@@ -117,8 +123,12 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int chunk = (ntiles + p.splits - 1) / p.splits;
   const int t0 = sp * chunk, t1 = min(ntiles, t0 + chunk);
 
-  if (tid < 64)   // decode.cuh:535-539 / batch_decode_kernel: freq = rope_inv_scale * theta^(-2 i / 128), here in revolutions
-    rope_fr[tid] = p.rope_inv_scale * 0.15915494309189535f * __builtin_amdgcn_exp2f(-p.log2_theta * (float)(2 * tid) * (1.0f / kHeadDim));
+  if (tid < 64) {  // decode.cuh:535-539 / batch_decode_kernel: freq = rope_inv_scale * theta^(-2 i / 128), here in revolutions
+    if constexpr (kTable)
+      rope_fr[tid] = p.rope_table[tid];
+    else
+      rope_fr[tid] = p.rope_inv_scale * 0.15915494309189535f * __builtin_amdgcn_exp2f(-p.log2_theta * (float)(2 * tid) * (1.0f / kHeadDim));
+  }
   __syncthreads();
 
   // ---- my query row: lane (li, g) = (row 16 w + li of the block, k-group); B operand of S^T: q[row][32 ks + 8 g .. + 7], ks = 0..3.
@@ -142,7 +152,10 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float s, c;
-        pf_sincos_rev((float)pos * rope_fr[32 * hf + 8 * g + j], s, c);
+        if constexpr (kTable)
+          rope_sincos_exact((float)pos, rope_fr[32 * hf + 8 * g + j], s, c);
+        else
+          pf_sincos_rev((float)pos * rope_fr[32 * hf + 8 * g + j], s, c);
         const float x1 = (float)x[hf][j], x2 = (float)x[hf + 2][j];
         qf[hf][j] = (half_t)(x1 * c - x2 * s);
         qf[hf + 2][j] = (half_t)(x2 * c + x1 * s);
@@ -176,7 +189,7 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
     }
     return r;
   };
-  auto stage = [&](int tile, const PfTileRegs &r) {
+  auto stage = [&](int tile, const PfTileRegs &r, auto exact) {   // exact: std::bool_constant -- the product of a key's angle (rope_math.h)
     const int j = tile * kPfKeys + kk;
     const bool ok = j < len;                              // past the end: zeros (the loaded registers are zeros too, see load)
     const float ks = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq & 0xFFFF)) : 0.f;
@@ -193,7 +206,10 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
         const float x1 = __builtin_fmaf((float)((r.k1[hw] >> (4 * e)) & 0xF), ks, -kz);
         const float x2 = __builtin_fmaf((float)((r.k2[hw] >> (4 * e)) & 0xF), ks, -kz);
         float s, c;
-        pf_sincos_rev((float)j * rope_fr[16 * u + m], s, c);
+        if constexpr (decltype(exact)::value)
+          rope_sincos_exact((float)j, rope_fr[16 * u + m], s, c);
+        else
+          pf_sincos_rev((float)j * rope_fr[16 * u + m], s, c);
         klo[hw][e] = (half_t)(x1 * c - x2 * s);
         khi[hw][e] = (half_t)(x2 * c + x1 * s);
       }
@@ -222,7 +238,14 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   if (t0 < t1) regs = load(t0);
   for (int tile = t0; tile < t1; ++tile) {
     __syncthreads();                                      // the previous tile's LDS reads are done
-    stage(tile, regs);
+    if constexpr (kTable) {
+      if (tile * kPfKeys >= kRopeExactFrom)               // (workgroup-uniform) short contexts never take the exact form
+        stage(tile, regs, std::true_type{});
+      else
+        stage(tile, regs, std::false_type{});
+    } else {
+      stage(tile, regs, std::false_type{});
+    }
     __syncthreads();
     if (tile + 1 < t1) regs = load(tile + 1);             // in flight during this tile's products
     const int kt0 = tile * kPfKeys;
@@ -378,7 +401,8 @@ static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_le
 static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
                           const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
                           int batch, int num_layers, int layer_idx, int G, int num_kv_heads, int page_size, int head_dim, float rope_theta,
-                          float rope_scale, int max_pages, void *workspace, size_t workspace_bytes, void *stream) {
+                          float rope_scale, const float *rope_table, float attn_scale, int max_pages, void *workspace,
+                          size_t workspace_bytes, void *stream) {
   const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
                           page_size, head_dim);
   if (st != ATOM_OK) return st;
@@ -392,16 +416,23 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   if (!o && pl.splits < 2) return ATOM_ERR_INVALID_ARG;
   const int64_t grid = (int64_t)pl.nqb * batch * num_kv_heads * pl.splits;
   if (grid > 0x7fffffff || rows_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
+  if (const int rs = check_rope_table(rope_table, attn_scale)) return rs;   // (the _rope entries' own faults: behind every older one)
   PrefillParams p;                                        // by name: the fields' order is the kernel's business
   p.data = (const uint8_t *)kv_data, p.param = (const half_t *)kv_param;
   p.kv_indptr = kv_indptr, p.kv_indices = kv_indices, p.last_page_offset = last_page_offset, p.qo_indptr = qo_indptr;
   p.q = (const half_t *)q, p.o = (half_t *)o, p.ws = (float *)workspace;
   p.batch = batch, p.L = num_layers, p.layer = layer_idx, p.N = num_kv_heads, p.P = page_size;
   p.nqb = pl.nqb, p.splits = pl.splits;
-  p.qk_scale = kLog2e / sqrtf((float)kHeadDim), p.log2_theta = log2f(rope_theta), p.rope_inv_scale = 1.0f / rope_scale;
+  p.qk_scale = kLog2e / sqrtf((float)kHeadDim) * attn_scale, p.log2_theta = log2f(rope_theta), p.rope_inv_scale = 1.0f / rope_scale;
   p.G = G, p.Nq = num_qo_heads;                           // (batch_prefill_kernel<false> reads neither)
+  p.rope_table = rope_table;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (G == 1 && !decode)                                  // the MHA entry: the GQA entries forward G = 1 to the MHA ops
+  if (rope_table) {                                       // the same plan, the kTable instantiation of the same kernel
+    if (G == 1 && !decode)
+      hipLaunchKernelGGL((batch_prefill_kernel<false, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_prefill_kernel<true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  } else if (G == 1 && !decode)                                  // the MHA entry: the GQA entries forward G = 1 to the MHA ops
     hipLaunchKernelGGL(batch_prefill_kernel<false>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
   else
     hipLaunchKernelGGL(batch_prefill_kernel<true>, dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
@@ -425,8 +456,8 @@ int atom_batch_prefill_i4(void *o, const void *q, const int32_t *qo_indptr, int6
                           int batch, int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
   return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
-                        num_layers, layer_idx, 1, num_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
-                        workspace_bytes, stream);
+                        num_layers, layer_idx, 1, num_heads, page_size, head_dim, rope_theta, rope_scale, nullptr, 1.0f, max_pages_per_seq,
+                        workspace, workspace_bytes, stream);
 }
 
 size_t atom_batch_prefill_gqa_i4_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
@@ -443,8 +474,21 @@ int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, 
   const int G = gqa_group(num_qo_heads, num_kv_heads);
   if (G == 0) return ATOM_ERR_SHAPE;
   return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
-                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
-                        workspace_bytes, stream);
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, nullptr, 1.0f, max_pages_per_seq,
+                        workspace, workspace_bytes, stream);
+}
+
+int atom_batch_prefill_gqa_i4_rope(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
+                        max_pages_per_seq, workspace, workspace_bytes, stream);
 }
 
 size_t atom_batch_decode_gqa_i4_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq) {
@@ -471,8 +515,24 @@ int atom_batch_decode_gqa_i4(void *o, const void *q, const void *kv_data, const 
                                 num_qo_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace, workspace_bytes,
                                 stream);
   return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
-                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, max_pages_per_seq, workspace,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, nullptr, 1.0f, max_pages_per_seq, workspace,
                         workspace_bytes, stream);
+}
+
+int atom_batch_decode_gqa_i4_rope(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  if (G == 1)
+    return batch_decode_rope(o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_qo_heads,
+                             page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq, workspace,
+                             workspace_bytes, stream);
+  return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq,
+                        workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

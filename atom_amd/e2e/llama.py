@@ -13,6 +13,7 @@ import dataclasses
 import math
 
 from .. import ops
+from .rope import rope_init
 from ..utils import BatchedKvCacheInt4, BatchLenInfo
 
 GROUP = 128
@@ -227,10 +228,11 @@ def dequant_kv_u4(packed: torch.Tensor, param: torch.Tensor) -> torch.Tensor:
     return u * p[..., 0:1] - p[..., 1:2]
 
 
-def rope_llama(x: torch.Tensor, pos: torch.Tensor, theta: float = 1e4) -> torch.Tensor:
-    """x [T, heads, 128] fp32, pos [T]: pairs (i, i + 64), freq_i = theta^(-2i/128) (decode.cuh:40-72)."""
+def rope_llama(x: torch.Tensor, pos: torch.Tensor, theta: float = 1e4, inv_freq: torch.Tensor = None) -> torch.Tensor:
+    """x [T, heads, 128] fp32, pos [T]: pairs (i, i + 64), freq_i = theta^(-2i/128) (decode.cuh:40-72) -- or ``inv_freq`` [64] fp32,
+    radians per position, in its place (RoPE scaling: e2e/rope.py)."""
     d = x.shape[-1]
-    inv = theta ** (-torch.arange(0, d, 2, device=x.device, dtype=torch.float32) / d)
+    inv = theta ** (-torch.arange(0, d, 2, device=x.device, dtype=torch.float32) / d) if inv_freq is None else inv_freq
     ang = pos.to(torch.float32)[:, None] * inv[None, :]
     cos = torch.cat([ang.cos(), ang.cos()], -1)[:, None, :]
     sin = torch.cat([ang.sin(), ang.sin()], -1)[:, None, :]
@@ -238,15 +240,15 @@ def rope_llama(x: torch.Tensor, pos: torch.Tensor, theta: float = 1e4) -> torch.
     return x * cos + rot * sin
 
 
-def _append_and_decode(fusion, q, k32, v32, decode_kv, layer_idx, rope_theta, merge=True):
+def _append_and_decode(fusion, q, k32, v32, decode_kv, layer_idx, rope_theta, merge=True, **rope):
     """reference llama.py:168-196 for a pure decode step: this token's k / v into the INT4 paged cache, then attention over it -- one
     launch (DecodeFusion.kv_in_decode) or two; the same cache bytes and the same output either way.  ``merge=False``: the KV-split
     partial states instead of the output (ops.batch_decode_i4).  Grouped-query attention (q with more heads than the cache) always
-    takes two launches: the GQA decode op has no append built in."""
+    takes two launches: the GQA decode op has no append built in.  ``rope``: LlamaAttention.rope_kw (RoPE scaling; empty by default)."""
     if fusion.kv_in_decode and q.size(1) == ops._kv_dims(decode_kv)[1]:
-        return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, append_kv=(k32, v32), merge=merge)
+        return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, append_kv=(k32, v32), merge=merge, **rope)
     ops.quant_append_kv_i4(decode_kv, k32, v32, layer_idx)
-    return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, merge=merge)
+    return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, merge=merge, **rope)
 
 
 class LlamaAttention(nn.Module):
@@ -259,7 +261,11 @@ class LlamaAttention(nn.Module):
     A ``StaticBatchedKvCacheInt4`` as the prefill cache (the verify step of speculative decoding, capturable) always takes that op:
     its lengths live on the device, so no host-side prefix is looked at.
     Grouped-query attention: ``config.num_key_value_heads`` (default num_attention_heads) K/V heads, query head h reads K/V head
-    h // G; k_proj / v_proj are num_key_value_heads * 128 wide, the paged caches hold num_key_value_heads heads."""
+    h // G; k_proj / v_proj are num_key_value_heads * 128 wide, the paged caches hold num_key_value_heads heads.
+    RoPE scaling (e2e/rope.py: ``config.rope_parameters`` or ``rope_theta`` + ``rope_scaling``): ``linear`` is the ops' ``rope_scale``;
+    ``llama3`` and ``yarn`` put a per-pair frequency table in the non-persistent buffer ``rope_table`` (a fixed device address, absent
+    from ``state_dict``) and YaRN's attention_factor ** 2 in ``attn_scale``; every attention call below takes them (``rope_kw``).  A
+    config without scaling allocates nothing and makes the calls it always made; an unsupported type raises here."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -284,7 +290,25 @@ class LlamaAttention(nn.Module):
         self.v_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype="int4", bias=False, fusion=fusion)
         self.o_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="fp16", bias=False, fusion=fusion)
         self.reorder_index = nn.Parameter(torch.randperm(self.hidden_size).to(torch.int16), requires_grad=False)
-        self.rope_theta = float(getattr(config, "rope_theta", 1e4))
+        self.rope_theta, self.rope_scale, inv_freq, attention_factor = rope_init(config)
+        self.attn_scale = float(attention_factor) ** 2
+        self.register_buffer("rope_table", None if inv_freq is None else ops.rope_table(inv_freq, "cpu"), persistent=False)
+
+    @property
+    def rope_kw(self) -> dict:
+        """what the attention ops take besides ``rope_theta``: nothing for a config without RoPE scaling"""
+        kw = {}
+        if self.rope_scale != 1.0:
+            kw["rope_scale"] = self.rope_scale
+        if self.rope_table is not None or self.attn_scale != 1.0:
+            kw.update(rope_table=self.rope_table, attn_scale=self.attn_scale)
+        return kw
+
+    def _rope_eager(self, x, pos):
+        """RoPE of the eager torch prefill path, with the frequencies the ops use"""
+        if self.rope_table is not None:                          # the table is in revolutions per position
+            return rope_llama(x, pos, inv_freq=(self.rope_table.double() * (2.0 * math.pi)).float())
+        return rope_llama(x, pos if self.rope_scale == 1.0 else pos.to(torch.float32) / self.rope_scale, self.rope_theta)
 
     def _decode_qkv(self):
         """q_proj + k_proj + v_proj as one operand of dense_layer_gemm_i4_multi (decode steps)."""
@@ -348,7 +372,8 @@ class LlamaAttention(nn.Module):
                 k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, self._decode_kv_pair(), f32_mask=0b11)
             else:
                 k32, v32 = self.k_proj.forward_f32(hidden_states), self.v_proj.forward_f32(hidden_states)
-            o = _append_and_decode(self.fusion, q_proj.view(rows, nh, hd), k32, v32, decode_kv, self.layer_idx, self.rope_theta)
+            o = _append_and_decode(self.fusion, q_proj.view(rows, nh, hd), k32, v32, decode_kv, self.layer_idx, self.rope_theta,
+                                   **self.rope_kw)
             return self.o_proj(ops.reorder_fp16_i4(o.view(rows, self.hidden_size), self.reorder_index))
         k_u4, k_sz = self.k_proj(hidden_states)
         v_u4, v_sz = self.v_proj(hidden_states)
@@ -364,7 +389,7 @@ class LlamaAttention(nn.Module):
                 # every prefill request in ONE launch, over its cached prefix and its new tokens (csrc/prefill_i4.hip)
                 q = q_proj[:blen.doff].view(-1, nh, hd)
                 o = ops.batch_prefill_i4(q, blen.indptr, prefill_kv, self.layer_idx, rope_theta=self.rope_theta,
-                                         max_q_len=max(blen.prefills))
+                                         max_q_len=max(blen.prefills), **self.rope_kw)
                 outs.append(o.view(blen.doff, self.hidden_size))
             else:
                 kf, vf = dequant_kv_u4(k, ks), dequant_kv_u4(v, vs)
@@ -374,9 +399,10 @@ class LlamaAttention(nn.Module):
                 for q_len in blen.prefills:
                     sl = slice(beg, beg + q_len)
                     pos = torch.arange(q_len, device=q_proj.device)
-                    q = rope_llama(q_proj[sl].view(q_len, nh, hd).float(), pos, self.rope_theta).transpose(0, 1)
-                    kk = rope_llama(kf[sl], pos, self.rope_theta).transpose(0, 1)
-                    o = torch.nn.functional.scaled_dot_product_attention(q, kk, vf[sl].transpose(0, 1), is_causal=True)
+                    q = self._rope_eager(q_proj[sl].view(q_len, nh, hd).float(), pos).transpose(0, 1)
+                    kk = self._rope_eager(kf[sl], pos).transpose(0, 1)
+                    sdpa_scale = {} if self.attn_scale == 1.0 else {"scale": self._scale * self.attn_scale}
+                    o = torch.nn.functional.scaled_dot_product_attention(q, kk, vf[sl].transpose(0, 1), is_causal=True, **sdpa_scale)
                     outs.append(o.transpose(0, 1).reshape(q_len, self.hidden_size).to(q_proj.dtype))
                     beg += q_len
         if blen.decode > 0:
@@ -385,7 +411,7 @@ class LlamaAttention(nn.Module):
             ops.append_kv_i4(decode_kv, k_u4[blen.doff:].view(blen.decode, nkv, hd // 2),
                              v_u4[blen.doff:].view(blen.decode, nkv, hd // 2), k_sz[blen.doff:].view(blen.decode, nkv, 2),
                              v_sz[blen.doff:].view(blen.decode, nkv, 2), self.layer_idx)
-            o = ops.batch_decode_i4(q.contiguous(), decode_kv, self.layer_idx, rope_theta=self.rope_theta)
+            o = ops.batch_decode_i4(q.contiguous(), decode_kv, self.layer_idx, rope_theta=self.rope_theta, **self.rope_kw)
             outs.append(o.view(blen.decode, self.hidden_size))
         attn = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
         return self.o_proj(ops.reorder_fp16_i4(attn.contiguous(), self.reorder_index))
@@ -430,10 +456,12 @@ class LlamaDecoderLayer(nn.Module):
         splits = ops.decode_splits(rows, decode_kv, at.num_heads) if (mask & 2) and self.fusion.merge_in_o_proj else 1
         if splits >= 2 and ops.merge_q_gemm_fits(rows, hs, 1, hs, splits):
             # the KV-split merge in front of o_proj's quantiser, inside o_proj's launch (round 6): same bits, a launch fewer
-            part = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta, merge=False)
+            part = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta, merge=False,
+                                      **at.rope_kw)
             (attn,) = ops.dense_layer_gemm_i4_merge_q(part, splits, at.o_proj.single(), reorder_index=at.reorder_index)
         else:
-            o = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta).view(rows, hs)
+            o = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta,
+                                   **at.rope_kw).view(rows, hs)
             if mask & 2:
                 (attn,), _ = ops.dense_layer_gemm_i4_multi_q("reorder", o, at.o_proj.single(), reorder_index=at.reorder_index)
             else:

@@ -87,12 +87,12 @@ class LlamaDecoderLayerWithLora(LlamaDecoderLayer):
             assert prefill_kv is not None
             ops.init_kv_i4(prefill_kv, k_u4[:doff], v_u4[:doff], k_sz[:doff], v_sz[:doff], blen.indptr, layer_idx)
             o = ops.batch_prefill_i4(q[:doff].view(-1, nh, hd), blen.indptr, prefill_kv, layer_idx, rope_theta=at.rope_theta,
-                                     max_q_len=max(blen.prefills))
+                                     max_q_len=max(blen.prefills), **at.rope_kw)
             outs.append(o.view(doff, at.hidden_size))
         if blen.decode > 0:
             assert decode_kv is not None
             ops.append_kv_i4(decode_kv, k_u4[doff:], v_u4[doff:], k_sz[doff:], v_sz[doff:], layer_idx)
-            o = ops.batch_decode_i4(q[doff:].view(blen.decode, nh, hd), decode_kv, layer_idx, rope_theta=at.rope_theta)
+            o = ops.batch_decode_i4(q[doff:].view(blen.decode, nh, hd), decode_kv, layer_idx, rope_theta=at.rope_theta, **at.rope_kw)
             outs.append(o.view(blen.decode, at.hidden_size))
         attn = (outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)).contiguous()
         o = at.o_proj(ops.reorder_fp16_i4(attn, at.reorder_index))

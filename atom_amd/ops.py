@@ -695,7 +695,35 @@ def _decode_outputs(q, merge, ws_bytes, splits):
     return None, part, part
 
 
-def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True):
+def rope_table(inv_freq, device) -> torch.Tensor:
+    """The per-pair frequency table of ``batch_decode_i4`` / ``batch_prefill_i4`` (``rope_table=``) from HF-style ``inv_freq`` -- 64
+    values in RADIANS per position, pair i = dims (i, i + 64): divided by 2 pi in float64 and rounded ONCE to fp32, on ``device``.  The
+    kernels work in revolutions and use the table as loaded, so the fp32 values returned here are the definition of the angles."""
+    import numpy as np
+    f = inv_freq.detach().cpu().numpy() if isinstance(inv_freq, torch.Tensor) else inv_freq
+    f = np.asarray(f, dtype=np.float64).reshape(-1)
+    if f.shape != (64,):
+        raise ValueError(f"inv_freq must hold 64 values (head_dim 128), got {f.shape[0]}")
+    return torch.from_numpy((f / (2.0 * np.pi)).astype(np.float32)).to(device)
+
+
+def _rope_args(rope_table, attn_scale, device):
+    """(rope_table pointer or None, attn_scale) of the _rope entry points, checked; None where both are at their defaults (the call
+    then goes to the entry point without them)"""
+    if rope_table is None and isinstance(attn_scale, (int, float)) and float(attn_scale) == 1.0:
+        return None
+    if rope_table is not None:
+        t = rope_table
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.shape == (64,) and t.is_contiguous()):
+            what = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise TypeError(f"rope_table must be a contiguous float32 CUDA tensor of [64] (ops.rope_table), got {what}")
+        if t.device != device:
+            raise TypeError(f"rope_table lives on {t.device}, q on {device}")
+    return (None if rope_table is None else rope_table.data_ptr()), float(attn_scale)
+
+
+def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True,
+                    rope_table: torch.Tensor = None, attn_scale: float = 1.0):
     """Decode attention over the INT4 paged cache, RoPE fused.  Reference: punica/ops/__init__.py:21-30 ->
     FlashInferBatchDecodeKernel_i4 (rope_theta 1e4, rope_scale 1 hard-coded there).  q fp16 [batch, heads, 128].
     ``append_kv=(k_f32, v_f32)`` (round 6): quant_append_kv_i4 of this step's FP32 k / v projections inside the same launch
@@ -704,7 +732,11 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     [batch, heads, splits, 130] (a tensor of their own, not the shared workspace) for dense_layer_gemm_i4_merge_q.
     Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G); then the GQA op
     (atom_batch_decode_gqa_i4: each K/V tile read once per group, the prefill op's fp16 matrix-core numerics) runs, ``merge=False``
-    returns [batch, q heads, decode_splits(batch, kv, q heads), 130], and ``append_kv`` is refused (append with quant_append_kv_i4)."""
+    returns [batch, q heads, decode_splits(batch, kv, q heads), 130], and ``append_kv`` is refused (append with quant_append_kv_i4).
+    ``rope_table`` (RoPE scaling: Llama 3.1 "llama3", YaRN): float32 [64] on the device from ``ops.rope_table`` -- the frequency of
+    every RoPE pair, read by the launch (a fixed address under graph replay); with it ``rope_theta`` / ``rope_scale`` are ignored.
+    ``attn_scale`` multiplies the logits (YaRN: attention_factor ** 2).  Both at their defaults: the entry points and bits of a call
+    without them; otherwise the ``_rope`` entry points, for every form above (``append_kv=``, ``merge=False``, grouped-query)."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
@@ -718,6 +750,7 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq if gqa else None)
     lib = L.lib()
     name = "atom_batch_decode_gqa_i4" if gqa else "atom_batch_decode_i4"
+    rope = _rope_args(rope_table, attn_scale, q.device)
     plan = dims[:1] + dims[3:-1] + (max_pages,)              # (batch, [query heads,] K/V heads, page size, max_pages): what the plan queries take
     ws_bytes = getattr(lib, name + "_workspace_bytes")(*plan)
     o, ws, ret = _decode_outputs(q, merge, ws_bytes, None if merge else getattr(lib, name + "_splits")(*plan))
@@ -725,21 +758,27 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     if append_kv is not None:                                # (the MHA op only)
         _require_kv_f32(kv, *append_kv)
         name, new_kv = "atom_batch_decode_append_i4", tuple(t.data_ptr() for t in append_kv)
-    st = getattr(lib, name)(L.ptr(o), q.data_ptr(), *new_kv, *ptrs, *dims, float(rope_theta), float(rope_scale), max_pages, L.ptr(ws),
-                            ws_bytes, L.current_stream(q.device))
+    if rope is not None:                                     # the _rope entries: the grouped-query one serves the MHA op too (G = 1)
+        if name == "atom_batch_decode_i4":
+            name, dims = "atom_batch_decode_gqa_i4", dims[:3] + (num_heads,) + dims[3:]
+        name += "_rope"
+    st = getattr(lib, name)(L.ptr(o), q.data_ptr(), *new_kv, *ptrs, *dims, float(rope_theta), float(rope_scale), *(rope or ()), max_pages,
+                            L.ptr(ws), ws_bytes, L.current_stream(q.device))
     L.check(st, name)
     return ret
 
 
 def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
-                     max_q_len: int = None):
+                     max_q_len: int = None, rope_table: torch.Tensor = None, attn_scale: float = 1.0):
     """Prefill / chunked-prefill attention over the INT4 paged cache, causal, RoPE fused (atom_batch_prefill_i4).  q fp16
     [T, heads, 128] (not yet rotated); qo_indptr int32 [batch + 1] on the device: sequence b's queries are rows
     qo_indptr[b] .. qo_indptr[b+1] and its LAST positions in the cache (already written there, init_kv_i4).  ``max_q_len``: host-side
     bound of every sequence's query count (default T; it sizes the grid).  No host synchronisation: capturable in a graph.  With one
     query per sequence the output is batch_decode_i4's (fp16 matrix-core operands: within rounding of it).
     Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G,
-    atom_batch_prefill_gqa_i4: each staged K/V tile serves the whole group)."""
+    atom_batch_prefill_gqa_i4: each staged K/V tile serves the whole group).
+    ``rope_table`` / ``attn_scale``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_rope; both at their defaults: the call
+    without them)."""
     _require_cuda_half(q, "q")
     _require_cuda(qo_indptr, kv.data, kv.param)
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
@@ -755,8 +794,10 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     ws_bytes = lib.atom_batch_prefill_gqa_i4_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
     ws = _workspace(q.device, ws_bytes) if ws_bytes else None
     o = torch.empty_like(q)
-    st = lib.atom_batch_prefill_gqa_i4(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
-                                       float(rope_scale), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+    rope = _rope_args(rope_table, attn_scale, q.device)
+    fn = lib.atom_batch_prefill_gqa_i4 if rope is None else lib.atom_batch_prefill_gqa_i4_rope
+    st = fn(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta), float(rope_scale),
+            *(rope or ()), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
     L.check(st, "atom_batch_prefill_i4" if nq == num_heads else "atom_batch_prefill_gqa_i4")
     return o
 

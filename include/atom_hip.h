@@ -487,6 +487,39 @@ int atom_batch_prefill_gqa_i4(void *o, const void *q, const int32_t *qo_indptr, 
                               float rope_theta, float rope_scale, int max_pages_per_seq, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* RoPE scaling (Llama 3.1 / 3.2 "llama3", YaRN): the three entry points above with a per-pair FREQUENCY TABLE and an ATTENTION SCALE,
+ * inserted behind rope_scale; every other argument, the plan queries (*_workspace_bytes, *_splits) and the partial states (o == NULL)
+ * are the parent's.
+ *   rope_table  device float[64], 4-byte aligned: the frequency of RoPE pair i (dims i, i + 64) in REVOLUTIONS per position, i.e.
+ *               inv_freq_i / (2 pi).  The kernels use it as loaded -- nothing multiplies it -- so the angle of position p is
+ *               2 pi * p * rope_table[i] with the fp32 table value taken exactly: the table is its own definition.  With a table
+ *               rope_theta and rope_scale are checked as before and otherwise ignored.  The launch reads exactly 64 floats; bad values
+ *               (NaN, Inf, negative) give a wrong answer, never a fault.  The product p * rope_table[i] is formed exactly (p as a float:
+ *               exact below 2^24) before its fractional part is taken -- in the prefill / grouped-query kernel for the query always
+ *               and for keys from position 8192 on (below it the rounded product is off by < 1e-4 revolution) --, so positions of
+ *               131,072 cost no accuracy.
+ *   attn_scale  multiplies the logits (folded into the softmax scale on the host); YaRN passes attention_factor^2.
+ * Contract: rope_table == NULL and attn_scale == 1.0f give the parent entry point's bits (the same kernels, launch for launch) and
+ * the parent's error codes.  A call whose only faults are in the parent's arguments returns the parent's code, in the parent's order;
+ * the new faults are reported behind ALL of those: attn_scale not greater than 0 (or NaN) ATOM_ERR_INVALID_ARG, then a table that
+ * is not 4-byte aligned ATOM_ERR_ALIGN.  num_qo_heads == num_kv_heads: the grouped-query entries run the MHA kernels, as their parents. */
+int atom_batch_decode_gqa_i4_rope(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int atom_batch_prefill_gqa_i4_rope(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int atom_batch_decode_append_i4_rope(void *o, const void *q, const void *k_f32, const void *v_f32, void *kv_data, void *kv_param,
+                                     const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int batch,
+                                     int num_layers, int layer_idx, int num_heads, int page_size, int head_dim, float rope_theta,
+                                     float rope_scale, const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
 /* Page tables stepped on the device (csrc/kv_step.hip): rebuilds kv_indptr / kv_indices / last_page_offset -- the layout above, what
  * every attention and append entry point reads -- in ONE launch from buffers at fixed addresses, so that a captured decode step can
  * be replayed for the next token with no host work in between.

@@ -1,13 +1,18 @@
 """Bench of grouped-query attention (GQA) over the INT4 paged KV cache (atom_batch_decode_gqa_i4 / atom_batch_prefill_gqa_i4,
 csrc/prefill_i4.hip), 32 query heads on 8 K/V heads, pages of 16 tokens, warm caches:
-    python tools/gqa_bench.py [--iters K] [--warmup W] [--only decode|prefill|layer|NAME]   (on the GPU box)
+    python tools/gqa_bench.py [--iters K] [--warmup W] [--only decode|prefill|layer|NAME] [--rope-table [--theta-only]]   (on the GPU box)
 
 Per shape, on the same box in one run:
   gqa        the GQA op: 32 query heads on the 8-head cache
   mha_kv     the MHA op on a cache of 8 heads (8 query heads: the same KV bytes)
   mha_rep    the MHA op on the cache replicated to 32 heads (the only way to run a GQA model before the GQA ops)
 and a Llama-3-8B-shaped decode layer (hidden 4096, 32 / 8 heads, intermediate 14336) at context 1024: one decode step per batch size.
-Prints one line per shape and a JSON line with everything."""
+Prints one line per shape and a JSON line with everything.
+
+--rope-table: instead, the Llama-3.1-8B shapes (batch 1 at contexts 1,024 / 8,192 / 32,768 / 131,072 and batch 16 up to 32,768; a decode
+step and a 512-token chunk at the end of each context) with the THETA path (rope_theta = 5e5) and the TABLE path (the Llama 3.1
+frequency table, ops.rope_table) of the same op in one run, each timed twice in alternation (the two figures of a path show the
+run-to-run difference).  --theta-only skips the table path: the same figures from a build that has none."""
 import argparse
 import json
 import os
@@ -106,12 +111,55 @@ def layer(name, batch, iters, warmup):
     return r
 
 
+ROPE_SHAPES = [(1, c) for c in (1024, 8192, 32768, 131072)] + [(16, c) for c in (1024, 8192, 32768)]
+LLAMA31 = dict(rope_parameters=dict(rope_type="llama3", rope_theta=5e5, factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                    original_max_position_embeddings=8192))
+
+
+def rope_table(iters, warmup, theta_only):
+    """theta path against table path, per shape: decode and a 512-token chunk"""
+    paths = {"theta": dict(rope_theta=5e5)}
+    if not theta_only:
+        from atom_amd.e2e.rope import rope_init
+        paths["table"] = dict(rope_theta=5e5, rope_table=ops.rope_table(rope_init(LLAMA31)[2], "cuda"))
+    out = []
+    for batch, ctx in ROPE_SHAPES:
+        pool, kv, _ = _caches([ctx] * batch)
+        q = torch.randn((batch, NQ, 128), device="cuda").half()
+        chunk = 512
+        qc = torch.randn((batch * chunk, NQ, 128), device="cuda").half()
+        qo = torch.arange(batch + 1, dtype=torch.int32, device="cuda") * chunk
+        it = max(3, iters // 4) if batch * ctx >= 1 << 18 else iters          # (the long chunks take milliseconds)
+        r = {"batch": batch, "ctx": ctx, "splits": ops.decode_splits(batch, kv, NQ)}
+        for rnd in (1, 2):
+            for name, kw in paths.items():
+                r[f"decode_{name}_us_{rnd}"] = _time(lambda: ops.batch_decode_i4(q, kv, 0, **kw), iters, warmup)
+                r[f"chunk_{name}_us_{rnd}"] = _time(lambda: ops.batch_prefill_i4(qc, qo, kv, 0, max_q_len=chunk, **kw), it, warmup)
+        line = f"ROPE    b{batch:<3d} c{ctx:<7d}"
+        for op in ("decode", "chunk"):
+            th = [r[f"{op}_theta_us_{i}"] for i in (1, 2)]
+            line += f" {op}: theta {th[0]:9.1f} / {th[1]:9.1f} us"
+            if not theta_only:
+                tb = [r[f"{op}_table_us_{i}"] for i in (1, 2)]
+                r[f"{op}_table_over_theta"] = min(tb) / min(th)
+                line += f"  table {tb[0]:9.1f} / {tb[1]:9.1f} us ({r[f'{op}_table_over_theta']:.3f}x) "
+        print(line, flush=True)
+        out.append(r)
+        del pool, kv
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--rope-table", action="store_true", help="theta path against table path on the Llama-3.1-8B shapes")
+    ap.add_argument("--theta-only", action="store_true", help="with --rope-table: the theta path alone")
     a = ap.parse_args()
+    if a.rope_table:
+        print(json.dumps({"gqa_bench_rope_table": rope_table(a.iters, a.warmup, a.theta_only)}))
+        return
 
     def want(kind, name):
         return a.only in (None, kind, name)
