@@ -188,6 +188,26 @@ __device__ __forceinline__ void lds_dma_sv(const void *sbase, unsigned voff, uns
   else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_ushort %1, %2" ::"s"(m0v), "v"(voff), "s"(sbase) : "memory");
 }
 
+// One 16-byte global store per lane, by cache policy.  ST_PLAIN and ST_NT leave the line dirty in the XCD's L2 until the release at
+// kernel end; ST_WT (sc0 sc1) writes it through and drops it from that L2.  The write-through form has no builtin for 16 bytes and goes
+// through inline asm: the compiler does not count that store (no caller reads the bytes back or waits for them: the kernel's end does),
+// and the trailing s_nop keeps the next instruction from overwriting the data registers before the store has read them.
+enum StoreFlavour : int { ST_PLAIN = 0, ST_WT = 1, ST_NT = 2 };
+template <int FL>
+__device__ __forceinline__ void store16(void *dst, v4u v) {
+  static_assert(FL == ST_PLAIN || FL == ST_WT || FL == ST_NT, "store flavour");
+  if constexpr (FL == ST_NT) __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst));
+  else if constexpr (FL == ST_WT) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+  else *reinterpret_cast<v4u *>(dst) = v;
+}
+// ... at a wave-uniform base + a 32-bit lane offset + a constant: no 64-bit address arithmetic per store
+template <int FL, int IMM>
+__device__ __forceinline__ void store16_sv(char *sbase, unsigned voff, v4u v) {
+  static_assert(IMM >= 0 && IMM < 4096, "instruction offset");
+  if constexpr (FL == ST_WT) asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3 sc0 sc1\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase), "i"(IMM) : "memory");
+  else store16<FL>(sbase + voff + IMM, v);
+}
+
 // u4 code of one value under the _o4 epilogue.  REF = the reference code's arithmetic (no clamp, low 4 bits of the int8 cast;
 // |result| beyond int8 saturates), else clamp to [0, 15] and 0 for an all-equal group.
 template <bool REF>

@@ -1647,10 +1647,36 @@ __device__ __forceinline__ void q_step(QRegs<C, PAIR, SA2> &R, const char *lds, 
 //  * WHOLE (the caller's wave-uniform promise that the tile lies inside the output and that its byte offsets fit 32 bits): a store is
 //    scalar base of the token block's first row + one loop-invariant 32-bit lane offset + instruction offset 64 h -- no bounds compare
 //    and no 64-bit multiply per store.  Ragged tiles keep the checked path.
-template <class C, bool STORE, int NTB, bool WHOLE = false>
+//  * FL: the cache policy of the output stores (StoreFlavour, common.h; -DATOM_Q_ST_FLAVOUR=n in A/B builds), in the STORE forms only.
+//    Write-through: a pure-store kernel with the keeper's lane pattern (tools/probes/store_floor.cpp) holds its waves longer with it than
+//    with plain stores, but its launches follow each other sooner, because nothing is left dirty in the L2s for the release at kernel end;
+//    the keeper pays the longer stores in part and keeps the shorter end (profiles/f6q_write/).  nt stores are slower than plain ones.
+//    (The stores one pair slot earlier, right behind the de-quantisation that makes the block final, measured nothing: same place.)
+//  * ks (the traced instantiation only): stamps 9..13 -- entry, first store issued, slot 8, last MFMA, last store issued.
+#ifdef ATOM_Q_ST_FLAVOUR                     // A/B builds (tools/ab_build.sh)
+constexpr int kQStFlavour = ATOM_Q_ST_FLAVOUR;
+#else
+constexpr int kQStFlavour = ST_WT;
+#endif
+// Timing-only forms (tools build, profiles/f6q_write/): the keeper without its stores, and without its MFMAs and de-quantisation (it
+// stores c as the K loop left it).  Their outputs are garbage; nothing but tools/ab_build.sh builds them.
+#if defined(ATOM_TOOLS) && defined(ATOM_Q_KEEPER_NO_STORE)
+constexpr bool kQKeeperNoStore = true;
+#else
+constexpr bool kQKeeperNoStore = false;
+#endif
+#if defined(ATOM_TOOLS) && defined(ATOM_Q_KEEPER_NO_MATH)
+constexpr bool kQKeeperNoMath = true;
+#else
+constexpr bool kQKeeperNoMath = false;
+#endif
+struct QNoStamp { __device__ __forceinline__ void operator()(int) const {} };
+template <class C, bool STORE, int NTB, bool WHOLE = false, class KS = QNoStamp>
 __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, const char *slot1, int wm, int wn, int lane, float (&c)[4][NTB][4],
-                                         int m0, int n0) {
+                                         int m0, int n0, KS ks = KS()) {
   constexpr bool MERGED = true;
+  constexpr int FL = kQStFlavour;
+  ks(9);
   const int l15 = lane & 15, kb = lane >> 4;
   const int sw = (l15 >> 1) & 3;                                       // swizzle key (row >> 2) & 3 of row 2 * l15 + (blk & 1)
   const char *pw = slot + (wn * 64 + 2 * l15) * 64 + ((kb ^ sw) << 4);
@@ -1691,10 +1717,10 @@ __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, 
   auto store_block = [&](int tb) {                                     // fp16 outputs of token block tb: 8 consecutive features per pair
     const int m = m0 + wm * (16 * NTB) + p_row(tb) + 2 * l15;
     if constexpr (!WHOLE) { if (m >= p.M) return; }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    auto half = [&](auto hc) {
+      constexpr int h = decltype(hc)::value;
       const int n = n0 + wn * 64 + 32 * h + 8 * kb;
-      if constexpr (!WHOLE) { if (n >= p.N) continue; }
+      if constexpr (!WHOLE) { if (n >= p.N) return; }
       v4u o;
       half_t *ov = reinterpret_cast<half_t *>(&o);
 #pragma unroll
@@ -1702,13 +1728,17 @@ __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, 
         ov[2 * r] = f2h(c[2 * h][tb][r]);
         ov[2 * r + 1] = f2h(c[2 * h + 1][tb][r]);
       }
-      if constexpr (WHOLE) {
+      if constexpr (kQKeeperNoStore) {
+        asm volatile("" ::"v"(o));
+      } else if constexpr (WHOLE) {
         char *dtb = reinterpret_cast<char *>(p.D + ((int64_t)(m0 + p_row(tb)) * p.N + n0));   // the block's first row: wave-uniform
-        *reinterpret_cast<v4u *>(dtb + dvoff + 64 * h) = o;
+        store16_sv<FL, 64 * h>(dtb, dvoff, o);
       } else {
-        *reinterpret_cast<v4u *>(p.D + (int64_t)m * p.N + n) = o;
+        store16<FL>(p.D + (int64_t)m * p.N + n, o);
       }
-    }
+    };
+    half(std::integral_constant<int, 0>());
+    half(std::integral_constant<int, 1>());
   };
   auto dequant = [&](int j) {                                          // pair slot j: token block j / 2, feature-block pair j % 2
     const int tb = j >> 1, h = j & 1;
@@ -1723,26 +1753,33 @@ __device__ __forceinline__ void q_keeper(const GemmParams &p, const char *slot, 
   for (int i = 0; i < 2 * NTB; ++i) {
     const int tb = i >> 1, h = i & 1;
     __builtin_amdgcn_sched_barrier(0);
+    if (i == NTB) ks(11);
     if (h == 0) sa[tb & 1] = (float)sah[tb & 1];                       // this block's token scale arrived with its fragment
+    if constexpr (!kQKeeperNoMath) {
 #pragma unroll
-    for (int k = 0; k < 2; ++k) acc[i & 1][k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2 * h + k], bf[tb & 1], magic, 0, 0, 0);
-    if constexpr (MERGED) {
+      for (int k = 0; k < 2; ++k) acc[i & 1][k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[2 * h + k], bf[tb & 1], magic, 0, 0, 0);
+      if constexpr (MERGED) {
 #pragma unroll
-      for (int k = 0; k < 2; ++k) acc[i & 1][k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af1[2 * h + k], bf1[tb & 1], acc[i & 1][k], 0, 0, 0);
+        for (int k = 0; k < 2; ++k) acc[i & 1][k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af1[2 * h + k], bf1[tb & 1], acc[i & 1][k], 0, 0, 0);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
+    if (i == 2 * NTB - 1) ks(12);
     if (h == 1 && tb + 2 < NTB) {                                        // the buffer of block tb is free: block tb + 2
       bf[tb & 1] = __builtin_bit_cast(v4i, *reinterpret_cast<const v4u *>(pa + p_row(tb + 2) * 64));
       if constexpr (MERGED) bf1[tb & 1] = __builtin_bit_cast(v4i, *reinterpret_cast<const v4u *>(pa + d1 + p_row(tb + 2) * 64));
       sah[tb & 1] = *reinterpret_cast<const half_t *>(psa + p_row(tb + 2) * 4);
     }
-    if constexpr (STORE) { if (h == 1 && tb >= 1) store_block(tb - 1); }   // final since slot i - 1's de-quantisation
+    if constexpr (STORE) {                                               // final since slot i - 1's de-quantisation
+      if (h == 1 && tb >= 1) { store_block(tb - 1); if (tb == 1) ks(10); }
+    }
     __builtin_amdgcn_sched_barrier(0);
-    if (i > 0) dequant(i - 1);
+    if constexpr (!kQKeeperNoMath) { if (i > 0) dequant(i - 1); }
   }
   __builtin_amdgcn_sched_barrier(0);
-  dequant(2 * NTB - 1);
+  if constexpr (!kQKeeperNoMath) dequant(2 * NTB - 1);
   if constexpr (STORE) store_block(NTB - 1);
+  ks(13);
 }
 
 // GU != 0: the weight rows are gate_proj / up_proj interleaved per wave (32 gate features, then the same 32 up features), so a
@@ -1969,8 +2006,13 @@ __global__ __launch_bounds__(C::NT, C::OCC) void gemm_w4a4_f6q_kernel(GemmParams
 #else
     const bool whole = m0 + C::BM <= p.M && n0 + C::BN <= p.N && p.N <= (1 << 21);   // decided once per workgroup; see q_keeper
 #endif
-    if (whole) q_keeper<C, true, 8, true>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
-    else q_keeper<C, true, 8, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+    if constexpr (TR) {                                     // (the traced build stamps inside the keeper too)
+      if (whole) q_keeper<C, true, 8, true>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0, kstamp);
+      else q_keeper<C, true, 8, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0, kstamp);
+    } else {
+      if (whole) q_keeper<C, true, 8, true>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+      else q_keeper<C, true, 8, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
+    }
   } else {
     q_keeper<C, false>(p, slot_of(G), slot_of(G + 1), wm, wn, lane, c, m0, n0);
   }

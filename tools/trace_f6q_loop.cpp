@@ -51,6 +51,9 @@ int main(int argc, char **argv) {
              "barrier +%d | keeper + stores issued +%d | stores done +%d | total %d cycles = %.2f us, %.0f MHz\n", w, d(e[0], t00), d(e[1], e[0]), d(e[2], e[1]),
              d(e[3], e[2]), G, d(e[4], e[3]), d(e[4], e[3]) / (double)G, d(e[5], e[4]), d(e[6], e[5]), d(e[7], e[6]), d(e[8], e[7]), d(e[8], e[0]),
              d(e[63], e[62]) / 100.0, mhz);
+      if (e[9])                                             // stamps inside the keeper (a library from before them leaves 9..13 zero)
+        printf("         keeper: entry +0 | first store issued +%d | slot 8 +%d | last MFMA +%d | last store issued +%d | vmcnt(0) +%d\n", d(e[10], e[9]),
+               d(e[11], e[9]), d(e[12], e[9]), d(e[13], e[9]), d(e[8], e[9]));
     }
   }
   return 0;
