@@ -96,6 +96,12 @@ SIGNATURES = {
     "atom_batch_decode_gqa_i4_rope": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_batch_prefill_gqa_i4_rope": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
     "atom_batch_decode_append_i4_rope": (_int, [_vp] * 9 + [_int] * 6 + [_f32, _f32, _vp, _f32, _int, _vp, ctypes.c_size_t, _vp]),
+    # sliding window: the _rope lists with `window` behind attn_scale; the plan queries with `window` last
+    "atom_batch_decode_gqa_i4_win": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_prefill_gqa_i4_win": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_decode_gqa_i4_win_workspace_bytes": (ctypes.c_size_t, [_int] * 6),
+    "atom_batch_decode_gqa_i4_win_splits": (_int, [_int] * 6),
+    "atom_batch_prefill_gqa_i4_win_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 7),
     "atom_kv_step_i4": (_int, [_vp] * 7 + [_int] * 4 + [_vp]),
     "atom_moe_max_tiles": (_i64, [_i64, _int]),
     "atom_moe_route_topk": (_int, [_vp, _i64, _int, _int] + [_vp] * 9),

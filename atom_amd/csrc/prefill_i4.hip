@@ -68,6 +68,7 @@ struct PrefillParams {
   float qk_scale, log2_theta, rope_inv_scale;
   int G, Nq;         // GQA kernel only: query heads per K/V head, query heads (N * G); qo_indptr NULL = one query per sequence
   const float *rope_table;   // kTable kernels only: float[64], revolutions per position of pair i (the _rope entry points)
+  int window;        // kWindow kernels only: W >= 1, the query at position p sees keys p - W < j <= p (the _win entry points)
 };
 
 // sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
@@ -92,7 +93,12 @@ __device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * 
 // kTable (the _rope entry points): the frequency of pair i is p.rope_table[i] as loaded; log2_theta / rope_inv_scale are not read.  The
 // query's angle is formed exactly (rope_math.h), and so is a key's from position kRopeExactFrom on: the staging is VALU-bound, so the
 // choice is made per key tile (workgroup-uniform) and is a template argument of the staging code.
-template <bool kGqa, bool kTable = false>
+// kWindow (the _win entry points): sliding window W = p.window, the row at position p sees keys p - W < j <= p, the bound taken from
+// each row's own position.  The block's tiles start at the tile of its first row's lowest key and the KV splits divide that range (a
+// split that comes out empty writes the empty state m = -inf, l = 0, zeros, which decode_merge_kernel takes); a wave skips the tiles
+// wholly below its lowest row's bound, and the lower select runs only on tiles that cross some row's bound -- the causal mask's
+// scheme, mirrored.  A row whose keys so far are all masked stays NaN-free through m_use.
+template <bool kGqa, bool kTable = false, bool kWindow = false>
 __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
   __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
   __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
@@ -120,8 +126,15 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int prefix = len - q_b;                           // position of query 0
   const int kend = prefix + (min(q0 + kPfRows, nrows) + G - 1) / G;   // keys this block sees: 0 .. kend-1
   const int ntiles = kend > 0 ? (kend + kPfKeys - 1) / kPfKeys : 0;
-  const int chunk = (ntiles + p.splits - 1) / p.splits;
-  const int t0 = sp * chunk, t1 = min(ntiles, t0 + chunk);
+  int t0, t1;
+  if constexpr (kWindow) {                                // the splits divide [tlo, ntiles): tlo holds the lowest key of the block's first row
+    const int tlo = max(prefix + q0 / G - p.window + 1, 0) / kPfKeys;
+    const int chunk = (max(ntiles - tlo, 0) + p.splits - 1) / p.splits;
+    t0 = tlo + sp * chunk, t1 = min(ntiles, t0 + chunk);
+  } else {
+    const int chunk = (ntiles + p.splits - 1) / p.splits;
+    t0 = sp * chunk, t1 = min(ntiles, t0 + chunk);
+  }
 
   if (tid < 64) {  // decode.cuh:535-539 / batch_decode_kernel: freq = rope_inv_scale * theta^(-2 i / 128), here in revolutions
     if constexpr (kTable)
@@ -250,6 +263,9 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
     if (tile + 1 < t1) regs = load(tile + 1);             // in flight during this tile's products
     const int kt0 = tile * kPfKeys;
     if (!wave_live || kt0 > pmax_w) continue;             // (wave-uniform) no row of this wave sees a key of this tile
+    if constexpr (kWindow) {
+      if (kt0 + kPfKeys - 1 < pmin_w - p.window + 1) continue;   // (wave-uniform) ... the tile lies below every row's window
+    }
     // ---- S^T = K . Q^T
     v4f S[4];
     const char *kl = reinterpret_cast<const char *>(Ks);
@@ -264,6 +280,8 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
     }
     // ---- online softmax; lane holds row li's scores of keys kt0 + 16 kt + 4 g + r
     const bool masked = kt0 + kPfKeys - 1 > pmin_w;       // (wave-uniform) some key of the tile is past some row's position
+    [[maybe_unused]] bool lower = false;
+    if constexpr (kWindow) lower = kt0 <= pmax_w - p.window;
     float mt = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
@@ -271,6 +289,9 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
       for (int r = 0; r < 4; ++r) {
         float s = S[kt][r] * p.qk_scale;
         if (masked && kt0 + 16 * kt + 4 * g + r > pos) s = -INFINITY;
+        if constexpr (kWindow) {                          // (lower: wave-uniform) some key of the tile is below some row's window
+          if (lower && kt0 + 16 * kt + 4 * g + r <= pos - p.window) s = -INFINITY;
+        }
         S[kt][r] = s;
         mt = fmaxf(mt, s);
       }
@@ -341,10 +362,12 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
 
 // KV splits: only where the query blocks leave the chip short of work (short chunks on long prefixes).  Aim at ~2 workgroups per CU
 // (256 CUs) with at least 4 key tiles per split.
-static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages) {
+// win_tiles (the _win entry points; 0: no window): the most key tiles a query block touches under the window, see prefill_plan.
+static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages, int64_t win_tiles = 0) {
   if (max_pages <= 0) return 1;
   const int64_t blocks = (int64_t)batch * N * ((max_q_len + kPfRows - 1) / kPfRows);
-  const int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
   if (blocks >= 512 || tiles < 8) return 1;
   int64_t s = (512 + blocks - 1) / blocks;
   s = std::min<int64_t>(s, tiles / 4);
@@ -362,9 +385,11 @@ static int gqa_group(int num_qo_heads, int num_kv_heads) {   // G, or 0 for a re
 // Decode: a unit is (sequence, K/V head) -- one workgroup streams the unit's KV range (or one split of it) once for the whole group.
 // Splits: the decode op's cost model (kv_i4.hip decode_splits_total) with units in place of (sequence, head) pairs, 64-key tiles, at
 // least 2 tiles per split and 512 resident workgroups (2 per CU: 140 VGPRs + 32 AGPRs, 2 waves per SIMD).
-static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages) {
+static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, int64_t win_tiles = 0) {
   if (max_pages <= 0) return 1;
-  const int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys, units = (int64_t)batch * num_kv_heads;
+  int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
+  const int64_t units = (int64_t)batch * num_kv_heads;
   const int64_t smax = std::max<int64_t>(std::min<int64_t>(tiles / 2, 32), 1);
   int best = 1;
   double best_cost = 1e30;
@@ -377,39 +402,47 @@ static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages) 
 }
 
 // The plan of a call: query rows of a (sequence, K/V head) at most -- max_q_len * G, or G for the decode entry (one query per
-// sequence) --, the query blocks they make, and the KV splits by the entry's policy.
+// sequence) --, the query blocks they make, and the KV splits by the entry's policy.  window (the _win entry points; 0: none): the
+// policies see the most key tiles a query block can touch under the window in place of the cache's -- a block's rows span
+// (min(rows, 64) - 1) / G positions, so its keys are n = window + that span contiguous ones, which touch (n + 62) / 64 + 1 tiles at
+// the worst alignment; never more than the cache's tiles, so a window that covers the cache gives the un-windowed plan.
 struct PrefillPlan {
   int rows, nqb, splits;
 };
-static PrefillPlan prefill_plan(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages) {
+static PrefillPlan prefill_plan(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
+                                int window = 0) {
   PrefillPlan pl;
   pl.rows = decode ? G : (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
   pl.nqb = (int)(((int64_t)pl.rows + kPfRows - 1) / kPfRows);
-  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages) : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages);
+  const int64_t win_tiles = window > 0 ? ((int64_t)window + (std::min(pl.rows, kPfRows) - 1) / G + kPfKeys - 2) / kPfKeys + 1 : 0;
+  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages, win_tiles)
+                     : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages, win_tiles);
   return pl;
 }
 
-static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages) {
+static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
+                                      int window = 0) {
   if (total_q < 1 || batch < 1 || num_kv_heads < 1 || P < 16 || max_q_len < 1) return 0;
-  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages).splits;
+  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages, window).splits;
   return s > 1 ? partial_state_bytes(total_q * num_kv_heads * G, s) : 0;
 }
 
 // The one host path of batch_prefill_kernel.  decode: the grouped-query decode entry -- one query per sequence (no qo_indptr, total_q =
 // batch), and `o` may be NULL: the partial states stay in the workspace un-merged, as atom_batch_decode_i4 leaves them.  The prefill
-// entries refuse total_q / max_q_len (shape) before they look at alignment; the decode entry has no such arguments.
+// entries refuse total_q / max_q_len (shape) before they look at alignment; the decode entry has no such arguments.  window: NULL, or
+// the _win entries' argument (checked behind every other fault); those run the kWindow instantiations, the GQA form at every G.
 static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
                           const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
                           int batch, int num_layers, int layer_idx, int G, int num_kv_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, const float *rope_table, float attn_scale, int max_pages, void *workspace,
-                          size_t workspace_bytes, void *stream) {
+                          size_t workspace_bytes, void *stream, const int *window = nullptr) {
   const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
                           page_size, head_dim);
   if (st != ATOM_OK) return st;
   if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f) || (!decode && (!o || !qo_indptr))) return ATOM_ERR_INVALID_ARG;
   if (!decode && (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1)) return ATOM_ERR_SHAPE;
   if ((o && !aligned16(o)) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
-  PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages);
+  PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages, window ? std::max(*window, 0) : 0);
   const int num_qo_heads = num_kv_heads * G;
   const int64_t rows_heads = total_q * num_qo_heads;
   if (pl.splits > 1 && !workspace_holds(workspace, workspace_bytes, rows_heads, pl.splits)) pl.splits = 1;
@@ -417,6 +450,7 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   const int64_t grid = (int64_t)pl.nqb * batch * num_kv_heads * pl.splits;
   if (grid > 0x7fffffff || rows_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
   if (const int rs = check_rope_table(rope_table, attn_scale)) return rs;   // (the _rope entries' own faults: behind every older one)
+  if (window && *window < 1) return ATOM_ERR_INVALID_ARG;                    // (the _win entries' own fault: behind those)
   PrefillParams p;                                        // by name: the fields' order is the kernel's business
   p.data = (const uint8_t *)kv_data, p.param = (const half_t *)kv_param;
   p.kv_indptr = kv_indptr, p.kv_indices = kv_indices, p.last_page_offset = last_page_offset, p.qo_indptr = qo_indptr;
@@ -426,8 +460,14 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   p.qk_scale = kLog2e / sqrtf((float)kHeadDim) * attn_scale, p.log2_theta = log2f(rope_theta), p.rope_inv_scale = 1.0f / rope_scale;
   p.G = G, p.Nq = num_qo_heads;                           // (batch_prefill_kernel<false> reads neither)
   p.rope_table = rope_table;
+  p.window = window ? *window : 0;                        // (only the kWindow instantiations read it)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (rope_table) {                                       // the same plan, the kTable instantiation of the same kernel
+  if (window) {                                           // the GQA form for every head ratio, with or without a table
+    if (rope_table)
+      hipLaunchKernelGGL((batch_prefill_kernel<true, true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_prefill_kernel<true, false, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  } else if (rope_table) {                                       // the same plan, the kTable instantiation of the same kernel
     if (G == 1 && !decode)
       hipLaunchKernelGGL((batch_prefill_kernel<false, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
     else
@@ -533,6 +573,52 @@ int atom_batch_decode_gqa_i4_rope(void *o, const void *q, const void *kv_data, c
   return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
                         layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq,
                         workspace, workspace_bytes, stream);
+}
+
+// ---- sliding window: the _rope entries with `window` behind attn_scale (include/atom_hip.h); always the matrix-core kernel
+
+size_t atom_batch_decode_gqa_i4_win_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                    int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1 ? prefill_workspace_bytes(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window) : 0;
+}
+
+int atom_batch_decode_gqa_i4_win_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0 || batch < 1 || page_size < 16 || window < 1) return 0;
+  return prefill_plan(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window).splits;
+}
+
+size_t atom_batch_prefill_gqa_i4_win_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                     int max_q_len, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1 ? prefill_workspace_bytes(false, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages_per_seq, window)
+                          : 0;
+}
+
+int atom_batch_decode_gqa_i4_win(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                 const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                 int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                 const float *rope_table, float attn_scale, int window, int max_pages_per_seq, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq,
+                        workspace, workspace_bytes, stream, &window);
+}
+
+int atom_batch_prefill_gqa_i4_win(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                  const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                  const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                  int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, int max_pages_per_seq, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
+                        max_pages_per_seq, workspace, workspace_bytes, stream, &window);
 }
 
 }  // extern "C"

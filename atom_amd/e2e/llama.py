@@ -244,8 +244,9 @@ def _append_and_decode(fusion, q, k32, v32, decode_kv, layer_idx, rope_theta, me
     """reference llama.py:168-196 for a pure decode step: this token's k / v into the INT4 paged cache, then attention over it -- one
     launch (DecodeFusion.kv_in_decode) or two; the same cache bytes and the same output either way.  ``merge=False``: the KV-split
     partial states instead of the output (ops.batch_decode_i4).  Grouped-query attention (q with more heads than the cache) always
-    takes two launches: the GQA decode op has no append built in.  ``rope``: LlamaAttention.rope_kw (RoPE scaling; empty by default)."""
-    if fusion.kv_in_decode and q.size(1) == ops._kv_dims(decode_kv)[1]:
+    takes two launches: the GQA decode op has no append built in -- and so does a sliding window, whose op is the matrix-core kernel at
+    every head ratio.  ``rope``: LlamaAttention.rope_kw (RoPE scaling, the window; empty by default)."""
+    if fusion.kv_in_decode and q.size(1) == ops._kv_dims(decode_kv)[1] and rope.get("window") is None:
         return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, append_kv=(k32, v32), merge=merge, **rope)
     ops.quant_append_kv_i4(decode_kv, k32, v32, layer_idx)
     return ops.batch_decode_i4(q, decode_kv, layer_idx, rope_theta=rope_theta, merge=merge, **rope)
@@ -265,7 +266,12 @@ class LlamaAttention(nn.Module):
     RoPE scaling (e2e/rope.py: ``config.rope_parameters`` or ``rope_theta`` + ``rope_scaling``): ``linear`` is the ops' ``rope_scale``;
     ``llama3`` and ``yarn`` put a per-pair frequency table in the non-persistent buffer ``rope_table`` (a fixed device address, absent
     from ``state_dict``) and YaRN's attention_factor ** 2 in ``attn_scale``; every attention call below takes them (``rope_kw``).  A
-    config without scaling allocates nothing and makes the calls it always made; an unsupported type raises here."""
+    config without scaling allocates nothing and makes the calls it always made; an unsupported type raises here.
+    Sliding-window attention: ``config.sliding_window`` = W (Mistral-7B-v0.1: 4096) -- the query at position p sees keys
+    p - W < j <= p.  With ``config.layer_types`` only the layers marked "sliding_attention" are windowed; ``use_sliding_window`` False
+    switches it off; a non-positive value raises.  The window travels in ``rope_kw`` to every attention call (the ops' ``window=``);
+    a windowed layer's prefill always attends through ops.batch_prefill_i4 (the torch route has no lower bound), and its decode step
+    appends and attends in two launches.  Pages behind the window stay allocated.  None / absent: the calls it always made."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -293,6 +299,22 @@ class LlamaAttention(nn.Module):
         self.rope_theta, self.rope_scale, inv_freq, attention_factor = rope_init(config)
         self.attn_scale = float(attention_factor) ** 2
         self.register_buffer("rope_table", None if inv_freq is None else ops.rope_table(inv_freq, "cpu"), persistent=False)
+        self.window = self._config_window(config, layer_idx)
+
+    @staticmethod
+    def _config_window(config, layer_idx):
+        """this layer's sliding window (an int >= 1) or None"""
+        w = getattr(config, "sliding_window", None)
+        if w is None:
+            return None
+        if isinstance(w, bool) or int(w) != w or int(w) < 1:
+            raise ValueError(f"config.sliding_window must be a positive integer or None, got {w!r}")
+        if getattr(config, "use_sliding_window", True) is False:
+            return None
+        types = getattr(config, "layer_types", None)
+        if types is not None and types[layer_idx] != "sliding_attention":
+            return None
+        return int(w)
 
     @property
     def rope_kw(self) -> dict:
@@ -302,6 +324,8 @@ class LlamaAttention(nn.Module):
             kw["rope_scale"] = self.rope_scale
         if self.rope_table is not None or self.attn_scale != 1.0:
             kw.update(rope_table=self.rope_table, attn_scale=self.attn_scale)
+        if self.window is not None:
+            kw["window"] = self.window
         return kw
 
     def _rope_eager(self, x, pos):
@@ -385,7 +409,7 @@ class LlamaAttention(nn.Module):
             ks = k_sz[:blen.doff].view(-1, nkv, 2)
             vs = v_sz[:blen.doff].view(-1, nkv, 2)
             ops.init_kv_i4(prefill_kv, k, v, ks, vs, blen.indptr, self.layer_idx)
-            if static_prefill or self.fusion.prefill_attn or max(prefixes) > 0:
+            if static_prefill or self.fusion.prefill_attn or self.window is not None or max(prefixes) > 0:
                 # every prefill request in ONE launch, over its cached prefix and its new tokens (csrc/prefill_i4.hip)
                 q = q_proj[:blen.doff].view(-1, nh, hd)
                 o = ops.batch_prefill_i4(q, blen.indptr, prefill_kv, self.layer_idx, rope_theta=self.rope_theta,
@@ -453,7 +477,8 @@ class LlamaDecoderLayer(nn.Module):
         else:
             outlier, norms, outlier_scales, norm_scales = il(hidden_states)
             q, k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, at._decode_qkv(), f32_mask=0b110)
-        splits = ops.decode_splits(rows, decode_kv, at.num_heads) if (mask & 2) and self.fusion.merge_in_o_proj else 1
+        splits = ops.decode_splits(rows, decode_kv, at.num_heads, **({} if at.window is None else {"window": at.window})) \
+            if (mask & 2) and self.fusion.merge_in_o_proj else 1
         if splits >= 2 and ops.merge_q_gemm_fits(rows, hs, 1, hs, splits):
             # the KV-split merge in front of o_proj's quantiser, inside o_proj's launch (round 6): same bits, a launch fewer
             part = _append_and_decode(self.fusion, q.view(rows, at.num_heads, at.head_dim), k32, v32, decode_kv, at.layer_idx, at.rope_theta, merge=False,

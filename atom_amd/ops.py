@@ -673,11 +673,24 @@ def _qo_heads(num_qo_heads: int, num_kv_heads: int) -> int:
     return num_qo_heads
 
 
-def decode_splits(batch: int, kv, num_qo_heads: int = None) -> int:
+def _window_arg(window):
+    """``window=`` of the attention ops, checked: None, or an int >= 1"""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"window must be None or an int >= 1 (keys p - window < j <= p), got {window!r}")
+    return window
+
+
+def decode_splits(batch: int, kv, num_qo_heads: int = None, window: int = None) -> int:
     """How many partial states per (sequence, head) batch_decode_i4 produces for this cache (1: none; small batches: one per workgroup of
-    four KV-split waves).  ``num_qo_heads``: the query heads of a grouped-query call (default: the cache's head count)."""
+    four KV-split waves).  ``num_qo_heads``: the query heads of a grouped-query call (default: the cache's head count).  ``window``:
+    of the sliding-window call (atom_batch_decode_gqa_i4_win_splits, the grouped-query plan at every head ratio)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     max_pages = int(getattr(kv, "max_pages", 0))
+    if _window_arg(window) is not None:
+        nq = num_heads if num_qo_heads is None else _qo_heads(int(num_qo_heads), num_heads)
+        return int(L.lib().atom_batch_decode_gqa_i4_win_splits(int(batch), nq, num_heads, page_size, max_pages, window))
     if num_qo_heads is None or num_qo_heads == num_heads:
         return int(L.lib().atom_batch_decode_i4_splits(int(batch), num_heads, page_size, max_pages))
     nq = _qo_heads(int(num_qo_heads), num_heads)
@@ -723,7 +736,7 @@ def _rope_args(rope_table, attn_scale, device):
 
 
 def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True,
-                    rope_table: torch.Tensor = None, attn_scale: float = 1.0):
+                    rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None):
     """Decode attention over the INT4 paged cache, RoPE fused.  Reference: punica/ops/__init__.py:21-30 ->
     FlashInferBatchDecodeKernel_i4 (rope_theta 1e4, rope_scale 1 hard-coded there).  q fp16 [batch, heads, 128].
     ``append_kv=(k_f32, v_f32)`` (round 6): quant_append_kv_i4 of this step's FP32 k / v projections inside the same launch
@@ -736,13 +749,33 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     ``rope_table`` (RoPE scaling: Llama 3.1 "llama3", YaRN): float32 [64] on the device from ``ops.rope_table`` -- the frequency of
     every RoPE pair, read by the launch (a fixed address under graph replay); with it ``rope_theta`` / ``rope_scale`` are ignored.
     ``attn_scale`` multiplies the logits (YaRN: attention_factor ** 2).  Both at their defaults: the entry points and bits of a call
-    without them; otherwise the ``_rope`` entry points, for every form above (``append_kv=``, ``merge=False``, grouped-query)."""
+    without them; otherwise the ``_rope`` entry points, for every form above (``append_kv=``, ``merge=False``, grouped-query).
+    ``window`` (sliding-window attention): an int W >= 1 -- the query at position p sees keys p - W < j <= p, plain causal attention
+    for a sequence no longer than W.  None: exactly the calls above.  With a window atom_batch_decode_gqa_i4_win runs -- the
+    grouped-query (matrix-core) op at every head ratio, MHA caches included --, ``merge=False`` takes its splits from
+    ``decode_splits(batch, kv, q heads, window=W)``, and ``append_kv`` is refused (the fused append lives in the FP32 decode kernel)."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
     gqa = q.dim() == 3 and q.size(1) != num_heads
     nq = _qo_heads(q.size(1), num_heads) if gqa else num_heads
     assert q.shape == (batch, nq, head_dim)
+    if _window_arg(window) is not None:
+        if append_kv is not None:
+            raise ValueError("append_kv= is not built for sliding-window attention (the fused append lives in the FP32 decode kernel): "
+                             "append with quant_append_kv_i4 first")
+        _require_cuda(kv.data, kv.param)
+        assert batch == kv.last_page_offset.numel()
+        ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq)
+        lib = L.lib()
+        plan = (batch, nq, num_heads, page_size, max_pages, window)
+        ws_bytes = lib.atom_batch_decode_gqa_i4_win_workspace_bytes(*plan)
+        o, ws, ret = _decode_outputs(q, merge, ws_bytes, None if merge else lib.atom_batch_decode_gqa_i4_win_splits(*plan))
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_decode_gqa_i4_win(L.ptr(o), q.data_ptr(), *ptrs, *dims, float(rope_theta), float(rope_scale), table, scale, window,
+                                              max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_decode_gqa_i4_win")
+        return ret
     if gqa and append_kv is not None:
         raise ValueError("append_kv= is not built for grouped-query attention: append with quant_append_kv_i4 first")
     _require_cuda(kv.data, kv.param)
@@ -769,7 +802,7 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
 
 
 def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
-                     max_q_len: int = None, rope_table: torch.Tensor = None, attn_scale: float = 1.0):
+                     max_q_len: int = None, rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None):
     """Prefill / chunked-prefill attention over the INT4 paged cache, causal, RoPE fused (atom_batch_prefill_i4).  q fp16
     [T, heads, 128] (not yet rotated); qo_indptr int32 [batch + 1] on the device: sequence b's queries are rows
     qo_indptr[b] .. qo_indptr[b+1] and its LAST positions in the cache (already written there, init_kv_i4).  ``max_q_len``: host-side
@@ -778,7 +811,9 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     Grouped-query attention: q may hold any multiple G of the cache's heads (query head h reads K/V head h // G,
     atom_batch_prefill_gqa_i4: each staged K/V tile serves the whole group).
     ``rope_table`` / ``attn_scale``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_rope; both at their defaults: the call
-    without them)."""
+    without them).
+    ``window``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_win) -- the bound of every query row from that row's own
+    position; None: exactly the calls above."""
     _require_cuda_half(q, "q")
     _require_cuda(qo_indptr, kv.data, kv.param)
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
@@ -791,6 +826,16 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     assert qo_indptr.numel() == batch + 1
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
+    if _window_arg(window) is not None:
+        ws_bytes = lib.atom_batch_prefill_gqa_i4_win_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages, window)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_prefill_gqa_i4_win(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
+                                               float(rope_scale), table, scale, window, max_pages, L.ptr(ws), ws_bytes,
+                                               L.current_stream(q.device))
+        L.check(st, "atom_batch_prefill_gqa_i4_win")
+        return o
     ws_bytes = lib.atom_batch_prefill_gqa_i4_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
     ws = _workspace(q.device, ws_bytes) if ws_bytes else None
     o = torch.empty_like(q)

@@ -520,6 +520,40 @@ int atom_batch_decode_append_i4_rope(void *o, const void *q, const void *k_f32, 
                                      float rope_scale, const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
                                      size_t workspace_bytes, void *stream);
 
+/* Sliding-window attention (Mistral-7B-v0.1, "sliding_attention" layers): the grouped-query _rope entry points with `window` inserted
+ * behind attn_scale, and their plan queries with `window` as the last argument.
+ *   - window = W >= 1: the query at position p sees the keys j with p - W < j <= p -- W keys including its own (HF's
+ *     kv_idx > q_idx - sliding_window).
+ *   - The bound is per query row, from that row's own position: not from its chunk's first row, not from the sequence's end.
+ *   - A sequence no longer than W gets plain causal attention.
+ *   - RoPE (rope_theta / rope_scale / rope_table), attn_scale, the head mapping h -> h / G and the paging are the _rope entries'.
+ *   - Pages behind the window stay allocated and are not read: the call frees nothing.
+ * Both entries run the matrix-core kernel (csrc/prefill_i4.hip, the kWindow instantiations) at EVERY head ratio, num_qo_heads ==
+ * num_kv_heads included -- nothing forwards to the FP32 decode op -- so their numerics are the grouped-query ops' and their plan is
+ * the grouped-query plan: the split policies see the most 64-key tiles a query block can touch under the window (never more than the
+ * cache holds: a window that covers max_pages_per_seq * page_size keys plans as the un-windowed grouped-query op).  Query blocks split
+ * the tiles from their first row's lowest key on; a split that gets no tile writes the empty state (m = -inf, l = 0).
+ * o == NULL (decode entry, splits >= 2) leaves the partial states float [batch][num_qo_heads][splits][130] un-merged, for
+ * atom_gemm_w4a4_multi_merge_q; splits is atom_batch_decode_gqa_i4_win_splits with the same arguments.
+ * Errors: every fault of the _rope entries, in their order; behind ALL of them window < 1 is ATOM_ERR_INVALID_ARG.  The queries
+ * return 0 for window < 1 and for the inputs their parents reject. */
+size_t atom_batch_decode_gqa_i4_win_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                    int window);
+int atom_batch_decode_gqa_i4_win_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window);
+size_t atom_batch_prefill_gqa_i4_win_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                     int max_q_len, int max_pages_per_seq, int window);
+int atom_batch_decode_gqa_i4_win(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                 const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                 int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                 const float *rope_table, float attn_scale, int window, int max_pages_per_seq, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+int atom_batch_prefill_gqa_i4_win(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                  const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                  const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                  int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, int max_pages_per_seq, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 /* Page tables stepped on the device (csrc/kv_step.hip): rebuilds kv_indptr / kv_indices / last_page_offset -- the layout above, what
  * every attention and append entry point reads -- in ONE launch from buffers at fixed addresses, so that a captured decode step can
  * be replayed for the next token with no host work in between.

@@ -1,6 +1,6 @@
 """Bench of grouped-query attention (GQA) over the INT4 paged KV cache (atom_batch_decode_gqa_i4 / atom_batch_prefill_gqa_i4,
 csrc/prefill_i4.hip), 32 query heads on 8 K/V heads, pages of 16 tokens, warm caches:
-    python tools/gqa_bench.py [--iters K] [--warmup W] [--only decode|prefill|layer|NAME] [--rope-table [--theta-only]]   (on the GPU box)
+    python tools/gqa_bench.py [--iters K] [--warmup W] [--only decode|prefill|layer|NAME] [--rope-table [--theta-only] | --window W]   (on the GPU box)
 
 Per shape, on the same box in one run:
   gqa        the GQA op: 32 query heads on the 8-head cache
@@ -12,7 +12,12 @@ Prints one line per shape and a JSON line with everything.
 --rope-table: instead, the Llama-3.1-8B shapes (batch 1 at contexts 1,024 / 8,192 / 32,768 / 131,072 and batch 16 up to 32,768; a decode
 step and a 512-token chunk at the end of each context) with the THETA path (rope_theta = 5e5) and the TABLE path (the Llama 3.1
 frequency table, ops.rope_table) of the same op in one run, each timed twice in alternation (the two figures of a path show the
-run-to-run difference).  --theta-only skips the table path: the same figures from a build that has none."""
+run-to-run difference).  --theta-only skips the table path: the same figures from a build that has none.
+
+--window W: instead, sliding-window attention (atom_batch_decode_gqa_i4_win / atom_batch_prefill_gqa_i4_win).  Per batch 1 / 16 / 64
+the windowed decode op at contexts 4 W and 8 W against the un-windowed op of the same build at context W (the same keys staged) and at
+the full context, and the windowed prefill of 1 x 2 W against the un-windowed one; every figure timed twice in alternation (the two
+figures of the un-windowed op at context W are the spread the comparison is read against)."""
 import argparse
 import json
 import os
@@ -149,6 +154,52 @@ def rope_table(iters, warmup, theta_only):
     return out
 
 
+def window(W, iters, warmup):
+    """windowed decode at 4 W / 8 W against un-windowed at W and at the full context; windowed prefill of 1 x 2 W against un-windowed"""
+    out = {"window": W, "decode": [], "prefill": []}
+    for batch in (1, 16, 64):
+        q = torch.randn((batch, NQ, 128), device="cuda").half()
+        pool0, kv0, _ = _caches([W] * batch)
+        r = {"batch": batch, "base_ctx": W, "splits_base": ops.decode_splits(batch, kv0, NQ)}
+        runs = {"base": (kv0, {})}
+        pools = [pool0]
+        for ctx in (4 * W, 8 * W):
+            pool, kv, _ = _caches([ctx] * batch)
+            pools.append(pool)
+            runs[f"win_c{ctx}"] = (kv, {"window": W})
+            runs[f"full_c{ctx}"] = (kv, {})
+            r[f"splits_win_c{ctx}"] = ops.decode_splits(batch, kv, NQ, window=W)
+            r[f"splits_full_c{ctx}"] = ops.decode_splits(batch, kv, NQ)
+        for rnd in (1, 2):
+            for name, (kv, kw) in runs.items():
+                r[f"{name}_us_{rnd}"] = _time(lambda: ops.batch_decode_i4(q, kv, 0, **kw), iters, warmup)
+        base = [r["base_us_1"], r["base_us_2"]]
+        line = f"WINDOW  decode b{batch:<3d} W {W}: un-windowed at ctx {W} {base[0]:8.1f} / {base[1]:8.1f} us (splits {r['splits_base']})"
+        for ctx in (4 * W, 8 * W):
+            wn, fl = [r[f"win_c{ctx}_us_{i}"] for i in (1, 2)], [r[f"full_c{ctx}_us_{i}"] for i in (1, 2)]
+            r[f"win_c{ctx}_over_base"] = min(wn) / min(base)
+            r[f"win_c{ctx}_over_full"] = min(wn) / min(fl)
+            line += (f" | ctx {ctx}: windowed {wn[0]:8.1f} / {wn[1]:8.1f} us (splits {r[f'splits_win_c{ctx}']}, {r[f'win_c{ctx}_over_base']:.3f}x of base) "
+                     f"un-windowed {fl[0]:8.1f} / {fl[1]:8.1f} us")
+        print(line, flush=True)
+        out["decode"].append(r)
+        del pools, runs, kv0
+    n = 2 * W
+    pool, kv, _ = _caches([n])
+    q = torch.randn((n, NQ, 128), device="cuda").half()
+    qo = torch.tensor([0, n], dtype=torch.int32, device="cuda")
+    r = {"q_len": n}
+    it = max(3, iters // 4)
+    for rnd in (1, 2):
+        r[f"win_us_{rnd}"] = _time(lambda: ops.batch_prefill_i4(q, qo, kv, 0, max_q_len=n, window=W), it, warmup)
+        r[f"full_us_{rnd}"] = _time(lambda: ops.batch_prefill_i4(q, qo, kv, 0, max_q_len=n), it, warmup)
+    r["win_over_full"] = min(r["win_us_1"], r["win_us_2"]) / min(r["full_us_1"], r["full_us_2"])
+    print(f"WINDOW  prefill 1x{n} W {W}: windowed {r['win_us_1']:9.1f} / {r['win_us_2']:9.1f} us  un-windowed {r['full_us_1']:9.1f} / "
+          f"{r['full_us_2']:9.1f} us ({r['win_over_full']:.3f}x)", flush=True)
+    out["prefill"].append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -156,7 +207,11 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--rope-table", action="store_true", help="theta path against table path on the Llama-3.1-8B shapes")
     ap.add_argument("--theta-only", action="store_true", help="with --rope-table: the theta path alone")
+    ap.add_argument("--window", type=int, default=None, help="sliding-window attention with this window (4096: Mistral-7B-v0.1)")
     a = ap.parse_args()
+    if a.window is not None:
+        print(json.dumps({"gqa_bench_window": window(a.window, a.iters, a.warmup)}))
+        return
     if a.rope_table:
         print(json.dumps({"gqa_bench_rope_table": rope_table(a.iters, a.warmup, a.theta_only)}))
         return
