@@ -102,7 +102,14 @@ SIGNATURES = {
     "atom_batch_decode_gqa_i4_win_workspace_bytes": (ctypes.c_size_t, [_int] * 6),
     "atom_batch_decode_gqa_i4_win_splits": (_int, [_int] * 6),
     "atom_batch_prefill_gqa_i4_win_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 7),
+    # rolling cache: the _win lists with `kv_start` behind window; plan queries of their own with the _win queries' arguments
+    "atom_batch_decode_gqa_i4_ring": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_prefill_gqa_i4_ring": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_decode_gqa_i4_ring_workspace_bytes": (ctypes.c_size_t, [_int] * 6),
+    "atom_batch_decode_gqa_i4_ring_splits": (_int, [_int] * 6),
+    "atom_batch_prefill_gqa_i4_ring_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 7),
     "atom_kv_step_i4": (_int, [_vp] * 7 + [_int] * 4 + [_vp]),
+    "atom_kv_step_ring_i4": (_int, [_vp] * 7 + [_int] * 5 + [_vp, _vp]),
     "atom_moe_max_tiles": (_i64, [_i64, _int]),
     "atom_moe_route_topk": (_int, [_vp, _i64, _int, _int] + [_vp] * 9),
     "atom_moe_gemm_w4a4_f16": (_int, [_vp] * 15 + [_i64, _i64, _int, _i64, _int, _i64, _int, _int, _int, _vp]),

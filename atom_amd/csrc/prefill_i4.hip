@@ -69,6 +69,7 @@ struct PrefillParams {
   int G, Nq;         // GQA kernel only: query heads per K/V head, query heads (N * G); qo_indptr NULL = one query per sequence
   const float *rope_table;   // kTable kernels only: float[64], revolutions per position of pair i (the _rope entry points)
   int window;        // kWindow kernels only: W >= 1, the query at position p sees keys p - W < j <= p (the _win entry points)
+  const int32_t *kv_start;   // kStart kernels only: int32 [batch], the position of each page list's first token (the _ring entry points)
 };
 
 // sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
@@ -98,8 +99,16 @@ __device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * 
 // split that comes out empty writes the empty state m = -inf, l = 0, zeros, which decode_merge_kernel takes); a wave skips the tiles
 // wholly below its lowest row's bound, and the lower select runs only on tiles that cross some row's bound -- the causal mask's
 // scheme, mirrored.  A row whose keys so far are all masked stays NaN-free through m_use.
-template <bool kGqa, bool kTable = false, bool kWindow = false>
+// kStart (the _ring entry points; only with kGqa and kWindow): the page list of sequence b starts at position start = p.kv_start[b], a
+// multiple of P (kv_step.hip, the ring step), not at 0: len = start + the list's tokens, and load() finds key j in page (j - start) / P
+// of the list.  Everything else stays in ABSOLUTE positions -- prefix, pos, kend, the tile grid tile * 64, both masks, a key's RoPE
+// angle -- so with equal contents and splits the call does what the _win call does on a cache that still lists pages 0 .. : the same
+// operations in the same order.  Keys below `start` are not loaded and staged as zeros (as those past the end); the ring step keeps
+// start <= p - W + 1 for every live row, so the lower select masks them.  tlo is clamped to start / 64: a caller that breaks the
+// guarantee gets a finite, unspecified result and never a read outside the listed pages.
+template <bool kGqa, bool kTable = false, bool kWindow = false, bool kStart = false>
 __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
+  static_assert(!kStart || (kGqa && kWindow), "a list that starts behind position 0 is read only under a window");
   __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
   __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
   __shared__ float rope_fr[64];
@@ -122,13 +131,16 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int q0 = qb * kPfRows;
   if (q0 >= nrows) return;                                // (uniform over the workgroup: before any barrier)
   const int pg0 = p.kv_indptr[b];
-  const int len = (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
+  [[maybe_unused]] int start = 0;                         // position of the page list's first token
+  if constexpr (kStart) start = p.kv_start[b];
+  const int len = start + (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
   const int prefix = len - q_b;                           // position of query 0
   const int kend = prefix + (min(q0 + kPfRows, nrows) + G - 1) / G;   // keys this block sees: 0 .. kend-1
   const int ntiles = kend > 0 ? (kend + kPfKeys - 1) / kPfKeys : 0;
   int t0, t1;
   if constexpr (kWindow) {                                // the splits divide [tlo, ntiles): tlo holds the lowest key of the block's first row
-    const int tlo = max(prefix + q0 / G - p.window + 1, 0) / kPfKeys;
+    int tlo = max(prefix + q0 / G - p.window + 1, 0) / kPfKeys;
+    if constexpr (kStart) tlo = max(tlo, start / kPfKeys);   // (a no-op under the ring step's guarantee: no tile wholly below the list)
     const int chunk = (max(ntiles - tlo, 0) + p.splits - 1) / p.splits;
     t0 = tlo + sp * chunk, t1 = min(ntiles, t0 + chunk);
   } else {
@@ -184,8 +196,11 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   auto load = [&](int tile) -> PfTileRegs {
     PfTileRegs r;
     const int j = tile * kPfKeys + kk;
-    if (j < len) {
-      const int pg = j / P, e = j - pg * P;
+    bool in_list = j < len;
+    if constexpr (kStart) in_list = in_list && j >= start;   // 0 <= (j - start) / P < the list's pages, whatever kv_start holds
+    if (in_list) {
+      const int jl = kStart ? j - start : j;
+      const int pg = jl / P, e = jl - pg * P;
       const int64_t page = p.kv_indices[pg0 + pg];
       const uint8_t *kp = kbase + page * page_bytes + e * 64;
       const half_t *pp = qpbase + page * page_halves + e * 2;
@@ -204,7 +219,8 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   };
   auto stage = [&](int tile, const PfTileRegs &r, auto exact) {   // exact: std::bool_constant -- the product of a key's angle (rope_math.h)
     const int j = tile * kPfKeys + kk;
-    const bool ok = j < len;                              // past the end: zeros (the loaded registers are zeros too, see load)
+    bool ok = j < len;                                    // past the end: zeros (the loaded registers are zeros too, see load)
+    if constexpr (kStart) ok = ok && j >= start;          // ... and so is a key in front of the list
     const float ks = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq & 0xFFFF)) : 0.f;
     const float kz = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq >> 16)) : 0.f;
     const float vs = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.vq & 0xFFFF)) : 0.f;
@@ -363,10 +379,17 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
 // KV splits: only where the query blocks leave the chip short of work (short chunks on long prefixes).  Aim at ~2 workgroups per CU
 // (256 CUs) with at least 4 key tiles per split.
 // win_tiles (the _win entry points; 0: no window): the most key tiles a query block touches under the window, see prefill_plan.
-static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages, int64_t win_tiles = 0) {
+// ring (the _ring entry points): a list of max_pages pages that starts at a multiple of P, not of 64 -- its n = max_pages * P tokens
+// touch up to (n + 62) / 64 + 1 tiles of the absolute grid (the bound of n contiguous keys at the worst alignment, as prefill_plan's).
+static int64_t cache_tiles(int P, int max_pages, bool ring) {
+  const int64_t n = (int64_t)max_pages * P;
+  return ring ? (n + kPfKeys - 2) / kPfKeys + 1 : (n + kPfKeys - 1) / kPfKeys;
+}
+
+static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages, int64_t win_tiles = 0, bool ring = false) {
   if (max_pages <= 0) return 1;
   const int64_t blocks = (int64_t)batch * N * ((max_q_len + kPfRows - 1) / kPfRows);
-  int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  int64_t tiles = cache_tiles(P, max_pages, ring);
   if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
   if (blocks >= 512 || tiles < 8) return 1;
   int64_t s = (512 + blocks - 1) / blocks;
@@ -385,9 +408,9 @@ static int gqa_group(int num_qo_heads, int num_kv_heads) {   // G, or 0 for a re
 // Decode: a unit is (sequence, K/V head) -- one workgroup streams the unit's KV range (or one split of it) once for the whole group.
 // Splits: the decode op's cost model (kv_i4.hip decode_splits_total) with units in place of (sequence, head) pairs, 64-key tiles, at
 // least 2 tiles per split and 512 resident workgroups (2 per CU: 140 VGPRs + 32 AGPRs, 2 waves per SIMD).
-static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, int64_t win_tiles = 0) {
+static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, int64_t win_tiles = 0, bool ring = false) {
   if (max_pages <= 0) return 1;
-  int64_t tiles = ((int64_t)max_pages * P + kPfKeys - 1) / kPfKeys;
+  int64_t tiles = cache_tiles(P, max_pages, ring);
   if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
   const int64_t units = (int64_t)batch * num_kv_heads;
   const int64_t smax = std::max<int64_t>(std::min<int64_t>(tiles / 2, 32), 1);
@@ -406,24 +429,27 @@ static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, 
 // policies see the most key tiles a query block can touch under the window in place of the cache's -- a block's rows span
 // (min(rows, 64) - 1) / G positions, so its keys are n = window + that span contiguous ones, which touch (n + 62) / 64 + 1 tiles at
 // the worst alignment; never more than the cache's tiles, so a window that covers the cache gives the un-windowed plan.
+// ring (the _ring entry points): max_pages is the ring's size and the list starts off the 64-key grid, see cache_tiles; a ring of
+// ceil((W - 1 + max_add) / P) + 1 pages holds more than any block's keys, so the window bound governs and the plan is the _win
+// call's on a cache that never released a page (max_pages large).
 struct PrefillPlan {
   int rows, nqb, splits;
 };
 static PrefillPlan prefill_plan(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
-                                int window = 0) {
+                                int window = 0, bool ring = false) {
   PrefillPlan pl;
   pl.rows = decode ? G : (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
   pl.nqb = (int)(((int64_t)pl.rows + kPfRows - 1) / kPfRows);
   const int64_t win_tiles = window > 0 ? ((int64_t)window + (std::min(pl.rows, kPfRows) - 1) / G + kPfKeys - 2) / kPfKeys + 1 : 0;
-  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages, win_tiles)
-                     : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages, win_tiles);
+  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages, win_tiles, ring)
+                     : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages, win_tiles, ring);
   return pl;
 }
 
 static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
-                                      int window = 0) {
+                                      int window = 0, bool ring = false) {
   if (total_q < 1 || batch < 1 || num_kv_heads < 1 || P < 16 || max_q_len < 1) return 0;
-  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages, window).splits;
+  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages, window, ring).splits;
   return s > 1 ? partial_state_bytes(total_q * num_kv_heads * G, s) : 0;
 }
 
@@ -431,18 +457,21 @@ static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_le
 // batch), and `o` may be NULL: the partial states stay in the workspace un-merged, as atom_batch_decode_i4 leaves them.  The prefill
 // entries refuse total_q / max_q_len (shape) before they look at alignment; the decode entry has no such arguments.  window: NULL, or
 // the _win entries' argument (checked behind every other fault); those run the kWindow instantiations, the GQA form at every G.
+// ring: the _ring entries -- window is theirs too, kv_start is checked behind it, and the kStart instantiations run.
 static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
                           const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
                           int batch, int num_layers, int layer_idx, int G, int num_kv_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, const float *rope_table, float attn_scale, int max_pages, void *workspace,
-                          size_t workspace_bytes, void *stream, const int *window = nullptr) {
+                          size_t workspace_bytes, void *stream, const int *window = nullptr, bool ring = false,
+                          const int32_t *kv_start = nullptr) {
   const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
                           page_size, head_dim);
   if (st != ATOM_OK) return st;
   if (!q || !(rope_theta > 0.f) || !(rope_scale > 0.f) || (!decode && (!o || !qo_indptr))) return ATOM_ERR_INVALID_ARG;
   if (!decode && (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1)) return ATOM_ERR_SHAPE;
   if ((o && !aligned16(o)) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
-  PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages, window ? std::max(*window, 0) : 0);
+  PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages, window ? std::max(*window, 0) : 0,
+                                ring);
   const int num_qo_heads = num_kv_heads * G;
   const int64_t rows_heads = total_q * num_qo_heads;
   if (pl.splits > 1 && !workspace_holds(workspace, workspace_bytes, rows_heads, pl.splits)) pl.splits = 1;
@@ -451,6 +480,8 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   if (grid > 0x7fffffff || rows_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
   if (const int rs = check_rope_table(rope_table, attn_scale)) return rs;   // (the _rope entries' own faults: behind every older one)
   if (window && *window < 1) return ATOM_ERR_INVALID_ARG;                    // (the _win entries' own fault: behind those)
+  if (ring && !kv_start) return ATOM_ERR_INVALID_ARG;                        // (the _ring entries' own faults: behind that)
+  if (ring && (reinterpret_cast<uintptr_t>(kv_start) & 3u)) return ATOM_ERR_ALIGN;
   PrefillParams p;                                        // by name: the fields' order is the kernel's business
   p.data = (const uint8_t *)kv_data, p.param = (const half_t *)kv_param;
   p.kv_indptr = kv_indptr, p.kv_indices = kv_indices, p.last_page_offset = last_page_offset, p.qo_indptr = qo_indptr;
@@ -461,8 +492,14 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   p.G = G, p.Nq = num_qo_heads;                           // (batch_prefill_kernel<false> reads neither)
   p.rope_table = rope_table;
   p.window = window ? *window : 0;                        // (only the kWindow instantiations read it)
+  p.kv_start = kv_start;                                  // (only the kStart instantiations read it)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (window) {                                           // the GQA form for every head ratio, with or without a table
+  if (ring) {                                             // (always with a window)
+    if (rope_table)
+      hipLaunchKernelGGL((batch_prefill_kernel<true, true, true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_prefill_kernel<true, false, true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
+  } else if (window) {                                           // the GQA form for every head ratio, with or without a table
     if (rope_table)
       hipLaunchKernelGGL((batch_prefill_kernel<true, true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
     else
@@ -619,6 +656,53 @@ int atom_batch_prefill_gqa_i4_win(void *o, const void *q, const int32_t *qo_indp
   return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
                         num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
                         max_pages_per_seq, workspace, workspace_bytes, stream, &window);
+}
+
+// ---- rolling cache: the _win entries with `kv_start` behind window (include/atom_hip.h); the page list starts at position kv_start[b]
+
+size_t atom_batch_decode_gqa_i4_ring_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                     int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1 ? prefill_workspace_bytes(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true) : 0;
+}
+
+int atom_batch_decode_gqa_i4_ring_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0 || batch < 1 || page_size < 16 || window < 1) return 0;
+  return prefill_plan(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true).splits;
+}
+
+size_t atom_batch_prefill_gqa_i4_ring_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                      int max_q_len, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1
+             ? prefill_workspace_bytes(false, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true)
+             : 0;
+}
+
+int atom_batch_decode_gqa_i4_ring(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq,
+                        workspace, workspace_bytes, stream, &window, true, kv_start);
+}
+
+int atom_batch_prefill_gqa_i4_ring(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
+                        max_pages_per_seq, workspace, workspace_bytes, stream, &window, true, kv_start);
 }
 
 }  // extern "C"

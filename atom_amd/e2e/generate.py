@@ -16,6 +16,8 @@ the state its own output has led to: ops.guide_advance and ops.guide_mask, two m
 every verify row a state of its own and writes the drafts a state forces, ops.guide_mask masks the batch * (K + 1) rows.
 ``SpecDecodeGraph(penalties=)`` / ``generate(sampling=, speculative=SpeculativeParams(penalised=True))`` penalise every verify row as if
 the drafts in front of it had been emitted and count what a step emitted on the device: ops.penalize_rows, one launch.
+``generate(rolling_kv=True)`` runs a sliding-window model over a ``RollingKvCacheInt4``: a ring of pages per sequence, advanced inside the
+replayed step (ops.kv_step_ring_i4), so the pages a sequence holds do not grow with the tokens it generates.
 """
 from __future__ import annotations
 
@@ -25,7 +27,8 @@ from typing import Mapping, Sequence, Union
 import torch
 
 from .. import ops
-from ..utils import BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, StaticBatchedKvCacheInt4, StaticBeamKvCacheInt4
+from ..utils import (BatchedKvCacheInt4, BatchLenInfo, KvCacheInt4, KvPoolInt4, RollingKvCacheInt4, StaticBatchedKvCacheInt4,
+                     StaticBeamKvCacheInt4)
 from .guide import LogitGuide, TokenAutomaton
 
 
@@ -531,14 +534,17 @@ _UNGUIDED = "speculative unless it is SpeculativeParams(guided=True)"
 _UNPENALISED = "penalties unless it is SpeculativeParams(penalised=True)"     # a message lists the fields themselves, as "penalties" does
 _REFUSES = (("guide", ("num_beams", _UNGUIDED)),
             ("speculative", ("num_beams", "logprobs", "return_logits", "caches", _UNPENALISED)),
-            ("num_beams", ("sampling", "logprobs", "return_logits", "caches")))
+            ("num_beams", ("sampling", "logprobs", "return_logits", "caches")),
+            ("rolling_kv", ("caches", "num_beams", "speculative")))
 
 
-def _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide):
+def _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide,
+                       rolling_kv=False):
     """Raises ``ValueError`` for the first entry of ``_REFUSES`` that applies (and for a drafter or statistics without ``speculative``)."""
     named = {"guide": guide is not None, "speculative": speculative is not None, "num_beams": num_beams is not None,
              "sampling": sampling is not None, "logprobs": logprobs is not None, "return_logits": bool(return_logits),
-             "caches": caches is not None, _UNGUIDED: speculative is not None and not speculative.guided}
+             "caches": caches is not None, _UNGUIDED: speculative is not None and not speculative.guided,
+             "rolling_kv": bool(rolling_kv)}
     named = {name: [name] * given for name, given in named.items()}          # what a message lists for each name: itself, if given
     used, neutral = named.setdefault("penalties", []), SamplingParams()
     for q in ([] if sampling is None else _params_list(sampling)):
@@ -552,6 +558,24 @@ def _check_combination(caches, return_logits, sampling, logprobs, num_beams, spe
             raise ValueError(f"generate: {feature} does not combine with {', '.join(refused[:1] if feature == 'guide' else refused)}")
         if feature == "speculative" and not named[feature] and (drafter is not None or return_spec_stats):
             raise ValueError("generate: drafter and return_spec_stats need speculative")
+
+
+def _rolling_window(model) -> int:
+    """The one sliding window that every attention layer of ``model`` carries -- what ``generate(rolling_kv=True)`` sizes the rings
+    by.  A layer without a window would read a history the rolling cache has released, and layers of different windows would need
+    rings of their own: both are a ``ValueError`` that names the layer."""
+    layers = [m for m in model.modules() if hasattr(m, "window") and hasattr(m, "layer_idx") and hasattr(m, "rope_kw")]
+    if not layers:
+        raise ValueError("generate: rolling_kv needs a model with attention layers that carry a sliding window, found none")
+    for m in layers:
+        if m.window is None:
+            raise ValueError(f"generate: rolling_kv needs a sliding window on every attention layer; layer {m.layer_idx} has none "
+                             f"(config.sliding_window unset, use_sliding_window False, or a layer_types entry that is not "
+                             f"'sliding_attention')")
+        if m.window != layers[0].window:
+            raise ValueError(f"generate: rolling_kv needs one window for all layers; layer {m.layer_idx} has {m.window}, layer "
+                             f"{layers[0].layer_idx} has {layers[0].window}")
+    return layers[0].window
 
 
 def _prefill(model, prompts: Sequence[Sequence[int]], seqs: Sequence[KvCacheInt4], device):
@@ -570,7 +594,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
              sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None,
              speculative: SpeculativeParams = None, drafter=None, return_spec_stats: bool = False,
-             guide: Union[TokenAutomaton, Sequence[TokenAutomaton]] = None):
+             guide: Union[TokenAutomaton, Sequence[TokenAutomaton]] = None, rolling_kv: bool = False):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -617,8 +641,17 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     unless it is ``SpeculativeParams(guided=True)``: then every verify row is masked with a state of its own (ops.guide_walk_rows, and
     ops.guide_mask over the ``batch * (K + 1)`` rows: two launches per step), a draft that follows a state with a
     single allowed token is replaced by that token (``force_drafts``), and what ``speculative`` refuses stays refused.
-    ``guide=None`` is the code above, launch for launch, with nothing allocated."""
-    _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide)
+    ``guide=None`` is the code above, launch for launch, with nothing allocated.
+    ``rolling_kv=True`` (a sliding-window model: every attention layer must carry the same window W, else ``ValueError`` naming the
+    layer): the decode loop runs over a ``RollingKvCacheInt4`` in place of the static cache -- ``ceil(W / page) + 1`` pages per sequence
+    however many tokens are generated, the ring advanced on the device inside the replayed step (ops.kv_step_ring_i4).
+    The prompt is still prefilled into ordinary pages (peak ``ceil(prompt / page)`` pages per sequence); those behind the window go back
+    to the pool before the first replayed step.  Same tokens and logits as the default wherever both caches give the attention op the
+    same KV split.  Combines with ``sampling``, the penalties, ``logprobs``, ``return_logits`` and ``guide``; refused with
+    ``ValueError``: ``caches`` (a cache without its head is no ``KvCacheInt4``), ``num_beams`` and ``speculative``.
+    ``rolling_kv=False`` is the code above, launch for launch."""
+    _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide, rolling_kv)
+    window = _rolling_window(model) if rolling_kv else None
     if num_beams is not None:
         return [hyps[0].tokens for hyps in beam_search(model, prompts, max_new_tokens, pool, num_beams, eos_token_id=eos_token_id)]
     n_lp = _check_logprobs(logprobs)
@@ -655,7 +688,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
                 static.close()
         new = None
     elif max_new_tokens > 1:
-        static = StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
+        static = RollingKvCacheInt4(seqs, window) if rolling_kv else StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
             dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp,
                              penalties=penalties, guide=guides)

@@ -271,7 +271,8 @@ class LlamaAttention(nn.Module):
     p - W < j <= p.  With ``config.layer_types`` only the layers marked "sliding_attention" are windowed; ``use_sliding_window`` False
     switches it off; a non-positive value raises.  The window travels in ``rope_kw`` to every attention call (the ops' ``window=``);
     a windowed layer's prefill always attends through ops.batch_prefill_i4 (the torch route has no lower bound), and its decode step
-    appends and attends in two launches.  Pages behind the window stay allocated.  None / absent: the calls it always made."""
+    appends and attends in two launches.  Pages behind the window stay allocated unless the cache is a ``RollingKvCacheInt4``
+    (``generate(rolling_kv=True)``): the ops then read its page list from ``kv_start`` on.  None / absent: the calls it always made."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()

@@ -666,6 +666,36 @@ def kv_step_rows_i4(kv, adds: torch.Tensor, lookahead: int = 0):
     L.check(st, "atom_kv_step_rows_i4")
 
 
+def kv_step_ring_i4(kv, add: int = 1):
+    """NEW (rolling cache of a sliding-window model): ``kv_step_i4`` for a utils.RollingKvCacheInt4, whose page-table rows are RINGS --
+    logical page g of a sequence lives in slot g % row_pages (atom_kv_step_ring_i4).  Every sequence gains ``add`` tokens; its tables
+    list the pages that the step's new rows still see under ``kv.window``, in logical order, and ``kv.kv_start`` receives the position
+    of each list's first token (what the attention ops then read).  The slot of the new last page is one whose previous tenant fell
+    behind the window.  A sequence whose live pages would outnumber its ring keeps its length and sets the cache's status word.  One
+    launch on the current stream, no host synchronisation, capturable."""
+    tensors, batch, cap = _kv_step_tables(kv)
+    start = kv.kv_start
+    if not start.is_cuda:
+        raise L.AtomHipError("KV-cache page tables must live on the GPU: no CPU fallback")
+    assert start.dtype == torch.int32 and start.is_contiguous() and start.numel() == batch
+    st = L.lib().atom_kv_step_ring_i4(*(t.data_ptr() for t in tensors), batch, cap, kv.page_size, int(add), int(kv.window),
+                                       start.data_ptr(), L.current_stream(kv.page_table.device))
+    L.check(st, "atom_kv_step_ring_i4")
+
+
+def _ring_start(kv, window):
+    """``kv.kv_start`` of a rolling cache (utils.RollingKvCacheInt4) for a call with ``window`` -- the call then takes the _ring entry
+    points --, None for every other cache.  A rolling cache has released the pages behind ITS window: an un-windowed call, or one with
+    a wider window, would silently read a truncated history and is refused."""
+    start = getattr(kv, "kv_start", None)
+    if start is None:
+        return None
+    if window is None or window > kv.window:
+        raise ValueError(f"a rolling cache serves only windowed calls no wider than its own window ({kv.window}), got window={window!r}: "
+                         f"the pages behind that window are released")
+    return start
+
+
 def _qo_heads(num_qo_heads: int, num_kv_heads: int) -> int:
     """grouped-query attention: query head h reads the cache's K/V head h // G -- the query head count must be a multiple of the cache's"""
     if num_qo_heads < 1 or num_qo_heads % num_kv_heads:
@@ -685,12 +715,15 @@ def _window_arg(window):
 def decode_splits(batch: int, kv, num_qo_heads: int = None, window: int = None) -> int:
     """How many partial states per (sequence, head) batch_decode_i4 produces for this cache (1: none; small batches: one per workgroup of
     four KV-split waves).  ``num_qo_heads``: the query heads of a grouped-query call (default: the cache's head count).  ``window``:
-    of the sliding-window call (atom_batch_decode_gqa_i4_win_splits, the grouped-query plan at every head ratio)."""
+    of the sliding-window call (atom_batch_decode_gqa_i4_win_splits, the grouped-query plan at every head ratio; on a rolling cache
+    atom_batch_decode_gqa_i4_ring_splits, and a call without a window or with one wider than the cache's is a ``ValueError``)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     max_pages = int(getattr(kv, "max_pages", 0))
+    ring = _ring_start(kv, _window_arg(window)) is not None
     if _window_arg(window) is not None:
         nq = num_heads if num_qo_heads is None else _qo_heads(int(num_qo_heads), num_heads)
-        return int(L.lib().atom_batch_decode_gqa_i4_win_splits(int(batch), nq, num_heads, page_size, max_pages, window))
+        query = L.lib().atom_batch_decode_gqa_i4_ring_splits if ring else L.lib().atom_batch_decode_gqa_i4_win_splits
+        return int(query(int(batch), nq, num_heads, page_size, max_pages, window))
     if num_qo_heads is None or num_qo_heads == num_heads:
         return int(L.lib().atom_batch_decode_i4_splits(int(batch), num_heads, page_size, max_pages))
     nq = _qo_heads(int(num_qo_heads), num_heads)
@@ -753,13 +786,33 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     ``window`` (sliding-window attention): an int W >= 1 -- the query at position p sees keys p - W < j <= p, plain causal attention
     for a sequence no longer than W.  None: exactly the calls above.  With a window atom_batch_decode_gqa_i4_win runs -- the
     grouped-query (matrix-core) op at every head ratio, MHA caches included --, ``merge=False`` takes its splits from
-    ``decode_splits(batch, kv, q heads, window=W)``, and ``append_kv`` is refused (the fused append lives in the FP32 decode kernel)."""
+    ``decode_splits(batch, kv, q heads, window=W)``, and ``append_kv`` is refused (the fused append lives in the FP32 decode kernel).
+    A rolling cache (utils.RollingKvCacheInt4: it has a ``kv_start`` tensor) takes atom_batch_decode_gqa_i4_ring with the same
+    arguments and ``kv.kv_start``: the same positions, masks and angles, read from a page list that starts at ``kv_start[b]``.
+    ``window=None`` or a window wider than the cache's is a ``ValueError`` there.  Every other cache makes exactly the calls above."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
     gqa = q.dim() == 3 and q.size(1) != num_heads
     nq = _qo_heads(q.size(1), num_heads) if gqa else num_heads
     assert q.shape == (batch, nq, head_dim)
+    start = _ring_start(kv, _window_arg(window))
+    if start is not None:
+        if append_kv is not None:
+            raise ValueError("append_kv= is not built for sliding-window attention (the fused append lives in the FP32 decode kernel): "
+                             "append with quant_append_kv_i4 first")
+        _require_cuda(kv.data, kv.param, start)
+        assert batch == kv.last_page_offset.numel() == start.numel() and start.dtype == torch.int32 and start.is_contiguous()
+        ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq)
+        lib = L.lib()
+        plan = (batch, nq, num_heads, page_size, max_pages, window)
+        ws_bytes = lib.atom_batch_decode_gqa_i4_ring_workspace_bytes(*plan)
+        o, ws, ret = _decode_outputs(q, merge, ws_bytes, None if merge else lib.atom_batch_decode_gqa_i4_ring_splits(*plan))
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_decode_gqa_i4_ring(L.ptr(o), q.data_ptr(), *ptrs, *dims, float(rope_theta), float(rope_scale), table, scale, window,
+                                               start.data_ptr(), max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_decode_gqa_i4_ring")
+        return ret
     if _window_arg(window) is not None:
         if append_kv is not None:
             raise ValueError("append_kv= is not built for sliding-window attention (the fused append lives in the FP32 decode kernel): "
@@ -813,7 +866,8 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     ``rope_table`` / ``attn_scale``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_rope; both at their defaults: the call
     without them).
     ``window``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_win) -- the bound of every query row from that row's own
-    position; None: exactly the calls above."""
+    position; None: exactly the calls above.  A rolling cache takes atom_batch_prefill_gqa_i4_ring, as in ``batch_decode_i4``; a
+    chunk there is at most the cache's ``max_add`` tokens (what ``kv.step(add)`` admits)."""
     _require_cuda_half(q, "q")
     _require_cuda(qo_indptr, kv.data, kv.param)
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
@@ -826,6 +880,19 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     assert qo_indptr.numel() == batch + 1
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
+    start = _ring_start(kv, _window_arg(window))
+    if start is not None:
+        _require_cuda(start)
+        assert start.numel() == batch and start.dtype == torch.int32 and start.is_contiguous()
+        ws_bytes = lib.atom_batch_prefill_gqa_i4_ring_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages, window)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_prefill_gqa_i4_ring(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
+                                                float(rope_scale), table, scale, window, start.data_ptr(), max_pages, L.ptr(ws), ws_bytes,
+                                                L.current_stream(q.device))
+        L.check(st, "atom_batch_prefill_gqa_i4_ring")
+        return o
     if _window_arg(window) is not None:
         ws_bytes = lib.atom_batch_prefill_gqa_i4_win_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages, window)
         ws = _workspace(q.device, ws_bytes) if ws_bytes else None

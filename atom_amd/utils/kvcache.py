@@ -5,6 +5,8 @@ code written against the reference's objects runs on these.  Host-side only; the
 ``StaticBatchedKvCacheInt4`` (not in the reference) keeps the page tables at fixed device addresses and advances them on the device
 (ops.kv_step_i4 -> csrc/kv_step.hip), for decode steps replayed from a captured graph.  ``StaticBeamKvCacheInt4`` is its beam-search
 form: several rows per prompt that share full pages and are reordered on the device (ops.kv_beam_fork_i4 -> csrc/beam.hip).
+``RollingKvCacheInt4`` is the static cache of a sliding-window model: a ring of pages per sequence, the pages behind the window
+released (ops.kv_step_ring_i4 -> csrc/kv_step.hip; the attention ops' ``_ring`` entry points -> csrc/prefill_i4.hip).
 
 Pool layout (reference kvcache.py:17-26, page.cuh:78-110):
     buf    uint8 [capacity, num_layers, 2, num_heads, block_len, head_dim // 2]   packed u4, K at [.., 0, ..], V at [.., 1, ..]
@@ -190,6 +192,99 @@ class StaticBatchedKvCacheInt4:
         finally:
             for c in self._kv:
                 c.trim()
+
+
+class RollingKvCacheInt4:
+    """The static cache of a sliding-window model: the attributes of ``StaticBatchedKvCacheInt4`` -- every windowed attention op and
+    module takes it in its place -- but each sequence holds a RING of ``R = ceil((window - 1 + max_add) / page_size) + 1`` pages however
+    long it grows: logical page g (tokens g * page_size ...) lives in slot ``g % R`` of its ``page_table`` row, and ``step(add)``
+    (ops.kv_step_ring_i4, one launch) lists the pages the step's new rows still see, in logical order, and writes the position of each
+    list's first token to ``kv_start``.  The presence of ``kv_start`` is what sends the attention ops to their ``_ring`` entry points;
+    they refuse a call without a window or with one wider than ``window`` (the history behind it is gone).
+
+    ``kv``: prefilled ``KvCacheInt4`` sequences without spare pages.  The constructor returns every page that lies wholly behind the
+    window of the current length to the pool, takes fresh ones up to ``R`` per sequence (``RuntimeError`` before anything changes if
+    the pool cannot give them), and lays each row out so that logical page g sits in slot g % R.  From then on the sequences' page
+    lists are the rings, which no ``KvCacheInt4`` method understands: use the sequences again only after ``close()``.
+    ``max_add``: the most tokens one ``step`` may add (1: decode steps; q for chunks of q tokens); ``max_pages = R``."""
+
+    device_lengths = True      # the lengths live on the device: ``seqlens`` is stale between sync_host() calls (read by LlamaAttention)
+
+    def __init__(self, kv: Sequence[KvCacheInt4], window: int, max_add: int = 1):
+        assert len(kv) > 0
+        pool = kv[0].pool
+        assert all(c.pool is pool for c in kv)
+        assert len({id(c) for c in kv}) == len(kv)
+        if isinstance(window, bool) or int(window) != window or window < 1 or int(max_add) != max_add or max_add < 1:
+            raise ValueError(f"window and max_add must be integers >= 1, got {window!r} and {max_add!r}")
+        P, device = pool.block_len, pool.buf.device
+        assert all(len(c.indicies) == -(-c.seqlen // P) for c in kv), "the sequences must hold no spare pages"
+        self.window, self.max_add = int(window), int(max_add)
+        R = -(-(self.window - 1 + self.max_add) // P) + 1
+        first = [max(0, c.seqlen - self.window) // P for c in kv]           # the first page a step to the current length lists
+        need = sum(R - (len(c.indicies) - f) for c, f in zip(kv, first))
+        if need > pool.num_free_blocks + sum(first):
+            raise RuntimeError(f"RollingKvCacheInt4: {need} more pages needed ({len(kv)} rings of {R}), {pool.num_free_blocks} free in "
+                               f"the pool and {sum(first)} behind the window")
+        for c, f in zip(kv, first):                                         # every sequence first: the pool may need these pages back
+            for idx in c.indicies[:f]:
+                pool.free_block(idx)
+        rows = []
+        for c, f in zip(kv, first):
+            live = {g % R: idx for g, idx in enumerate(c.indicies[f:], start=f)}
+            rows.append([live[s] if s in live else pool.alloc_block() for s in range(R)])
+            c._indicies[:] = rows[-1]                                       # what close() releases
+        self._kv = list(kv)
+        batch = len(kv)
+        self.data = pool.buf
+        self.param = pool.param
+        self.max_pages = R
+        self.seqlens = [c.seqlen for c in kv]
+        self.page_table = torch.tensor(rows, dtype=torch.int32, device=device)
+        self.row_pages = torch.full((batch,), R, dtype=torch.int32, device=device)
+        self._dev = torch.tensor(self.seqlens + [0] * batch + [0, 0, 0, 0], dtype=torch.int32, device=device)
+        self.lengths = self._dev[:2 * batch]
+        self.state = self._dev[2 * batch:]
+        self.indptr = torch.zeros(batch + 1, dtype=torch.int32, device=device)
+        self.indicies = torch.zeros(batch * R, dtype=torch.int32, device=device)
+        self.last_page_offset = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.kv_start = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.step(0)
+
+    @property
+    def page_size(self):
+        return self.data.size(-2)
+
+    def step(self, add: int = 1):
+        """One launch on the current stream: every sequence gains ``add`` tokens (0: rebuild the tables only), at most ``max_add``.
+        Capturable."""
+        if int(add) > self.max_add:
+            raise ValueError(f"RollingKvCacheInt4: a step of {add} tokens on rings sized for max_add={self.max_add}")
+        from .. import ops
+        ops.kv_step_ring_i4(self, add)
+
+    def sync_host(self):
+        """Read the lengths and the status word back (one copy, the only synchronisation) and bring ``seqlens`` and the sequences'
+        ``seqlen`` up to date.  Raises if a sequence's live pages outgrew its ring (it kept its last legal length) or a stored length
+        was out of range; the status word is cleared."""
+        batch = len(self._kv)
+        host = self._dev.tolist()
+        status, parity = host[2 * batch], host[2 * batch + 1] & 1
+        self.seqlens = host[parity * batch:(parity + 1) * batch]
+        for c, n in zip(self._kv, self.seqlens):
+            c._seqlen = n
+        if status:
+            self.state[0].zero_()
+            raise RuntimeError(f"RollingKvCacheInt4: status {status} (1: a sequence needed more live pages than its ring holds and was "
+                               f"not advanced, 2: a stored length was out of range); lengths now {self.seqlens}")
+
+    def close(self):
+        """``sync_host()``, then every sequence is RELEASED: its history has lost its head, which no ``KvCacheInt4`` can describe."""
+        try:
+            self.sync_host()
+        finally:
+            for c in self._kv:
+                c.release()
 
 
 class StaticBeamKvCacheInt4:

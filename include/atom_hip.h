@@ -554,6 +554,43 @@ int atom_batch_prefill_gqa_i4_win(void *o, const void *q, const int32_t *qo_indp
                                   const float *rope_table, float attn_scale, int window, int max_pages_per_seq, void *workspace,
                                   size_t workspace_bytes, void *stream);
 
+/* Sliding-window attention over a ROLLING cache: the _win entry points with `kv_start` inserted behind window.
+ *   kv_start int32 [batch] on the device: the position of the first token of sequence b's page list -- what atom_kv_step_ring_i4
+ *   writes.  The pages behind the window have been released; the list holds the live ones in logical order.
+ *   - start = kv_start[b] is a multiple of page_size, not necessarily of 64.
+ *   - The sequence's length is start + (pages - 1) * page_size + last_page_offset.
+ *   - Everything else stays in ABSOLUTE positions: the positions of the queries (the LAST q_b of that length), the causal and the
+ *     window bound, the 64-key tile grid, the KV splits and the RoPE angle of key j.  Given equal contents and an equal split count the
+ *     call performs the operations of the _win call on a cache that released nothing, in the same order: the results are bit-identical.
+ *   - Key j is read from page (j - start) / page_size of the list.  Keys with j < start or j >= length are not loaded; they are
+ *     staged as zeros.
+ *   - The caller guarantees start <= p - window + 1 for every query position p (atom_kv_step_ring_i4 does), so the window bound
+ *     already masks every key below start.  A caller that breaks the guarantee gets an unspecified finite result; no value of
+ *     kv_start makes the kernel read outside the listed pages.
+ * Plan: max_pages_per_seq is the ring's size R, and a list of R * page_size tokens that starts off a 64-key boundary touches up to
+ * (R * page_size + 62) / 64 + 1 tiles, one more than the _win plan assumes for that many pages -- so these entries have plan queries of
+ * their own, with the _win queries' arguments.  For a ring of at least ceil((window - 1 + q_b) / page_size) + 1 pages the window
+ * bound governs and the plan is the _win call's at a large max_pages_per_seq.  The partial-state layout is unchanged (o == NULL on the
+ * decode entry feeds atom_gemm_w4a4_multi_merge_q).
+ * Errors: every fault of the _win entries, in their order; behind ALL of them a null kv_start is ATOM_ERR_INVALID_ARG, one that is not
+ * 4-byte aligned ATOM_ERR_ALIGN. */
+size_t atom_batch_decode_gqa_i4_ring_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                     int window);
+int atom_batch_decode_gqa_i4_ring_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window);
+size_t atom_batch_prefill_gqa_i4_ring_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                      int max_q_len, int max_pages_per_seq, int window);
+int atom_batch_decode_gqa_i4_ring(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int atom_batch_prefill_gqa_i4_ring(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+
 /* Page tables stepped on the device (csrc/kv_step.hip): rebuilds kv_indptr / kv_indices / last_page_offset -- the layout above, what
  * every attention and append entry point reads -- in ONE launch from buffers at fixed addresses, so that a captured decode step can
  * be replayed for the next token with no host work in between.
@@ -589,6 +626,29 @@ int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t
 int atom_kv_step_rows_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                          int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, const int32_t *adds, int lookahead,
                          void *stream);
+
+/* The step over a RING of pages (rolling cache of a sliding-window model; the same kernel body): the arguments of
+ * atom_kv_step_i4 plus `window` = W >= 1 and an output kv_start int32 [batch].
+ *   - page_table[b][0 .. R), R = min(row_pages[b], cap), is a ring: logical page g of sequence b (tokens g * page_size ..
+ *     g * page_size + page_size - 1) lives in slot g % R.  `lens` stays the ABSOLUTE length, double-buffered as above; `state` as above.
+ * For the new length n = len_b + add:
+ *   - first live logical page f = max(0, n - max(add, 1) - W + 1) / page_size: the lowest key that the oldest of the step's new rows
+ *     still sees, floored to a page;
+ *   - last live logical page l = (n + page_size - 1) / page_size - 1; the page count is cnt = l - f + 1, 0 for an empty sequence;
+ *   - cnt > R: the sequence is NOT advanced, its tables are those of its old length (the pages f .. l of n = len_b, add = 0) and
+ *     ATOM_KV_STEP_OVERFLOW is set -- a status bit, never a fault;
+ *   - a stored length below 0 or above 0x7fffffff - add is clamped into that range and ATOM_KV_STEP_BAD_LENGTH is set; a stored
+ *     length whose own pages exceed R is flagged too and listed by its last R pages (none for R = 0: the sequence is then empty).  No
+ *     page count above R and no index from outside a row ever reaches kv_indices.
+ * Outputs: kv_indptr, the exclusive prefix sum of cnt; kv_indices in LOGICAL order, entry j of sequence b = page_table[b][(f + j) % R];
+ * last_page_offset = (n - 1) % page_size + 1 (0 when empty); kv_start[b] = f * page_size (what the _ring attention entries take).
+ * Why a slot may be reused: the page that receives token n - 1 sits in slot l % R; that slot's previous tenant was logical page
+ * l - R < f, which is no longer listed.  The bytes of the slot beyond n are stale and are never read: the attention kernels stop at
+ * the length.  There is no ring form of atom_kv_step_rows_i4.
+ * Errors: as atom_kv_step_i4, with ATOM_ERR_INVALID_ARG for window < 1 or a null kv_start and ATOM_ERR_ALIGN for a kv_start off 4 bytes. */
+int atom_kv_step_ring_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                         int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, int window,
+                         int32_t *kv_start, void *stream);
 
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised
