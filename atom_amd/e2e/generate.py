@@ -827,6 +827,8 @@ def beam_search(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, po
     if not 1 <= int(num_return) <= W:
         raise ValueError(f"num_return must be 1 .. num_beams, got {num_return}")
     assert max_new_tokens >= 1 and len(prompts) > 0 and all(len(p) > 0 for p in prompts)
+    if pool.buf.shape[-1] == 32:                               # (refused before a page is taken: ops.kv_beam_fork_i4 would raise mid-search)
+        raise NotImplementedError("beam search is not built for head size 64 (the KV fork kernel copies 128-wide heads)")
     device, G = pool.buf.device, len(prompts)
     seqs = [KvCacheInt4(pool, 0) for _ in prompts]
     try:

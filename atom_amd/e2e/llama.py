@@ -272,7 +272,11 @@ class LlamaAttention(nn.Module):
     switches it off; a non-positive value raises.  The window travels in ``rope_kw`` to every attention call (the ops' ``window=``);
     a windowed layer's prefill always attends through ops.batch_prefill_i4 (the torch route has no lower bound), and its decode step
     appends and attends in two launches.  Pages behind the window stay allocated unless the cache is a ``RollingKvCacheInt4``
-    (``generate(rolling_kv=True)``): the ops then read its page list from ``kv_start`` on.  None / absent: the calls it always made."""
+    (``generate(rolling_kv=True)``): the ops then read its page list from ``kv_start`` on.  None / absent: the calls it always made.
+    Head size 64 (``hidden_size / num_attention_heads``, or an explicit ``config.head_dim``; Llama-3.2-1B, TinyLlama): k_proj / v_proj
+    give fp16, and every step goes projections -> ops.kv_quant_u4 -> ops.init_kv_i4 / append_kv_i4 -> the attention op -> o_proj, on
+    the kernels of csrc/attn_d64.hip (``_forward_d64``).  Prefill always takes the op; the fused decode routes (FP32 sums into the
+    quantising append, the quantisers inside the GEMMs, the merge inside o_proj) are off, and a sliding window raises here."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -280,27 +284,31 @@ class LlamaAttention(nn.Module):
         self.fusion = fusion if fusion is not None else FUSION
         self.hidden_size = config.hidden_size
         self.num_heads = config.num_attention_heads
-        self.head_dim = self.hidden_size // self.num_heads
+        explicit = getattr(config, "head_dim", None)
+        self.head_dim = self.hidden_size // self.num_heads if explicit is None else int(explicit)
         self._scale = 1 / math.sqrt(self.head_dim)
         self.layer_idx = layer_idx
         if self.head_dim * self.num_heads != self.hidden_size:
-            raise ValueError(f"hidden_size {self.hidden_size} is not divisible by num_heads {self.num_heads}")
-        if self.head_dim != 128:
-            raise ValueError("the INT4 KV kernels are built for head_dim 128 (as the reference's, punica_ops.cc:112)")
+            raise ValueError(f"hidden_size {self.hidden_size} is not num_heads {self.num_heads} x head_dim {self.head_dim}")
+        if self.head_dim not in (64, 128):
+            raise ValueError(f"the INT4 KV kernels are built for head_dim 128 (as the reference's, punica_ops.cc:112) and 64, got {self.head_dim}")
         nkv = getattr(config, "num_key_value_heads", None)
         self.num_kv_heads = self.num_heads if nkv is None else int(nkv)
         if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads:
             raise ValueError(f"num_key_value_heads {self.num_kv_heads} does not divide num_attention_heads {self.num_heads}")
         self.kv_dim = self.num_kv_heads * self.head_dim
         self.q_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="fp16", bias=False, fusion=fusion)
-        self.k_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype="int4", bias=False, fusion=fusion)
-        self.v_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype="int4", bias=False, fusion=fusion)
+        kv_out = "int4" if self.head_dim == 128 else "fp16"      # (the u4 epilogue quantises per 128 columns: head 64 takes ops.kv_quant_u4)
+        self.k_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype=kv_out, bias=False, fusion=fusion)
+        self.v_proj = LinearInt4(self.hidden_size, self.kv_dim, out_dtype=kv_out, bias=False, fusion=fusion)
         self.o_proj = LinearInt4(self.hidden_size, self.hidden_size, out_dtype="fp16", bias=False, fusion=fusion)
         self.reorder_index = nn.Parameter(torch.randperm(self.hidden_size).to(torch.int16), requires_grad=False)
-        self.rope_theta, self.rope_scale, inv_freq, attention_factor = rope_init(config)
+        self.rope_theta, self.rope_scale, inv_freq, attention_factor = rope_init(config, self.head_dim)
         self.attn_scale = float(attention_factor) ** 2
-        self.register_buffer("rope_table", None if inv_freq is None else ops.rope_table(inv_freq, "cpu"), persistent=False)
+        self.register_buffer("rope_table", None if inv_freq is None else ops.rope_table(inv_freq, "cpu", self.head_dim), persistent=False)
         self.window = self._config_window(config, layer_idx)
+        if self.window is not None and self.head_dim != 128:
+            raise NotImplementedError(f"sliding-window attention is built for head_dim 128, got {self.head_dim}")
 
     @staticmethod
     def _config_window(config, layer_idx):
@@ -358,12 +366,39 @@ class LlamaAttention(nn.Module):
         if kv is not None and ops._kv_dims(kv)[1] != self.num_kv_heads:
             raise ValueError(f"a paged KV cache of {ops._kv_dims(kv)[1]} heads for a layer of {self.num_kv_heads} K/V heads "
                              f"(num_key_value_heads; {self.num_heads} query heads)")
+        if kv is not None and ops._kv_dims(kv)[3] != self.head_dim:
+            raise ValueError(f"a paged KV cache of head size {ops._kv_dims(kv)[3]} for a layer of head size {self.head_dim}")
+
+    def _forward_d64(self, hidden_states, blen, prefill_kv, decode_kv):
+        """head size 64: one op order for every step -- fp16 projections, the per-head quantiser, the cache write, the attention op"""
+        nh, hd, nkv = self.num_heads, self.head_dim, self.num_kv_heads
+        q_proj = self.q_proj(hidden_states)
+        rows, doff = q_proj.size(0), blen.doff
+        k_u4, k_sz = ops.kv_quant_u4(self.k_proj(hidden_states).view(rows, nkv, hd))
+        v_u4, v_sz = ops.kv_quant_u4(self.v_proj(hidden_states).view(rows, nkv, hd))
+        outs = []
+        if len(blen.prefills) > 0:
+            assert prefill_kv is not None
+            ops.init_kv_i4(prefill_kv, k_u4[:doff], v_u4[:doff], k_sz[:doff], v_sz[:doff], blen.indptr, self.layer_idx)
+            o = ops.batch_prefill_i4(q_proj[:doff].view(-1, nh, hd), blen.indptr, prefill_kv, self.layer_idx, rope_theta=self.rope_theta,
+                                     max_q_len=max(blen.prefills), **self.rope_kw)
+            outs.append(o.view(doff, self.hidden_size))
+        if blen.decode > 0:
+            assert decode_kv is not None
+            ops.append_kv_i4(decode_kv, k_u4[doff:], v_u4[doff:], k_sz[doff:], v_sz[doff:], self.layer_idx)
+            o = ops.batch_decode_i4(q_proj[doff:].view(blen.decode, nh, hd), decode_kv, self.layer_idx, rope_theta=self.rope_theta,
+                                    **self.rope_kw)
+            outs.append(o.view(blen.decode, self.hidden_size))
+        attn = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return self.o_proj(ops.reorder_fp16_i4(attn.contiguous(), self.reorder_index))
 
     def forward(self, hidden_states, blen: BatchLenInfo, prefill_kv: BatchedKvCacheInt4 | None,
                 decode_kv: BatchedKvCacheInt4 | None) -> torch.Tensor:
         nh, hd, nkv = self.num_heads, self.head_dim, self.num_kv_heads
         self._check_cache(prefill_kv)
         self._check_cache(decode_kv)
+        if hd == 64:
+            return self._forward_d64(hidden_states, blen, prefill_kv, decode_kv)
         prefixes = []
         # a static cache as the prefill cache (the verify step of speculative decoding): its lengths live on the device and its host list
         # is stale during replay, so there is no host-side prefix to check -- the requests always attend through ops.batch_prefill_i4,
@@ -530,7 +565,8 @@ class LlamaDecoderLayer(nn.Module):
         rows = hidden_states.size(0) if torch.is_tensor(hidden_states) else 0
         fu = self.fusion
         if (fu.q_decode and self._q_mask_for(rows) and fu.decode and fu.kv_append and 0 < rows <= 2 and hidden_states.dim() == 2 and hidden_states.is_contiguous()
-                and len(blen.prefills) == 0 and blen.decode == rows and decode_kv is not None and self._fused_q_fits(rows)):
+                and len(blen.prefills) == 0 and blen.decode == rows and decode_kv is not None and self.self_attn.head_dim == 128
+                and self._fused_q_fits(rows)):
             self.self_attn._check_cache(decode_kv)
             return self._decode_fused_q(hidden_states, decode_kv, self._q_mask_for(rows))
         attn = self.self_attn(self.input_layernorm(hidden_states), blen, prefill_kv, decode_kv)

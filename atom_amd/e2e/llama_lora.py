@@ -52,6 +52,11 @@ class LlamaDecoderLayerWithLora(LlamaDecoderLayer):
 
     lora = None          # (manager, ids int32 device buffer) while adapters are set
 
+    def __init__(self, config, layer_idx: int, fusion=None):
+        super().__init__(config, layer_idx, fusion)
+        if self.self_attn.head_dim != 128:
+            raise NotImplementedError(f"the LoRA classes are built for head_dim 128, got {self.self_attn.head_dim}")
+
     def _lora(self, y, x, module, blen):
         mgr, ids = self.lora
         m = mgr.mgr.get(module)

@@ -75,6 +75,8 @@ class MixtralDecoderLayer(nn.Module):
             raise NotImplementedError("sliding-window attention is not implemented: config.sliding_window must be None (Mixtral-8x7B ships null)")
         self.hidden_size = config.hidden_size
         self.self_attn = LlamaAttention(config=config, layer_idx=layer_idx, fusion=fusion)
+        if self.self_attn.head_dim != 128:
+            raise NotImplementedError(f"the Mixtral classes are built for head_dim 128, got {self.self_attn.head_dim}")
         self.block_sparse_moe = MixtralSparseMoeInt4(config)
         self.input_layernorm = LlamaRMSNormInt4(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = LlamaRMSNormInt4(config.hidden_size, eps=config.rms_norm_eps)

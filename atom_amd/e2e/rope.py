@@ -4,15 +4,15 @@
 
     theta             the RoPE base (``rope_theta``)
     rope_scale        the ops' position divisor: ``factor`` for type ``linear``, else 1.0
-    inv_freq          float64 [64], radians per position of pair i (dims i, i + 64) -- or None where the ops' own
-                      ``theta ** (-2 i / 128) / rope_scale`` is the definition (no scaling, ``default``, ``linear``)
+    inv_freq          float64 [head_dim / 2], radians per position of pair i (dims i, i + head_dim / 2) -- or None where the ops' own
+                      ``theta ** (-2 i / head_dim) / rope_scale`` is the definition (no scaling, ``default``, ``linear``)
     attention_factor  what HF multiplies cos / sin by (YaRN); the logits take its square (``attn_scale``).  1.0 elsewhere.
 
 Both config spellings are read: ``config.rope_parameters`` (transformers 5: a dict with ``rope_theta`` and ``rope_type``; ``rope_theta``
 itself may then be None or absent) and ``config.rope_theta`` + ``config.rope_scaling`` (transformers 4; the type key is ``rope_type`` or
 the legacy ``type``).  The definitions are those of ``transformers.modeling_rope_utils`` (``_compute_llama3_parameters``,
 ``_compute_yarn_parameters``, ``_compute_linear_scaling_rope_parameters``), computed in float64 -- transformers computes in fp32 --
-for head_dim 128, full rotary.  Types whose frequencies depend on the running length (``dynamic``, ``longrope``) or that this tree has
+for the model's real head size (``rope_init(config, head_dim)``: 128 or 64), full rotary.  Types whose frequencies depend on the running length (``dynamic``, ``longrope``) or that this tree has
 no kernel argument for (``proportional``, YaRN's ``mscale`` / ``mscale_all_dim``, a partial rotary factor) raise NotImplementedError
 naming the type: a config is never silently run with other frequencies than its own."""
 import math
@@ -44,13 +44,13 @@ def rope_parameters(config) -> dict:
     return rp
 
 
-def _llama3(rp, base):
+def _llama3(rp, base, head_dim=HEAD_DIM):
     for key in ("factor", "low_freq_factor", "high_freq_factor", "original_max_position_embeddings"):
         if rp.get(key) is None:
             raise ValueError(f"rope type llama3 needs {key!r}")
     factor, low, high = float(rp["factor"]), float(rp["low_freq_factor"]), float(rp["high_freq_factor"])
     old_len = float(rp["original_max_position_embeddings"])
-    inv = 1.0 / base ** (np.arange(0, HEAD_DIM, 2, dtype=np.float64) / HEAD_DIM)
+    inv = 1.0 / base ** (np.arange(0, head_dim, 2, dtype=np.float64) / head_dim)
     wavelen = 2.0 * math.pi / inv
     out = np.where(wavelen > old_len / low, inv / factor, inv)
     smooth = (old_len / wavelen - low) / (high - low)
@@ -59,7 +59,7 @@ def _llama3(rp, base):
     return np.where(medium, smoothed, out), 1.0
 
 
-def _yarn(rp, base, config):
+def _yarn(rp, base, config, head_dim=HEAD_DIM):
     if rp.get("mscale") or rp.get("mscale_all_dim"):
         raise NotImplementedError("rope type 'yarn' with mscale / mscale_all_dim is not implemented")
     if rp.get("original_max_position_embeddings") is None:
@@ -76,23 +76,23 @@ def _yarn(rp, base, config):
     truncate = rp.get("truncate", True)
 
     def correction_dim(rotations):
-        return (HEAD_DIM * math.log(orig / (rotations * 2 * math.pi))) / (2 * math.log(base))
+        return (head_dim * math.log(orig / (rotations * 2 * math.pi))) / (2 * math.log(base))
 
     low, high = correction_dim(beta_fast), correction_dim(beta_slow)
     if truncate:
         low, high = math.floor(low), math.ceil(high)
-    low, high = max(low, 0), min(high, HEAD_DIM - 1)
+    low, high = max(low, 0), min(high, head_dim - 1)
     if low == high:
         high += 0.001
-    pos_freqs = base ** (np.arange(0, HEAD_DIM, 2, dtype=np.float64) / HEAD_DIM)
-    ramp = np.clip((np.arange(HEAD_DIM // 2, dtype=np.float64) - low) / (high - low), 0.0, 1.0)
+    pos_freqs = base ** (np.arange(0, head_dim, 2, dtype=np.float64) / head_dim)
+    ramp = np.clip((np.arange(head_dim // 2, dtype=np.float64) - low) / (high - low), 0.0, 1.0)
     extrapolation = 1.0 - ramp
     inv = (1.0 / (factor * pos_freqs)) * (1.0 - extrapolation) + (1.0 / pos_freqs) * extrapolation
     return inv, float(attention_factor)
 
 
-def rope_init(config):
-    """(theta, rope_scale, inv_freq float64 [64] or None, attention_factor) of a config -- see the module's text"""
+def rope_init(config, head_dim: int = HEAD_DIM):
+    """(theta, rope_scale, inv_freq float64 [head_dim / 2] or None, attention_factor) of a config -- see the module's text"""
     rp = rope_parameters(config)
     theta, kind = rp["rope_theta"], rp["rope_type"]
     if not theta > 0:
@@ -106,9 +106,9 @@ def rope_init(config):
             raise ValueError("rope type linear needs a positive 'factor'")
         return theta, float(rp["factor"]), None, 1.0
     if kind == "llama3":
-        inv, af = _llama3(rp, theta)
+        inv, af = _llama3(rp, theta, head_dim)
         return theta, 1.0, inv, af
     if kind == "yarn":
-        inv, af = _yarn(rp, theta, config)
+        inv, af = _yarn(rp, theta, config, head_dim)
         return theta, 1.0, inv, af
     raise NotImplementedError(f"rope type {kind!r} is not implemented (supported: default, linear, llama3, yarn)")

@@ -565,6 +565,17 @@ def _kv_dims(kv):
     return num_layers, num_heads, page_size, half_dim * 2
 
 
+def _d64(kv) -> bool:
+    """a cache of 64-wide heads: its calls go to the _d64 entry points (csrc/attn_d64.hip); every other cache makes the calls it made"""
+    return _kv_dims(kv)[3] == 64
+
+
+def _refuse_d64(kv, what):
+    if _d64(kv):
+        raise NotImplementedError(f"{what} is not built for head size 64 (csrc/attn_d64.hip serves kv_quant_u4, init_kv_i4 / append_kv_i4, "
+                                  f"batch_prefill_i4 and batch_decode_i4)")
+
+
 def _require_cuda(*tensors):
     for t in tensors:
         if not t.is_cuda:
@@ -588,8 +599,9 @@ def _kv_append(kv, k, v, k_param, v_param, append_indptr, layer_idx, what):
     total = k.size(0)
     assert k.shape == v.shape == (total, num_heads, head_dim // 2) and k.dtype == v.dtype == torch.uint8
     assert k_param.numel() == v_param.numel() == total * num_heads * 2 and k_param.dtype == torch.float16
-    st = L.lib().atom_kv_append_i4(*ptrs, k.contiguous().data_ptr(), v.contiguous().data_ptr(), k_param.contiguous().data_ptr(),
-                                    v_param.contiguous().data_ptr(), L.ptr(append_indptr), total, *dims, L.current_stream(k.device))
+    fn = L.lib().atom_kv_append_i4_d64 if head_dim == 64 else L.lib().atom_kv_append_i4
+    st = fn(*ptrs, k.contiguous().data_ptr(), v.contiguous().data_ptr(), k_param.contiguous().data_ptr(),
+            v_param.contiguous().data_ptr(), L.ptr(append_indptr), total, *dims, L.current_stream(k.device))
     L.check(st, what)
 
 
@@ -617,6 +629,7 @@ def _require_kv_f32(kv, k_f32, v_f32):
 def quant_append_kv_i4(kv, k_f32: torch.Tensor, v_f32: torch.Tensor, layer_idx: int):
     """NEW (fused decode step): quantise the FP32 k / v projections [batch, heads*128] per head (the _o4 epilogue) and
     append them as the last token of every sequence.  Same cache contents as dense_layer_gemm_i4_o4 + append_kv_i4."""
+    _refuse_d64(kv, "quant_append_kv_i4 (the fused quantising append)")
     _require_kv_f32(kv, k_f32, v_f32)
     ptrs, dims, _ = _kv_args(kv, layer_idx)
     st = L.lib().atom_kv_quant_append_f32(*ptrs, k_f32.data_ptr(), v_f32.data_ptr(), *dims, L.current_stream(k_f32.device))
@@ -719,6 +732,11 @@ def decode_splits(batch: int, kv, num_qo_heads: int = None, window: int = None) 
     atom_batch_decode_gqa_i4_ring_splits, and a call without a window or with one wider than the cache's is a ``ValueError``)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     max_pages = int(getattr(kv, "max_pages", 0))
+    if head_dim == 64:                                       # one plan at every head ratio (atom_batch_decode_gqa_i4_d64_splits)
+        if _window_arg(window) is not None:
+            _refuse_d64(kv, "window=")
+        nq = num_heads if num_qo_heads is None else _qo_heads(int(num_qo_heads), num_heads)
+        return int(L.lib().atom_batch_decode_gqa_i4_d64_splits(int(batch), nq, num_heads, page_size, max_pages))
     ring = _ring_start(kv, _window_arg(window)) is not None
     if _window_arg(window) is not None:
         nq = num_heads if num_qo_heads is None else _qo_heads(int(num_qo_heads), num_heads)
@@ -741,28 +759,31 @@ def _decode_outputs(q, merge, ws_bytes, splits):
     return None, part, part
 
 
-def rope_table(inv_freq, device) -> torch.Tensor:
+def rope_table(inv_freq, device, head_dim: int = 128) -> torch.Tensor:
     """The per-pair frequency table of ``batch_decode_i4`` / ``batch_prefill_i4`` (``rope_table=``) from HF-style ``inv_freq`` -- 64
-    values in RADIANS per position, pair i = dims (i, i + 64): divided by 2 pi in float64 and rounded ONCE to fp32, on ``device``.  The
+    values in RADIANS per position, pair i = dims (i, i + 64) (``head_dim=64``: 32 values, pair i = dims (i, i + 32)): divided by 2 pi in
+    float64 and rounded ONCE to fp32, on ``device``.  The
     kernels work in revolutions and use the table as loaded, so the fp32 values returned here are the definition of the angles."""
     import numpy as np
     f = inv_freq.detach().cpu().numpy() if isinstance(inv_freq, torch.Tensor) else inv_freq
     f = np.asarray(f, dtype=np.float64).reshape(-1)
-    if f.shape != (64,):
-        raise ValueError(f"inv_freq must hold 64 values (head_dim 128), got {f.shape[0]}")
+    if head_dim not in (64, 128):
+        raise ValueError(f"head_dim must be 128 or 64, got {head_dim}")
+    if f.shape != (head_dim // 2,):
+        raise ValueError(f"inv_freq must hold {head_dim // 2} values (head_dim {head_dim}), got {f.shape[0]}")
     return torch.from_numpy((f / (2.0 * np.pi)).astype(np.float32)).to(device)
 
 
-def _rope_args(rope_table, attn_scale, device):
+def _rope_args(rope_table, attn_scale, device, pairs=64):
     """(rope_table pointer or None, attn_scale) of the _rope entry points, checked; None where both are at their defaults (the call
     then goes to the entry point without them)"""
     if rope_table is None and isinstance(attn_scale, (int, float)) and float(attn_scale) == 1.0:
         return None
     if rope_table is not None:
         t = rope_table
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.shape == (64,) and t.is_contiguous()):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.shape == (pairs,) and t.is_contiguous()):
             what = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise TypeError(f"rope_table must be a contiguous float32 CUDA tensor of [64] (ops.rope_table), got {what}")
+            raise TypeError(f"rope_table must be a contiguous float32 CUDA tensor of [{pairs}] (ops.rope_table), got {what}")
         if t.device != device:
             raise TypeError(f"rope_table lives on {t.device}, q on {device}")
     return (None if rope_table is None else rope_table.data_ptr()), float(attn_scale)
@@ -789,13 +810,33 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     ``decode_splits(batch, kv, q heads, window=W)``, and ``append_kv`` is refused (the fused append lives in the FP32 decode kernel).
     A rolling cache (utils.RollingKvCacheInt4: it has a ``kv_start`` tensor) takes atom_batch_decode_gqa_i4_ring with the same
     arguments and ``kv.kv_start``: the same positions, masks and angles, read from a page list that starts at ``kv_start[b]``.
-    ``window=None`` or a window wider than the cache's is a ``ValueError`` there.  Every other cache makes exactly the calls above."""
+    ``window=None`` or a window wider than the cache's is a ``ValueError`` there.  Every other cache makes exactly the calls above.
+    A cache of 64-wide heads (``kv.data`` [.., 32]; q [batch, heads, 64]) takes atom_batch_decode_gqa_i4_d64 at every head ratio:
+    ``rope_table`` is then float32 [32]; ``window=``, ``append_kv=``, ``merge=False`` and a rolling cache raise ``NotImplementedError``."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
     gqa = q.dim() == 3 and q.size(1) != num_heads
     nq = _qo_heads(q.size(1), num_heads) if gqa else num_heads
     assert q.shape == (batch, nq, head_dim)
+    if head_dim == 64:
+        # head size 64: atom_batch_decode_gqa_i4_d64 at every head ratio -- the prefill op's kernel with one query per sequence
+        for arg, name in ((window, "window="), (append_kv, "append_kv="), (None if merge else False, "merge=False"),
+                          (getattr(kv, "kv_start", None), "a rolling cache")):
+            if arg is not None:
+                _refuse_d64(kv, name)
+        _require_cuda(kv.data, kv.param)
+        assert batch == kv.last_page_offset.numel() and q.is_contiguous()
+        ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq)
+        lib = L.lib()
+        ws_bytes = lib.atom_batch_decode_gqa_i4_d64_workspace_bytes(batch, nq, num_heads, page_size, max_pages)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        table, scale = _rope_args(rope_table, attn_scale, q.device, 32) or (None, 1.0)
+        st = lib.atom_batch_decode_gqa_i4_d64(o.data_ptr(), q.data_ptr(), *ptrs, *dims, float(rope_theta), float(rope_scale), table, scale,
+                                              max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_decode_gqa_i4_d64")
+        return o
     start = _ring_start(kv, _window_arg(window))
     if start is not None:
         if append_kv is not None:
@@ -880,6 +921,18 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     assert qo_indptr.numel() == batch + 1
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
+    if head_dim == 64:                                      # head size 64: atom_batch_prefill_gqa_i4_d64
+        for arg, name in ((window, "window="), (getattr(kv, "kv_start", None), "a rolling cache")):
+            if arg is not None:
+                _refuse_d64(kv, name)
+        ws_bytes = lib.atom_batch_prefill_gqa_i4_d64_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        table, scale = _rope_args(rope_table, attn_scale, q.device, 32) or (None, 1.0)
+        st = lib.atom_batch_prefill_gqa_i4_d64(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
+                                               float(rope_scale), table, scale, max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_prefill_gqa_i4_d64")
+        return o
     start = _ring_start(kv, _window_arg(window))
     if start is not None:
         _require_cuda(start)
@@ -1177,13 +1230,15 @@ def add_lora(y: torch.Tensor, x: torch.Tensor, wa_T_all: torch.Tensor, wb_T_all:
 
 def kv_quant_u4(k: torch.Tensor):
     """NEW: fp16 k (or v) [T, kv_heads, 128] -> (packed u8 [T, kv_heads, 64], params fp16 [T, kv_heads, 2]) in the form ``init_kv_i4`` /
-    ``append_kv_i4`` take: the per-head quantiser of ``quant_append_kv_i4`` applied to ``k.float()``, without a cache."""
+    ``append_kv_i4`` take: the per-head quantiser of ``quant_append_kv_i4`` applied to ``k.float()``, without a cache.  Head size 64
+    ([T, kv_heads, 64] -> u8 [T, kv_heads, 32]): the same rule over the 64 values (atom_kv_quant_u4_f16_d64)."""
     _require_cuda_half(k, "k")
     t, heads, d = k.shape
     packed = torch.empty((t, heads, d // 2), dtype=torch.uint8, device=k.device)
     params = torch.empty((t, heads, 2), dtype=torch.float16, device=k.device)
-    st = L.lib().atom_kv_quant_u4_f16(k.data_ptr(), packed.data_ptr(), params.data_ptr(), t, heads, d, L.current_stream(k.device))
-    L.check(st, "atom_kv_quant_u4_f16")
+    name = "atom_kv_quant_u4_f16_d64" if d == 64 else "atom_kv_quant_u4_f16"   # (head size 64: 16 lanes per vector, csrc/attn_d64.hip)
+    st = getattr(L.lib(), name)(k.data_ptr(), packed.data_ptr(), params.data_ptr(), t, heads, d, L.current_stream(k.device))
+    L.check(st, name)
     return packed, params
 
 
@@ -1489,6 +1544,7 @@ def kv_beam_fork_i4(kv, parent: torch.Tensor):
     ``kv.table_out``, and one device-to-device copy on the same stream brings ``kv.page_table`` / ``kv.spare`` up to date, so
     ``ops.kv_step_i4`` keeps reading the one fixed table.  Two stream operations, no host synchronisation, capturable.  A parent outside
     the group keeps its row and sets the cache's status word (read by ``kv.sync_host()``)."""
+    _refuse_d64(kv, "kv_beam_fork_i4 (beam search)")
     tensors = (kv.page_table, kv.table_out, kv.spare, kv.spare_out, kv.row_pages, kv.lengths, kv.state, parent)
     for t in tensors + (kv.data, kv.param):
         if not t.is_cuda:

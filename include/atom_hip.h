@@ -591,6 +591,53 @@ int atom_batch_prefill_gqa_i4_ring(void *o, const void *q, const int32_t *qo_ind
                                    const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
                                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* Head size 64 (csrc/attn_d64.hip; Llama-3.2-1B, TinyLlama, SmolLM2: 64-wide heads).  Every entry point above keeps refusing
+ * head_dim = 64 with ATOM_ERR_SHAPE; these take head_dim = 64 and refuse everything else the same way.  Argument order: that of the
+ * 128 counterpart (atom_kv_quant_u4_f16, atom_kv_append_i4, atom_batch_prefill_gqa_i4_rope, atom_batch_decode_gqa_i4_rope).
+ *   Cache: kv_data u8 [pages, L, 2, N, P, 32], kv_param f16 [pages, L, 2, N, P, 2]; dim d of a head vector in byte d / 2, low nibble
+ *   first; (scale, zero) per (token, head) over the 64 values: scale = (hi - lo) / 15, zero = -lo, round half away from zero, clamp to
+ *   0 .. 15, all codes 0 where scale == 0.  RoPE pairs (i, i + 32), frequency theta^(-2 i / 64) / rope_scale; rope_table (or NULL) is
+ *   float32 [32], revolutions per position of pair i, and with it the angle is the exact product (rope_math.h).  The logits are scaled
+ *   by attn_scale / sqrt(64).
+ *   atom_kv_quant_u4_f16_d64: k fp16 [T, kv_heads, 64] -> packed u8 [T, kv_heads, 32] + param fp16 [T, kv_heads, 2].
+ *   atom_kv_append_i4_d64: those operands into the pages; append_indptr int32 [batch + 1] (prompts: each sequence's tokens are its
+ *   LAST ones) or NULL (one token per sequence, total_tokens == batch).
+ *   atom_batch_prefill_gqa_i4_d64 / atom_batch_decode_gqa_i4_d64: causal attention, row r of (sequence, K/V head h) is query r / G of
+ *   query head h G + r % G (G = num_qo_heads / num_kv_heads; 1: MHA); the decode entry is the prefill entry with one query per
+ *   sequence.  One kernel on 128-key tiles with fp16 MFMA operands; keys past a sequence's end are never loaded; read-only on the
+ *   cache; no host synchronisation.  `o` is required (no un-merged form).
+ *   Plan: _splits is the number of KV splits the call takes when the workspace holds them, _workspace_bytes their partial states,
+ *   float [rows][heads][splits][66] (64 un-normalised values, the running maximum in base 2, the denominator): rows * heads * splits
+ *   * 66 * 4 bytes when splits > 1, else 0.  A missing, small or misaligned workspace runs the call unsplit.  Queries answer 0 for
+ *   rejected shapes.
+ * Errors, in order: head counts that do not divide, head_dim != 64 or another bad cache dimension ATOM_ERR_SHAPE (null cache pointers
+ * ATOM_ERR_INVALID_ARG in front, cache misalignment ATOM_ERR_ALIGN behind); null q / o / qo_indptr or a non-positive rope_theta /
+ * rope_scale ATOM_ERR_INVALID_ARG; total_q / max_q_len < 1 ATOM_ERR_SHAPE; o / q not 16-byte or qo_indptr not 4-byte aligned
+ * ATOM_ERR_ALIGN; attn_scale not positive ATOM_ERR_INVALID_ARG; rope_table not 4-byte aligned ATOM_ERR_ALIGN.
+ * Not built for head 64: sliding window, ring, beam fork, the fused quantising appends, the un-merged decode output. */
+int atom_kv_quant_u4_f16_d64(const void *k, void *packed, void *param, int64_t T, int kv_heads, int head_dim, void *stream);
+int atom_kv_append_i4_d64(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                          const int32_t *last_page_offset, const void *k, const void *v, const void *k_param, const void *v_param,
+                          const int32_t *append_indptr, int64_t total_tokens, int batch, int num_layers, int layer_idx, int num_heads,
+                          int page_size, int head_dim, void *stream);
+size_t atom_batch_prefill_gqa_i4_d64_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                     int max_q_len, int max_pages_per_seq);
+int atom_batch_prefill_gqa_i4_d64_splits(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_q_len,
+                                         int max_pages_per_seq);
+size_t atom_batch_decode_gqa_i4_d64_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq);
+int atom_batch_decode_gqa_i4_d64_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq);
+int atom_batch_prefill_gqa_i4_d64(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                  const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                  const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                  int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int atom_batch_decode_gqa_i4_d64(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                 const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                 int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                 const float *rope_table, float attn_scale, int max_pages_per_seq, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
 /* Page tables stepped on the device (csrc/kv_step.hip): rebuilds kv_indptr / kv_indices / last_page_offset -- the layout above, what
  * every attention and append entry point reads -- in ONE launch from buffers at fixed addresses, so that a captured decode step can
  * be replayed for the next token with no host work in between.

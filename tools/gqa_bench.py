@@ -17,7 +17,11 @@ run-to-run difference).  --theta-only skips the table path: the same figures fro
 --window W: instead, sliding-window attention (atom_batch_decode_gqa_i4_win / atom_batch_prefill_gqa_i4_win).  Per batch 1 / 16 / 64
 the windowed decode op at contexts 4 W and 8 W against the un-windowed op of the same build at context W (the same keys staged) and at
 the full context, and the windowed prefill of 1 x 2 W against the un-windowed one; every figure timed twice in alternation (the two
-figures of the un-windowed op at context W are the spread the comparison is read against)."""
+figures of the un-windowed op at context W are the spread the comparison is read against).
+
+--head-dim 64: instead, the head-64 ops (csrc/attn_d64.hip) at Llama-3.2-1B heads -- 32 query heads on 8 K/V heads of 64 -- against the
+128 ops on a cache of EQUAL BYTES (16 query heads on 4 K/V heads of 128: the same K/V bytes, the same q and o bytes, the same FLOPs),
+on the decode and prefill shapes above, every figure timed twice in alternation."""
 import argparse
 import json
 import os
@@ -51,10 +55,10 @@ def _time(fn, iters, warmup):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-def _caches(seqlens, heads=NKV, layers=1):
+def _caches(seqlens, heads=NKV, layers=1, head_dim=128):
     """a random cache of `heads` heads, and the same contents replicated to NQ heads"""
     dev = torch.device("cuda")
-    pool = KvPoolInt4(layers, heads, 128, sum(-(-s // BLOCK) for s in seqlens) + 1, BLOCK, dev)
+    pool = KvPoolInt4(layers, heads, head_dim, sum(-(-s // BLOCK) for s in seqlens) + 1, BLOCK, dev)
     pool.buf.copy_(torch.randint(0, 256, pool.buf.shape, device=dev, dtype=torch.uint8))
     pool.param.copy_((torch.rand(pool.param.shape, device=dev) * 0.2 + 0.01).half())
     kv = BatchedKvCacheInt4([KvCacheInt4(pool, s) for s in seqlens])
@@ -200,6 +204,36 @@ def window(W, iters, warmup):
     return out
 
 
+def head64(iters, warmup, only):
+    """head 64 at 32 / 8 heads against head 128 at 16 / 4 heads on a cache of equal bytes: decode steps and prefill shapes"""
+    out = []
+    shapes = [(n, [(c - 1, 1)] * b, True) for n, (b, c) in DECODE.items()] + [(n, s, False) for n, s in PREFILL.items()]
+    for name, seqs, dec in shapes:
+        if only not in (None, "decode" if dec else "prefill", name):
+            continue
+        seqlens, qlens = [a + n for a, n in seqs], [n for _, n in seqs]
+        T, mq = sum(qlens), max(qlens)
+        qo = torch.tensor([0] + torch.tensor(qlens).cumsum(0).tolist(), dtype=torch.int32, device="cuda")
+        runs, keep = {}, []
+        for hd, nq, nkv in ((64, NQ, NKV), (128, NQ // 2, NKV // 2)):
+            pool, kv, _ = _caches(seqlens, heads=nkv, head_dim=hd)
+            keep.append(pool)
+            q = torch.randn((T, nq, hd), device="cuda").half()
+            fn = (lambda q=q, kv=kv: ops.batch_decode_i4(q, kv, 0)) if dec else (lambda q=q, kv=kv: ops.batch_prefill_i4(q, qo, kv, 0, max_q_len=mq))
+            runs[f"d{hd}"] = (fn, ops.decode_splits(len(seqs), kv, nq) if dec else None)
+        it = iters if T < 1024 else max(3, iters // 4)
+        r = {"shape": name, "decode": dec, "splits_d64": runs["d64"][1], "splits_d128": runs["d128"][1]}
+        for rnd in (1, 2):
+            for key, (fn, _) in runs.items():
+                r[f"{key}_us_{rnd}"] = _time(fn, it, warmup)
+        r["d64_over_d128"] = min(r["d64_us_1"], r["d64_us_2"]) / min(r["d128_us_1"], r["d128_us_2"])
+        print(f"HEAD64  {name:18s} head 64 (32 on 8) {r['d64_us_1']:9.1f} / {r['d64_us_2']:9.1f} us  head 128 (16 on 4) {r['d128_us_1']:9.1f} / "
+              f"{r['d128_us_2']:9.1f} us  ({r['d64_over_d128']:.3f}x)  splits {r['splits_d64']} / {r['splits_d128']}", flush=True)
+        out.append(r)
+        del runs, keep
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -208,7 +242,11 @@ def main():
     ap.add_argument("--rope-table", action="store_true", help="theta path against table path on the Llama-3.1-8B shapes")
     ap.add_argument("--theta-only", action="store_true", help="with --rope-table: the theta path alone")
     ap.add_argument("--window", type=int, default=None, help="sliding-window attention with this window (4096: Mistral-7B-v0.1)")
+    ap.add_argument("--head-dim", type=int, default=128, choices=(64, 128), help="64: the head-64 ops against the 128 ops on equal bytes")
     a = ap.parse_args()
+    if a.head_dim == 64:
+        print(json.dumps({"gqa_bench_head64": head64(a.iters, a.warmup, a.only)}))
+        return
     if a.window is not None:
         print(json.dumps({"gqa_bench_window": window(a.window, a.iters, a.warmup)}))
         return
