@@ -108,6 +108,12 @@ SIGNATURES = {
     "atom_batch_decode_gqa_i4_ring_workspace_bytes": (ctypes.c_size_t, [_int] * 6),
     "atom_batch_decode_gqa_i4_ring_splits": (_int, [_int] * 6),
     "atom_batch_prefill_gqa_i4_ring_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 7),
+    # attention sinks: the _ring lists with (sinks, pos_shift) behind kv_start; plan queries of their own with the _ring queries' arguments
+    "atom_batch_decode_gqa_i4_sink": (_int, [_vp] * 7 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, _int, _vp, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_prefill_gqa_i4_sink": (_int, [_vp, _vp, _vp, _i64, _int] + [_vp] * 5 + [_int] * 7 + [_f32, _f32, _vp, _f32, _int, _vp, _int, _vp, _int, _vp, ctypes.c_size_t, _vp]),
+    "atom_batch_decode_gqa_i4_sink_workspace_bytes": (ctypes.c_size_t, [_int] * 6),
+    "atom_batch_decode_gqa_i4_sink_splits": (_int, [_int] * 6),
+    "atom_batch_prefill_gqa_i4_sink_workspace_bytes": (ctypes.c_size_t, [_i64] + [_int] * 7),
     # head size 64 (csrc/attn_d64.hip): the argument lists of atom_kv_quant_u4_f16, atom_kv_append_i4 and the _rope attention entries
     "atom_kv_quant_u4_f16_d64": (_int, [_vp] * 3 + [_i64, _int, _int, _vp]),
     "atom_kv_append_i4_d64": (_int, [_vp] * 10 + [_i64] + [_int] * 6 + [_vp]),
@@ -119,6 +125,7 @@ SIGNATURES = {
     "atom_batch_prefill_gqa_i4_d64_splits": (_int, [_i64] + [_int] * 6),
     "atom_kv_step_i4": (_int, [_vp] * 7 + [_int] * 4 + [_vp]),
     "atom_kv_step_ring_i4": (_int, [_vp] * 7 + [_int] * 5 + [_vp, _vp]),
+    "atom_kv_step_sink_i4": (_int, [_vp] * 7 + [_int] * 6 + [_vp, _vp, _vp]),
     "atom_moe_max_tiles": (_i64, [_i64, _int]),
     "atom_moe_route_topk": (_int, [_vp, _i64, _int, _int] + [_vp] * 9),
     "atom_moe_gemm_w4a4_f16": (_int, [_vp] * 15 + [_i64, _i64, _int, _i64, _int, _i64, _int, _int, _int, _vp]),

@@ -36,6 +36,14 @@
 // l - R < f (l - f + 1 <= R), which is no longer listed -- no listed page is ever written over.  The bytes of that slot beyond n are
 // the old tenant's, stale: they must never be read, and the attention kernels stop at the length (keys >= len are staged as zeros and
 // not loaded); the append kernels write a token's slot before any launch reads it.
+//
+// atom_kv_step_sink_i4 (attention sinks) is the ring step with the first SP = ceil(S / P) slots of a row pinned: slots
+// 0 .. SP - 1 hold logical pages 0 .. SP - 1 and are never reused; logical page g >= SP lives in slot SP + (g - SP) % R', R' = the
+// row's slots - SP.  For the new length n the live ring pages are f .. l with f = max(SP, max(0, n - max(add, 1) - W + 1) / P),
+// l = (n - 1) / P; kv_indices lists the sink pages that exist (min(SP, l + 1)), then f .. l in logical order; kv_start[b] = f P and
+// pos_shift[b] = max(0, n - max(add, 1) - W + 1 - S), the keys evicted between the sinks and the window of the step's first row
+// (what the _sink attention entries take: prefill_i4.hip, kSink).  More live ring pages than R', or more sink pages than slots: the
+// sequence is not advanced, overflow bit.
 #include <type_traits>
 
 #include "common.h"
@@ -105,6 +113,45 @@ __device__ __forceinline__ int ring_len(int len, int add, int W, int row_pages, 
   return len;
 }
 
+// atom_kv_step_sink_i4: a third block, for the same reason
+struct KvSinkParams : KvRingParams {
+  int sinks;             // S in 1 .. 64
+  int32_t *shift;        // pos_shift [batch]
+};
+
+// The sink step of one sequence (atom_kv_step_sink_i4): ns sink pages listed (logical pages 0 .. ns - 1, slots 0 .. ns - 1), then cnt
+// ring pages from logical page f >= SP on; shift = the row's pos_shift.  The row has `slots` = min(row_pages, cap) slots, SP of them
+// pinned (all of them where slots <= SP: then no ring page fits).  Refusal and clamping as ring_len: a request that does not fit keeps
+// the length and gets the tables of a step of 0 tokens to it; a stored length that the slots cannot describe is flagged and its ring
+// part cut to the last R' pages -- with no ring slot, or too few sink slots, the sequence is emptied.  So ns <= min(SP, slots) and
+// cnt <= R' whatever the buffers hold, and every index the copy forms lies inside the row.
+struct SinkRow {
+  int f, cnt, ns, shift;
+};
+__device__ __forceinline__ SinkRow sink_pages(int n, int add, int W, int S, int SP, int P) {
+  if (n <= 0) return SinkRow{SP, 0, 0, 0};
+  const int lo = n - max(add, 1) - W + 1, l = (n - 1) / P;
+  const int f = max(SP, max(lo, 0) / P);
+  return SinkRow{f, max(l - f + 1, 0), min(SP, l + 1), max(lo - S, 0)};
+}
+__device__ __forceinline__ int sink_len(int len, int add, int W, int S, int row_pages, int cap, int P, int &flag, SinkRow &pg) {
+  const int slots = min(max(row_pages, 0), cap), SP = (S + P - 1) / P;
+  const int ssl = min(SP, slots), R = slots - ssl;
+  flag = 0;
+  if (len < 0) { len = 0; flag = ATOM_KV_STEP_BAD_LENGTH; }
+  if (len > 0x7fffffff - add) { len = 0x7fffffff - add; flag = ATOM_KV_STEP_BAD_LENGTH; }
+  pg = sink_pages(len + add, add, W, S, SP, P);
+  if (pg.ns <= ssl && pg.cnt <= R) return len + add;
+  flag |= ATOM_KV_STEP_OVERFLOW;
+  pg = sink_pages(len, 0, W, S, SP, P);
+  if (pg.ns > ssl || pg.cnt > R) {                         // (the stored length itself is outside what the slots can hold)
+    flag |= ATOM_KV_STEP_BAD_LENGTH;
+    if (R == 0 || pg.ns > ssl) { pg = SinkRow{SP, 0, 0, 0}; return 0; }
+    pg.f += pg.cnt - R, pg.cnt = R;
+  }
+  return len;
+}
+
 template <bool RING>
 struct RingLds {};
 template <>
@@ -112,14 +159,25 @@ struct RingLds<true> {
   int rot[kStepRows], slots[kStepRows];                   // per sequence of the group: f % R and R
 };
 
+template <bool SINK>
+struct SinkLds {};
+template <>
+struct SinkLds<true> {
+  int rot[kStepRows], slots[kStepRows], ns[kStepRows];    // per sequence of the group: (f - SP) % R', R' and the sink pages listed
+};
+
 // ROWS: atom_kv_step_rows_i4 (p.adds, p.look); else the scalar step (p.add for every sequence, no look-ahead: tab == the new length)
 // RING: atom_kv_step_ring_i4 (KvRingParams: p.window, p.start; never with ROWS) -- all of its code sits under `if constexpr (RING)`
-template <bool ROWS, bool RING = false>
-__global__ __launch_bounds__(kStepThreads) void kv_step_kernel(std::conditional_t<RING, KvRingParams, KvStepParams> p) {
+// SINK: atom_kv_step_sink_i4 (KvSinkParams: p.sinks, p.shift too; never with ROWS or RING) -- ... under `if constexpr (SINK)`
+template <bool ROWS, bool RING = false, bool SINK = false>
+__global__ __launch_bounds__(kStepThreads) void kv_step_kernel(
+    std::conditional_t<SINK, KvSinkParams, std::conditional_t<RING, KvRingParams, KvStepParams>> p) {
   static_assert(!(ROWS && RING), "the ring step has no per-sequence counts");
+  static_assert(!(SINK && (ROWS || RING)), "the sink step is a kernel of its own");
   __shared__ int s_part[kStepThreads / 64];
   __shared__ int s_off[kStepRows], s_cnt[kStepRows];
   [[maybe_unused]] __shared__ RingLds<RING> s_ring;
+  [[maybe_unused]] __shared__ SinkLds<SINK> s_sink;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int parity = p.state[1] & 1;
   const int32_t *cur = p.lens + (int64_t)parity * p.batch;
@@ -131,8 +189,12 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(std::conditional_
   // pages of every sequence in front of this group
   int acc = 0, flag, tab;
   [[maybe_unused]] RingRow pg{0, 0};
+  [[maybe_unused]] SinkRow sg{0, 0, 0, 0};
   for (int r = tid; r < row0; r += kStepThreads) {
-    if constexpr (RING) {
+    if constexpr (SINK) {
+      sink_len(cur[r], p.add, p.window, p.sinks, p.rows[r], p.cap, p.P, flag, sg);
+      acc += sg.ns + sg.cnt;
+    } else if constexpr (RING) {
       ring_len(cur[r], p.add, p.window, p.rows[r], p.cap, p.P, flag, pg);
       acc += pg.cnt;
     } else {
@@ -149,7 +211,19 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(std::conditional_
   int len = 0, cnt = 0, inc = 0;
   flag = 0, tab = 0;
   if (wave == 0) {
-    if constexpr (RING) {
+    if constexpr (SINK) {
+      sg = SinkRow{0, 0, 0, 0};
+      int R = 0, SP = 0;
+      if (row < p.batch) {
+        len = sink_len(cur[row], p.add, p.window, p.sinks, p.rows[row], p.cap, p.P, flag, sg);
+        cnt = sg.ns + sg.cnt, tab = len;
+        SP = (p.sinks + p.P - 1) / p.P;
+        R = max(min(max(p.rows[row], 0), p.cap) - SP, 0);
+      }
+      s_sink.rot[lane] = R > 0 ? (sg.f - SP) % R : 0;     // (f >= SP)
+      s_sink.slots[lane] = R;
+      s_sink.ns[lane] = sg.ns;
+    } else if constexpr (RING) {
       pg = RingRow{0, 0};
       int R = 0;
       if (row < p.batch) {
@@ -181,6 +255,7 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(std::conditional_
     p.indptr[row + 1] = base + inc;
     if (row == 0) p.indptr[0] = 0;
     if constexpr (RING) p.start[row] = pg.f * p.P;        // (f P <= len: no overflow)
+    if constexpr (SINK) p.start[row] = sg.f * p.P, p.shift[row] = sg.shift;   // (f P <= max(len, SP P): no overflow)
     if (flag) atomicOr(&p.state[0], flag);
   }
 
@@ -191,7 +266,14 @@ __global__ __launch_bounds__(kStepThreads) void kv_step_kernel(std::conditional_
     const int n = s_cnt[r];
     const int32_t *src = p.table + (int64_t)(row0 + r) * p.cap;
     int32_t *dst = p.indices + base + s_off[r];
-    if constexpr (RING) {                                   // logical order: entry j is slot (f + j) % R; j < n <= R <= cap
+    if constexpr (SINK) {                                   // entries j < ns: slot j; then k = j - ns < R': slot SP + (rot + k) % R'
+      const int rot = s_sink.rot[r], R = s_sink.slots[r], ns = s_sink.ns[r];   // (a ring entry exists only where the row has SP + R' slots)
+      const int SP = (p.sinks + p.P - 1) / p.P;
+      for (int j = blockIdx.y * 64 + lane; j < n; j += stride) {
+        const int k = rot + j - ns;
+        dst[j] = src[j < ns ? j : SP + k - (k >= R ? R : 0)];
+      }
+    } else if constexpr (RING) {                            // logical order: entry j is slot (f + j) % R; j < n <= R <= cap
       const int rot = s_ring.rot[r], R = s_ring.slots[r];
       for (int j = blockIdx.y * 64 + lane; j < n; j += stride) dst[j] = src[rot + j - (rot + j >= R ? R : 0)];
     } else {
@@ -222,18 +304,21 @@ static int step_slices(int batch, int cap) {
   return s;
 }
 
-// the checks all entries share (`adds`: null for the scalar entries; ring: window and kv_start too), then the launch
-static int kv_step(KvRingParams p, bool rows, hipStream_t stream, bool ring = false) {
+// the checks all entries share (`adds`: null for the scalar entries; ring: window and kv_start too; sink: those, sinks and pos_shift),
+// then the launch
+static int kv_step(KvSinkParams p, bool rows, hipStream_t stream, bool ring = false, bool sink = false) {
   if (!p.table || !p.rows || !p.lens || !p.indptr || !p.indices || !p.lpo || !p.state || (rows && !p.adds)) return ATOM_ERR_INVALID_ARG;
   if (p.add < 0 || p.look < 0) return ATOM_ERR_INVALID_ARG;
   if (ring && (p.window < 1 || !p.start)) return ATOM_ERR_INVALID_ARG;
+  if (sink && (p.sinks < 1 || p.sinks > 64 || !p.shift)) return ATOM_ERR_INVALID_ARG;
   if (p.batch < 1 || p.cap < 1 || p.P < 16 || (p.P % 16) != 0) return ATOM_ERR_SHAPE;
   if ((int64_t)p.cap * p.P > 0x7fffffff || (int64_t)p.batch * p.cap > 0x7fffffff) return ATOM_ERR_SHAPE;
   for (const void *q : {(const void *)p.table, (const void *)p.rows, (const void *)p.lens, (const void *)p.indptr, (const void *)p.indices,
-                        (const void *)p.lpo, (const void *)p.state, (const void *)p.adds, (const void *)p.start})
+                        (const void *)p.lpo, (const void *)p.state, (const void *)p.adds, (const void *)p.start, (const void *)p.shift})
     if (off_by(q, 3u)) return ATOM_ERR_ALIGN;
   const dim3 grid((unsigned)((p.batch + kStepRows - 1) / kStepRows), (unsigned)step_slices(p.batch, p.cap));
-  if (ring) hipLaunchKernelGGL((kv_step_kernel<false, true>), grid, dim3(kStepThreads), 0, stream, p);
+  if (sink) hipLaunchKernelGGL((kv_step_kernel<false, false, true>), grid, dim3(kStepThreads), 0, stream, p);
+  else if (ring) hipLaunchKernelGGL((kv_step_kernel<false, true>), grid, dim3(kStepThreads), 0, stream, static_cast<const KvRingParams &>(p));
   else if (rows) hipLaunchKernelGGL(kv_step_kernel<true>, grid, dim3(kStepThreads), 0, stream, static_cast<const KvStepParams &>(p));
   else hipLaunchKernelGGL(kv_step_kernel<false>, grid, dim3(kStepThreads), 0, stream, static_cast<const KvStepParams &>(p));
   return check_launch();
@@ -247,23 +332,31 @@ extern "C" {
 
 int atom_kv_step_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                     int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, void *stream) {
-  return kv_step(KvRingParams{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0}, 0, nullptr},
+  return kv_step(KvSinkParams{{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0}, 0, nullptr}, 0, nullptr},
                  false, reinterpret_cast<hipStream_t>(stream));
 }
 
 int atom_kv_step_rows_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                          int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, const int32_t *adds, int lookahead,
                          void *stream) {
-  return kv_step(KvRingParams{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, 0, adds, lookahead}, 0, nullptr},
+  return kv_step(KvSinkParams{{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, 0, adds, lookahead}, 0, nullptr}, 0, nullptr},
                  true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int atom_kv_step_ring_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                          int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, int window,
                          int32_t *kv_start, void *stream) {
-  return kv_step(KvRingParams{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0},
-                              window, kv_start},
+  return kv_step(KvSinkParams{{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0},
+                               window, kv_start}, 0, nullptr},
                  false, reinterpret_cast<hipStream_t>(stream), true);
+}
+
+int atom_kv_step_sink_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                         int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, int window, int sinks,
+                         int32_t *kv_start, int32_t *pos_shift, void *stream) {
+  return kv_step(KvSinkParams{{{page_table, row_pages, lens, kv_indptr, kv_indices, last_page_offset, state, batch, cap, page_size, add, nullptr, 0},
+                               window, kv_start}, sinks, pos_shift},
+                 false, reinterpret_cast<hipStream_t>(stream), true, true);
 }
 
 }  // extern "C"

@@ -70,6 +70,8 @@ struct PrefillParams {
   const float *rope_table;   // kTable kernels only: float[64], revolutions per position of pair i (the _rope entry points)
   int window;        // kWindow kernels only: W >= 1, the query at position p sees keys p - W < j <= p (the _win entry points)
   const int32_t *kv_start;   // kStart kernels only: int32 [batch], the position of each page list's first token (the _ring entry points)
+  int sinks;                 // kSink kernels only: S in 1 .. 64, keys j < S stay visible to every row behind them (the _sink entry points)
+  const int32_t *pos_shift;  // ... and int32 [batch], what the RoPE position of the query and of every key j >= S is lowered by; NULL: 0
 };
 
 // sin / cos of 2*pi*rev (v_sin_f32 / v_cos_f32 take revolutions)
@@ -106,9 +108,19 @@ __device__ __forceinline__ int v_off(int key, int ch) { return key * 256 + 16 * 
 // operations in the same order.  Keys below `start` are not loaded and staged as zeros (as those past the end); the ring step keeps
 // start <= p - W + 1 for every live row, so the lower select masks them.  tlo is clamped to start / 64: a caller that breaks the
 // guarantee gets a finite, unspecified result and never a read outside the listed pages.
-template <bool kGqa, bool kTable = false, bool kWindow = false, bool kStart = false>
+// kSink (the _sink entry points; only with kGqa and kWindow; prefill_sink.hip): attention sinks, S = p.sinks in 1 .. 64.  MASK: the row at
+// p sees key j iff j <= p and (j < S or j > p - W).  ROPE: the query rotates by p - shift, a key j < S by j, a key j >= S by j - shift,
+// shift = p.pos_shift[b] (an input: the kernel knows no policy; the ring step computes it).  Every other quantity stays absolute.
+//   tiles   a block's tile sequence is the sink tile 0 followed by [tlo, ntiles) -- tile 0 once where tlo == 0 -- and the KV splits
+//           divide that sequence's count; tile 0 is exempt from the below-the-window skip, and the lower select spares keys < S.
+//   list    with kStart the list is SP = ceil(S / P) sink pages, then the ring pages from start = kv_start[b] on: key j < SP P comes
+//           from page j / P, key j >= start from page SP + (j - start) / P, anything between is staged as zeros (always masked).  A
+//           list of at most SP pages has no ring part.  Both branches index below the list's page count whatever the three inputs hold.
+//   angle   under kTable the exact / short product is chosen per tile from the tile's first ROTATED position (tile 0: 0).
+template <bool kGqa, bool kTable = false, bool kWindow = false, bool kStart = false, bool kSink = false>
 __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams p) {
   static_assert(!kStart || (kGqa && kWindow), "a list that starts behind position 0 is read only under a window");
+  static_assert(!kSink || (kGqa && kWindow), "sinks are the keys a window would drop");
   __shared__ __attribute__((aligned(16))) half_t Ks[kPfKeys * kHeadDim];
   __shared__ __attribute__((aligned(16))) half_t Vs[kPfKeys * kHeadDim];
   __shared__ float rope_fr[64];
@@ -133,12 +145,32 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const int pg0 = p.kv_indptr[b];
   [[maybe_unused]] int start = 0;                         // position of the page list's first token
   if constexpr (kStart) start = p.kv_start[b];
-  const int len = start + (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
+  [[maybe_unused]] int nsink = 0, SP = 0, shift = 0;          // kSink: sinks, their pages, the sequence's position shift
+  if constexpr (kSink) {
+    nsink = p.sinks, SP = (nsink + P - 1) / P;
+    if (p.pos_shift) shift = p.pos_shift[b];
+  }
+  int len = start + (p.kv_indptr[b + 1] - pg0 - 1) * P + p.last_page_offset[b];
+  if constexpr (kSink && kStart) {                        // SP sink pages in front of the ring part, or no ring part at all
+    const int npg = p.kv_indptr[b + 1] - pg0;
+    if (npg <= SP) start = SP * P;                        // (then len <= start: no key takes the ring branch of load())
+    len = (npg <= SP ? 0 : start - SP * P) + (npg - 1) * P + p.last_page_offset[b];
+  }
   const int prefix = len - q_b;                           // position of query 0
   const int kend = prefix + (min(q0 + kPfRows, nrows) + G - 1) / G;   // keys this block sees: 0 .. kend-1
   const int ntiles = kend > 0 ? (kend + kPfKeys - 1) / kPfKeys : 0;
   int t0, t1;
-  if constexpr (kWindow) {                                // the splits divide [tlo, ntiles): tlo holds the lowest key of the block's first row
+  [[maybe_unused]] int tl = 0, sk = 0;                    // kSink: index i of the block's tile sequence is tile (i < sk ? 0 : tl + i - sk)
+  if constexpr (kSink) {                                  // [t0, t1) are indices of that sequence, which the splits divide
+    tl = max(prefix + q0 / G - p.window + 1, 0) / kPfKeys;
+    // the 4.23 clamp, for tiles behind the sink pages only: a tile that starts inside them (tl * 64 < SP P) is listed and may be in the
+    // window while start = SP P lies beyond it; load() is bounded by in_list without the clamp
+    if constexpr (kStart) { if (tl * kPfKeys >= SP * P) tl = max(tl, start / kPfKeys); }
+    sk = tl > 0 ? 1 : 0;
+    const int count = ntiles > 0 ? sk + max(ntiles - tl, 0) : 0;
+    const int chunk = (count + p.splits - 1) / p.splits;
+    t0 = sp * chunk, t1 = min(count, t0 + chunk);
+  } else if constexpr (kWindow) {                                // the splits divide [tlo, ntiles): tlo holds the lowest key of the block's first row
     int tlo = max(prefix + q0 / G - p.window + 1, 0) / kPfKeys;
     if constexpr (kStart) tlo = max(tlo, start / kPfKeys);   // (a no-op under the ring step's guarantee: no tile wholly below the list)
     const int chunk = (max(ntiles - tlo, 0) + p.splits - 1) / p.splits;
@@ -163,6 +195,7 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   const bool row_ok = ri < nrows;
   const int qi = ri / G, hq = h * G + (ri - qi * G);      // query index within the sequence, query head
   const int pos = prefix + qi;
+  const int rpos = kSink ? pos - shift : pos;             // the position the query rotates by
   const bool wave_live = q0 + 16 * w < nrows;             // (wave-uniform) any row of this wave exists
   const int pmin_w = prefix + (q0 + 16 * w) / G, pmax_w = prefix + (q0 + 16 * w + 15) / G;
   pf_h8 qf[4];
@@ -178,9 +211,9 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
       for (int j = 0; j < 8; ++j) {
         float s, c;
         if constexpr (kTable)
-          rope_sincos_exact((float)pos, rope_fr[32 * hf + 8 * g + j], s, c);
+          rope_sincos_exact((float)rpos, rope_fr[32 * hf + 8 * g + j], s, c);
         else
-          pf_sincos_rev((float)pos * rope_fr[32 * hf + 8 * g + j], s, c);
+          pf_sincos_rev((float)rpos * rope_fr[32 * hf + 8 * g + j], s, c);
         const float x1 = (float)x[hf][j], x2 = (float)x[hf + 2][j];
         qf[hf][j] = (half_t)(x1 * c - x2 * s);
         qf[hf + 2][j] = (half_t)(x2 * c + x1 * s);
@@ -197,9 +230,13 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
     PfTileRegs r;
     const int j = tile * kPfKeys + kk;
     bool in_list = j < len;
-    if constexpr (kStart) in_list = in_list && j >= start;   // 0 <= (j - start) / P < the list's pages, whatever kv_start holds
+    if constexpr (kSink && kStart)
+      in_list = in_list && (j < SP * P || j >= start);       // j / P < min(SP, pages); SP + (j - start) / P < pages (len's definition)
+    else if constexpr (kStart)
+      in_list = in_list && j >= start;                       // 0 <= (j - start) / P < the list's pages, whatever kv_start holds
     if (in_list) {
-      const int jl = kStart ? j - start : j;
+      int jl = kStart ? j - start : j;
+      if constexpr (kSink && kStart) jl = j < SP * P ? j : jl + SP * P;
       const int pg = jl / P, e = jl - pg * P;
       const int64_t page = p.kv_indices[pg0 + pg];
       const uint8_t *kp = kbase + page * page_bytes + e * 64;
@@ -220,7 +257,11 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   auto stage = [&](int tile, const PfTileRegs &r, auto exact) {   // exact: std::bool_constant -- the product of a key's angle (rope_math.h)
     const int j = tile * kPfKeys + kk;
     bool ok = j < len;                                    // past the end: zeros (the loaded registers are zeros too, see load)
-    if constexpr (kStart) ok = ok && j >= start;          // ... and so is a key in front of the list
+    if constexpr (kSink && kStart)
+      ok = ok && (j < SP * P || j >= start);              // ... and so is a key between the sink pages and the ring part
+    else if constexpr (kStart)
+      ok = ok && j >= start;                              // ... and so is a key in front of the list
+    const int jr = kSink && j >= nsink ? j - shift : j;       // the position the key rotates by
     const float ks = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq & 0xFFFF)) : 0.f;
     const float kz = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.kq >> 16)) : 0.f;
     const float vs = ok ? (float)__builtin_bit_cast(half_t, (unsigned short)(r.vq & 0xFFFF)) : 0.f;
@@ -236,9 +277,9 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
         const float x2 = __builtin_fmaf((float)((r.k2[hw] >> (4 * e)) & 0xF), ks, -kz);
         float s, c;
         if constexpr (decltype(exact)::value)
-          rope_sincos_exact((float)j, rope_fr[16 * u + m], s, c);
+          rope_sincos_exact((float)jr, rope_fr[16 * u + m], s, c);
         else
-          pf_sincos_rev((float)j * rope_fr[16 * u + m], s, c);
+          pf_sincos_rev((float)jr * rope_fr[16 * u + m], s, c);
         klo[hw][e] = (half_t)(x1 * c - x2 * s);
         khi[hw][e] = (half_t)(x2 * c + x1 * s);
       }
@@ -263,12 +304,14 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
   for (int dt = 0; dt < 8; ++dt) O[dt] = v4f{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;                   // row state (m reduced over the row's 4 lanes; l: this lane's keys only)
 
+  const auto tile_of = [&](int i) { return kSink ? (i < sk ? 0 : tl + i - sk) : i; };
   PfTileRegs regs;
-  if (t0 < t1) regs = load(t0);
-  for (int tile = t0; tile < t1; ++tile) {
+  if (t0 < t1) regs = load(tile_of(t0));
+  for (int it = t0; it < t1; ++it) {
+    const int tile = tile_of(it);
     __syncthreads();                                      // the previous tile's LDS reads are done
     if constexpr (kTable) {
-      if (tile * kPfKeys >= kRopeExactFrom)               // (workgroup-uniform) short contexts never take the exact form
+      if ((kSink && tile > 0 ? tile * kPfKeys - shift : tile * kPfKeys) >= kRopeExactFrom)   // (workgroup-uniform) short contexts never take the exact form
         stage(tile, regs, std::true_type{});
       else
         stage(tile, regs, std::false_type{});
@@ -276,11 +319,11 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
       stage(tile, regs, std::false_type{});
     }
     __syncthreads();
-    if (tile + 1 < t1) regs = load(tile + 1);             // in flight during this tile's products
+    if (it + 1 < t1) regs = load(tile_of(it + 1));        // in flight during this tile's products
     const int kt0 = tile * kPfKeys;
     if (!wave_live || kt0 > pmax_w) continue;             // (wave-uniform) no row of this wave sees a key of this tile
     if constexpr (kWindow) {
-      if (kt0 + kPfKeys - 1 < pmin_w - p.window + 1) continue;   // (wave-uniform) ... the tile lies below every row's window
+      if (kt0 + kPfKeys - 1 < pmin_w - p.window + 1 && !(kSink && tile == 0)) continue;   // (wave-uniform) ... the tile lies below every row's window
     }
     // ---- S^T = K . Q^T
     v4f S[4];
@@ -306,7 +349,7 @@ __global__ __launch_bounds__(kPfThreads) void batch_prefill_kernel(PrefillParams
         float s = S[kt][r] * p.qk_scale;
         if (masked && kt0 + 16 * kt + 4 * g + r > pos) s = -INFINITY;
         if constexpr (kWindow) {                          // (lower: wave-uniform) some key of the tile is below some row's window
-          if (lower && kt0 + 16 * kt + 4 * g + r <= pos - p.window) s = -INFINITY;
+          if (lower && kt0 + 16 * kt + 4 * g + r <= pos - p.window && !(kSink && kt0 + 16 * kt + 4 * g + r < nsink)) s = -INFINITY;
         }
         S[kt][r] = s;
         mt = fmaxf(mt, s);
@@ -386,11 +429,13 @@ static int64_t cache_tiles(int P, int max_pages, bool ring) {
   return ring ? (n + kPfKeys - 2) / kPfKeys + 1 : (n + kPfKeys - 1) / kPfKeys;
 }
 
-static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages, int64_t win_tiles = 0, bool ring = false) {
+// sink (the _sink entry points): 1 -- the sink tile that every block stages in front of its window's tiles
+static int prefill_splits(int batch, int N, int max_q_len, int P, int max_pages, int64_t win_tiles = 0, bool ring = false, int sink = 0) {
   if (max_pages <= 0) return 1;
   const int64_t blocks = (int64_t)batch * N * ((max_q_len + kPfRows - 1) / kPfRows);
   int64_t tiles = cache_tiles(P, max_pages, ring);
   if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
+  tiles += sink;
   if (blocks >= 512 || tiles < 8) return 1;
   int64_t s = (512 + blocks - 1) / blocks;
   s = std::min<int64_t>(s, tiles / 4);
@@ -408,10 +453,11 @@ static int gqa_group(int num_qo_heads, int num_kv_heads) {   // G, or 0 for a re
 // Decode: a unit is (sequence, K/V head) -- one workgroup streams the unit's KV range (or one split of it) once for the whole group.
 // Splits: the decode op's cost model (kv_i4.hip decode_splits_total) with units in place of (sequence, head) pairs, 64-key tiles, at
 // least 2 tiles per split and 512 resident workgroups (2 per CU: 140 VGPRs + 32 AGPRs, 2 waves per SIMD).
-static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, int64_t win_tiles = 0, bool ring = false) {
+static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, int64_t win_tiles = 0, bool ring = false, int sink = 0) {
   if (max_pages <= 0) return 1;
   int64_t tiles = cache_tiles(P, max_pages, ring);
   if (win_tiles > 0) tiles = std::min(tiles, win_tiles);
+  tiles += sink;
   const int64_t units = (int64_t)batch * num_kv_heads;
   const int64_t smax = std::max<int64_t>(std::min<int64_t>(tiles / 2, 32), 1);
   int best = 1;
@@ -432,24 +478,26 @@ static int gqa_decode_splits(int batch, int num_kv_heads, int P, int max_pages, 
 // ring (the _ring entry points): max_pages is the ring's size and the list starts off the 64-key grid, see cache_tiles; a ring of
 // ceil((W - 1 + max_add) / P) + 1 pages holds more than any block's keys, so the window bound governs and the plan is the _win
 // call's on a cache that never released a page (max_pages large).
+// sink (the _sink entry points): the _ring plan -- whether the call's list is a ring or starts at 0, so that both sides of a
+// comparison plan alike -- with one more tile for the policies to divide: the sink tile.
 struct PrefillPlan {
   int rows, nqb, splits;
 };
 static PrefillPlan prefill_plan(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
-                                int window = 0, bool ring = false) {
+                                int window = 0, bool ring = false, bool sink = false) {
   PrefillPlan pl;
   pl.rows = decode ? G : (int)std::min<int64_t>(std::min<int64_t>(max_q_len, total_q) * G, 0x7fffffff);
   pl.nqb = (int)(((int64_t)pl.rows + kPfRows - 1) / kPfRows);
   const int64_t win_tiles = window > 0 ? ((int64_t)window + (std::min(pl.rows, kPfRows) - 1) / G + kPfKeys - 2) / kPfKeys + 1 : 0;
-  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages, win_tiles, ring)
-                     : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages, win_tiles, ring);
+  pl.splits = decode ? gqa_decode_splits(batch, num_kv_heads, P, max_pages, win_tiles, ring || sink, sink)
+                     : prefill_splits(batch, num_kv_heads, pl.rows, P, max_pages, win_tiles, ring || sink, sink);
   return pl;
 }
 
 static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_len, int batch, int G, int num_kv_heads, int P, int max_pages,
-                                      int window = 0, bool ring = false) {
+                                      int window = 0, bool ring = false, bool sink = false) {
   if (total_q < 1 || batch < 1 || num_kv_heads < 1 || P < 16 || max_q_len < 1) return 0;
-  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages, window, ring).splits;
+  const int s = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, P, max_pages, window, ring, sink).splits;
   return s > 1 ? partial_state_bytes(total_q * num_kv_heads * G, s) : 0;
 }
 
@@ -458,12 +506,32 @@ static size_t prefill_workspace_bytes(bool decode, int64_t total_q, int max_q_le
 // entries refuse total_q / max_q_len (shape) before they look at alignment; the decode entry has no such arguments.  window: NULL, or
 // the _win entries' argument (checked behind every other fault); those run the kWindow instantiations, the GQA form at every G.
 // ring: the _ring entries -- window is theirs too, kv_start is checked behind it, and the kStart instantiations run.
+// sinks: NULL, or the _sink entries' argument -- window and kv_start are theirs too, but a NULL kv_start is no fault there: it selects
+// the instantiation whose list starts at position 0.  sinks outside 1 .. 64 and a misaligned pos_shift are reported behind the rest.
+#ifdef ATOM_PREFILL_SINK_TU
+// prefill_sink.hip: this file again, for the four kSink instantiations alone -- built without packed FP32 VALU ops, see the Makefile
+void launch_prefill_sink(const PrefillParams &p, unsigned grid, hipStream_t s) {
+  if (p.kv_start) {
+    if (p.rope_table)
+      hipLaunchKernelGGL((batch_prefill_kernel<true, true, true, true, true>), dim3(grid), dim3(kPfThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_prefill_kernel<true, false, true, true, true>), dim3(grid), dim3(kPfThreads), 0, s, p);
+  } else {
+    if (p.rope_table)
+      hipLaunchKernelGGL((batch_prefill_kernel<true, true, true, false, true>), dim3(grid), dim3(kPfThreads), 0, s, p);
+    else
+      hipLaunchKernelGGL((batch_prefill_kernel<true, false, true, false, true>), dim3(grid), dim3(kPfThreads), 0, s, p);
+  }
+}
+#else
+void launch_prefill_sink(const PrefillParams &p, unsigned grid, hipStream_t s);
+
 static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
                           const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
                           int batch, int num_layers, int layer_idx, int G, int num_kv_heads, int page_size, int head_dim, float rope_theta,
                           float rope_scale, const float *rope_table, float attn_scale, int max_pages, void *workspace,
                           size_t workspace_bytes, void *stream, const int *window = nullptr, bool ring = false,
-                          const int32_t *kv_start = nullptr) {
+                          const int32_t *kv_start = nullptr, const int *sinks = nullptr, const int32_t *pos_shift = nullptr) {
   const int st = check_kv(kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers, layer_idx, num_kv_heads,
                           page_size, head_dim);
   if (st != ATOM_OK) return st;
@@ -471,7 +539,7 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   if (!decode && (total_q < 1 || total_q > 0x7fffffff || max_q_len < 1)) return ATOM_ERR_SHAPE;
   if ((o && !aligned16(o)) || !aligned16(q) || (reinterpret_cast<uintptr_t>(qo_indptr) & 3u)) return ATOM_ERR_ALIGN;
   PrefillPlan pl = prefill_plan(decode, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages, window ? std::max(*window, 0) : 0,
-                                ring);
+                                ring, sinks != nullptr);
   const int num_qo_heads = num_kv_heads * G;
   const int64_t rows_heads = total_q * num_qo_heads;
   if (pl.splits > 1 && !workspace_holds(workspace, workspace_bytes, rows_heads, pl.splits)) pl.splits = 1;
@@ -480,8 +548,10 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   if (grid > 0x7fffffff || rows_heads > 0x7fffffff) return ATOM_ERR_SHAPE;
   if (const int rs = check_rope_table(rope_table, attn_scale)) return rs;   // (the _rope entries' own faults: behind every older one)
   if (window && *window < 1) return ATOM_ERR_INVALID_ARG;                    // (the _win entries' own fault: behind those)
-  if (ring && !kv_start) return ATOM_ERR_INVALID_ARG;                        // (the _ring entries' own faults: behind that)
+  if (ring && !kv_start && !sinks) return ATOM_ERR_INVALID_ARG;             // (the _ring entries' own faults: behind that)
   if (ring && (reinterpret_cast<uintptr_t>(kv_start) & 3u)) return ATOM_ERR_ALIGN;
+  if (sinks && (*sinks < 1 || *sinks > kPfKeys)) return ATOM_ERR_INVALID_ARG;   // (the _sink entries' own faults: behind those)
+  if (sinks && (reinterpret_cast<uintptr_t>(pos_shift) & 3u)) return ATOM_ERR_ALIGN;
   PrefillParams p;                                        // by name: the fields' order is the kernel's business
   p.data = (const uint8_t *)kv_data, p.param = (const half_t *)kv_param;
   p.kv_indptr = kv_indptr, p.kv_indices = kv_indices, p.last_page_offset = last_page_offset, p.qo_indptr = qo_indptr;
@@ -493,8 +563,11 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   p.rope_table = rope_table;
   p.window = window ? *window : 0;                        // (only the kWindow instantiations read it)
   p.kv_start = kv_start;                                  // (only the kStart instantiations read it)
+  p.sinks = sinks ? *sinks : 0, p.pos_shift = pos_shift;  // (only the kSink instantiations read them)
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (ring) {                                             // (always with a window)
+  if (sinks) {                                            // (always with a window; on a ring where kv_start is given)
+    launch_prefill_sink(p, (unsigned)grid, s);
+  } else if (ring) {                                             // (always with a window)
     if (rope_table)
       hipLaunchKernelGGL((batch_prefill_kernel<true, true, true, true>), dim3((unsigned)grid), dim3(kPfThreads), 0, s, p);
     else
@@ -517,8 +590,11 @@ static int launch_prefill(bool decode, void *o, const void *q, const int32_t *qo
   return check_launch();
 }
 
+#endif  // ATOM_PREFILL_SINK_TU
+
 }  // namespace atom
 
+#ifndef ATOM_PREFILL_SINK_TU
 using namespace atom;
 
 extern "C" {
@@ -705,4 +781,53 @@ int atom_batch_prefill_gqa_i4_ring(void *o, const void *q, const int32_t *qo_ind
                         max_pages_per_seq, workspace, workspace_bytes, stream, &window, true, kv_start);
 }
 
+// ---- attention sinks: the _ring entries with `sinks, pos_shift` behind kv_start (include/atom_hip.h); kv_start NULL: a list from 0
+
+size_t atom_batch_decode_gqa_i4_sink_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                     int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1 ? prefill_workspace_bytes(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true, true)
+                          : 0;
+}
+
+int atom_batch_decode_gqa_i4_sink_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0 || batch < 1 || page_size < 16 || window < 1) return 0;
+  return prefill_plan(true, batch, 1, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true, true).splits;
+}
+
+size_t atom_batch_prefill_gqa_i4_sink_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                      int max_q_len, int max_pages_per_seq, int window) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  return G && window >= 1
+             ? prefill_workspace_bytes(false, total_q, max_q_len, batch, G, num_kv_heads, page_size, max_pages_per_seq, window, true, true)
+             : 0;
+}
+
+int atom_batch_decode_gqa_i4_sink(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int sinks,
+                                  const int32_t *pos_shift, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(true, o, q, nullptr, batch, 1, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch, num_layers,
+                        layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale, max_pages_per_seq,
+                        workspace, workspace_bytes, stream, &window, true, kv_start, &sinks, pos_shift);
+}
+
+int atom_batch_prefill_gqa_i4_sink(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int sinks,
+                                   const int32_t *pos_shift, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream) {
+  const int G = gqa_group(num_qo_heads, num_kv_heads);
+  if (G == 0) return ATOM_ERR_SHAPE;
+  return launch_prefill(false, o, q, qo_indptr, total_q, max_q_len, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, batch,
+                        num_layers, layer_idx, G, num_kv_heads, page_size, head_dim, rope_theta, rope_scale, rope_table, attn_scale,
+                        max_pages_per_seq, workspace, workspace_bytes, stream, &window, true, kv_start, &sinks, pos_shift);
+}
+
 }  // extern "C"
+#endif  // ATOM_PREFILL_SINK_TU

@@ -535,16 +535,25 @@ _UNPENALISED = "penalties unless it is SpeculativeParams(penalised=True)"     # 
 _REFUSES = (("guide", ("num_beams", _UNGUIDED)),
             ("speculative", ("num_beams", "logprobs", "return_logits", "caches", _UNPENALISED)),
             ("num_beams", ("sampling", "logprobs", "return_logits", "caches")),
-            ("rolling_kv", ("caches", "num_beams", "speculative")))
+            ("rolling_kv", ("caches", "num_beams", "speculative")),
+            ("streaming", ("caches", "num_beams", "speculative", "rolling_kv")))
+
+
+@dataclasses.dataclass(frozen=True)
+class StreamingParams:
+    """``generate(streaming=)``: StreamingLLM decoding (Xiao et al., attention sinks) -- every layer sees the first ``sinks`` tokens
+    (1 .. 64) and the most recent ``window`` (>= 1, the query's own included), with RoPE positions counted inside that cache."""
+    sinks: int = 4
+    window: int = 1024
 
 
 def _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide,
-                       rolling_kv=False):
+                       rolling_kv=False, streaming=None):
     """Raises ``ValueError`` for the first entry of ``_REFUSES`` that applies (and for a drafter or statistics without ``speculative``)."""
     named = {"guide": guide is not None, "speculative": speculative is not None, "num_beams": num_beams is not None,
              "sampling": sampling is not None, "logprobs": logprobs is not None, "return_logits": bool(return_logits),
              "caches": caches is not None, _UNGUIDED: speculative is not None and not speculative.guided,
-             "rolling_kv": bool(rolling_kv)}
+             "rolling_kv": bool(rolling_kv), "streaming": streaming is not None}
     named = {name: [name] * given for name, given in named.items()}          # what a message lists for each name: itself, if given
     used, neutral = named.setdefault("penalties", []), SamplingParams()
     for q in ([] if sampling is None else _params_list(sampling)):
@@ -594,7 +603,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
              caches: Sequence[KvCacheInt4] = None, return_logits: bool = False,
              sampling: Union[SamplingParams, Sequence[SamplingParams]] = None, logprobs: int = None, num_beams: int = None,
              speculative: SpeculativeParams = None, drafter=None, return_spec_stats: bool = False,
-             guide: Union[TokenAutomaton, Sequence[TokenAutomaton]] = None, rolling_kv: bool = False):
+             guide: Union[TokenAutomaton, Sequence[TokenAutomaton]] = None, rolling_kv: bool = False,
+             streaming: StreamingParams = None):
     """Generation for a batch of prompts (lists of token ids): returns one list of new tokens per prompt, cut after its first
     ``eos_token_id``.  Greedy by default; ``sampling`` -- one ``SamplingParams`` or one per prompt -- draws every token with
     ops.sample instead, on the device: new token i of prompt b is draw number i of its seed, so a prompt's tokens do not depend
@@ -649,9 +659,33 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     to the pool before the first replayed step.  Same tokens and logits as the default wherever both caches give the attention op the
     same KV split.  Combines with ``sampling``, the penalties, ``logprobs``, ``return_logits`` and ``guide``; refused with
     ``ValueError``: ``caches`` (a cache without its head is no ``KvCacheInt4``), ``num_beams`` and ``speculative``.
-    ``rolling_kv=False`` is the code above, launch for launch."""
-    _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide, rolling_kv)
-    window = _rolling_window(model) if rolling_kv else None
+    ``rolling_kv=False`` is the code above, launch for launch.
+    ``streaming=StreamingParams(sinks=S, window=W)`` (a model WITHOUT a trained window): generation without bound on
+    ``ceil(S / page) + ceil(W / page) + 1`` pages per sequence.  ``model.set_streaming(S, W)`` for the duration of the call (restored on
+    exit, on an exception too); the prompt is prefilled into ordinary pages under the sink mask with shift 0, then moved onto a
+    ``RollingKvCacheInt4(sinks=S)`` -- the pages wholly between the sinks and the window go back to the pool -- and every further token is
+    the replayed step with ops.kv_step_sink_i4 in place of the plain step.  The tokens are those of an eager loop over a cache that
+    releases nothing, called with the same ``sinks``, ``window`` and shift.  Combines and refuses as ``rolling_kv`` does, and refuses
+    ``rolling_kv`` itself.  ``streaming=None`` is the code above, launch for launch."""
+    _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide, rolling_kv,
+                       streaming)
+    args = (model, prompts, max_new_tokens, pool, eos_token_id, caches, return_logits, sampling, logprobs, num_beams, speculative, drafter,
+            return_spec_stats, guide)
+    if streaming is None:
+        return _generate(*args, (_rolling_window(model), 0) if rolling_kv else None)
+    if not hasattr(model, "set_streaming"):
+        raise NotImplementedError(f"generate: streaming is not built for {type(model).__name__}")
+    before = model.streaming
+    model.set_streaming(int(streaming.sinks), int(streaming.window))
+    try:
+        return _generate(*args, (int(streaming.window), int(streaming.sinks)))
+    finally:
+        model.set_streaming(*(before or (None,)))
+
+
+def _generate(model, prompts, max_new_tokens, pool, eos_token_id, caches, return_logits, sampling, logprobs, num_beams, speculative,
+              drafter, return_spec_stats, guide, ring):
+    """``generate`` behind its checks.  ``ring``: None, or (window, sinks) of the ``RollingKvCacheInt4`` the decode loop runs over."""
     if num_beams is not None:
         return [hyps[0].tokens for hyps in beam_search(model, prompts, max_new_tokens, pool, num_beams, eos_token_id=eos_token_id)]
     n_lp = _check_logprobs(logprobs)
@@ -688,7 +722,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
                 static.close()
         new = None
     elif max_new_tokens > 1:
-        static = RollingKvCacheInt4(seqs, window) if rolling_kv else StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
+        static = RollingKvCacheInt4(seqs, ring[0], sinks=ring[1]) if ring else StaticBatchedKvCacheInt4(seqs, reserve=max_new_tokens - 1)
         try:
             dg = DecodeGraph(model, static, max_new_tokens - 1, keep_logits=return_logits, sampler=sampler, logprobs=n_lp,
                              penalties=penalties, guide=guides)

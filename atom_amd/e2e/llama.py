@@ -309,6 +309,7 @@ class LlamaAttention(nn.Module):
         self.window = self._config_window(config, layer_idx)
         if self.window is not None and self.head_dim != 128:
             raise NotImplementedError(f"sliding-window attention is built for head_dim 128, got {self.head_dim}")
+        self.sinks = None                                        # attention sinks: LlamaForCausalLM.set_streaming
 
     @staticmethod
     def _config_window(config, layer_idx):
@@ -333,9 +334,21 @@ class LlamaAttention(nn.Module):
             kw["rope_scale"] = self.rope_scale
         if self.rope_table is not None or self.attn_scale != 1.0:
             kw.update(rope_table=self.rope_table, attn_scale=self.attn_scale)
-        if self.window is not None:
-            kw["window"] = self.window
+        kw.update(self.window_kw)
         return kw
+
+    @property
+    def window_kw(self) -> dict:
+        """the window (and, under ``set_streaming``, the sinks) of this layer: what ``ops.decode_splits`` takes of ``rope_kw``"""
+        kw = {} if self.window is None else {"window": self.window}
+        if self.sinks is not None:
+            kw["sinks"] = self.sinks
+        return kw
+
+    def set_streaming(self, sinks, window):
+        """``LlamaForCausalLM.set_streaming`` for this layer (the checks are made there); ``None, None`` restores the config's window"""
+        self.sinks = sinks
+        self.window = window if sinks is not None else self._config_window(self.config, self.layer_idx)
 
     def _rope_eager(self, x, pos):
         """RoPE of the eager torch prefill path, with the frequencies the ops use"""
@@ -513,7 +526,7 @@ class LlamaDecoderLayer(nn.Module):
         else:
             outlier, norms, outlier_scales, norm_scales = il(hidden_states)
             q, k32, v32 = ops.dense_layer_gemm_i4_multi(norms, norm_scales, outlier, outlier_scales, at._decode_qkv(), f32_mask=0b110)
-        splits = ops.decode_splits(rows, decode_kv, at.num_heads, **({} if at.window is None else {"window": at.window})) \
+        splits = ops.decode_splits(rows, decode_kv, at.num_heads, **at.window_kw) \
             if (mask & 2) and self.fusion.merge_in_o_proj else 1
         if splits >= 2 and ops.merge_q_gemm_fits(rows, hs, 1, hs, splits):
             # the KV-split merge in front of o_proj's quantiser, inside o_proj's launch (round 6): same bits, a launch fewer
@@ -623,6 +636,32 @@ class LlamaForCausalLM(nn.Module):
         self.config = config
         self.model = self.model_class(config)
         self.lm_head = nn.Linear(config.hidden_size, config.vocab_size, bias=False, dtype=torch.float16)
+
+    streaming = None                                             # (sinks, window) under set_streaming
+
+    def set_streaming(self, sinks, window=None):
+        """StreamingLLM (attention sinks) for a model WITHOUT a trained sliding window: every attention layer keeps
+        the first ``sinks`` keys (1 .. 64) visible besides the most recent ``window`` (>= 1, the query's own included), and positions
+        are those inside that cache -- ``window`` and ``sinks`` travel in every layer's ``rope_kw``, the shift comes from the cache
+        (``pos_shift``: a ``RollingKvCacheInt4(sinks=...)`` writes it).  A streaming layer attends through the ops in prefill and in
+        decode, as a windowed layer does.  ``set_streaming(None)`` clears.  ``ValueError`` on a model whose layers carry a trained window
+        (that model uses ``generate(rolling_kv=True)``); ``NotImplementedError`` at head size 64 and on the Mixtral and LoRA classes."""
+        if type(self) is not LlamaForCausalLM:
+            raise NotImplementedError(f"attention sinks are not built for {type(self).__name__}")
+        if sinks is not None:
+            for name, v, hi in (("sinks", sinks, 64), ("window", window, None)):
+                if isinstance(v, bool) or not isinstance(v, int) or v < 1 or (hi is not None and v > hi):
+                    raise ValueError(f"set_streaming: {name} must be an int >= 1" + (f" and <= {hi}" if hi else "") + f", got {v!r}")
+        layers = [layer.self_attn for layer in self.model.layers]
+        for at in layers:                                        # every refusal before any layer changes
+            if sinks is not None and at._config_window(at.config, at.layer_idx) is not None:
+                raise ValueError(f"set_streaming: layer {at.layer_idx} carries a trained sliding window: attention sinks are for models "
+                                 f"without one (use generate(rolling_kv=True))")
+            if sinks is not None and at.head_dim != 128:
+                raise NotImplementedError(f"attention sinks are built for head_dim 128, got {at.head_dim}")
+        for at in layers:
+            at.set_streaming(sinks, window if sinks is not None else None)
+        self.streaming = None if sinks is None else (sinks, window)
 
     @torch.no_grad()
     def forward(self, input_ids, blen: BatchLenInfo, prefill_kv, decode_kv):

@@ -696,6 +696,55 @@ def kv_step_ring_i4(kv, add: int = 1):
     L.check(st, "atom_kv_step_ring_i4")
 
 
+def kv_step_sink_i4(kv, add: int = 1):
+    """NEW (attention sinks): ``kv_step_ring_i4`` for a utils.RollingKvCacheInt4 built with ``sinks=S`` -- the first ceil(S / page) slots
+    of a row hold the sequence's first pages for good, the rest is the ring (atom_kv_step_sink_i4).  The tables list the sink pages,
+    then the live ring pages; ``kv.kv_start`` receives the position of the first ring page and ``kv.pos_shift`` the keys evicted between
+    the sinks and the window of the step's first row (what the attention ops' ``sinks=`` calls read).  One launch, capturable."""
+    tensors, batch, cap = _kv_step_tables(kv)
+    for t in (kv.kv_start, kv.pos_shift):
+        if not t.is_cuda:
+            raise L.AtomHipError("KV-cache page tables must live on the GPU: no CPU fallback")
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == batch
+    st = L.lib().atom_kv_step_sink_i4(*(t.data_ptr() for t in tensors), batch, cap, kv.page_size, int(add), int(kv.window), int(kv.sinks),
+                                       kv.kv_start.data_ptr(), kv.pos_shift.data_ptr(), L.current_stream(kv.page_table.device))
+    L.check(st, "atom_kv_step_sink_i4")
+
+
+def _sink_args(kv, window, sinks, pos_shift, batch):
+    """``sinks=`` / ``pos_shift=`` of the attention ops, checked: None where ``sinks`` is None (a cache that pins sink pages then refuses
+    the call), else (kv_start tensor or None, S, pos_shift tensor or None).  ``pos_shift=None`` takes the cache's own ``pos_shift``
+    attribute where it has one (a rolling cache; any cache object a caller has given one), else no shift.  A rolling cache computed its
+    shifts for its OWN window, so a call that leaves ``pos_shift`` to it must name that window; a narrower one brings its own shifts."""
+    pinned = int(getattr(kv, "sinks", 0) or 0)
+    if sinks is None:
+        if pinned:
+            raise ValueError(f"a rolling cache with {pinned} sink tokens serves only calls with sinks={pinned}")
+        if pos_shift is not None:
+            raise ValueError("pos_shift needs sinks")
+        return None
+    if isinstance(sinks, bool) or not isinstance(sinks, int) or not 1 <= sinks <= 64:
+        raise ValueError(f"sinks must be None or an int in 1 .. 64, got {sinks!r}")
+    if window is None:
+        raise ValueError("sinks needs window (the sinks are the keys a window would drop)")
+    if _kv_dims(kv)[3] == 64:
+        _refuse_d64(kv, "sinks=")
+    start = getattr(kv, "kv_start", None)
+    if start is not None and (sinks != pinned or window > kv.window):
+        raise ValueError(f"a rolling cache with {pinned} sink tokens and window {kv.window} does not serve sinks={sinks}, window={window}: "
+                         f"the pages between are released")
+    if start is not None and pos_shift is None and window != kv.window:
+        raise ValueError(f"window={window} on a rolling cache of window {kv.window} needs pos_shift=: the cache's shifts are those of its own "
+                         f"window")
+    shift = getattr(kv, "pos_shift", None) if pos_shift is None else pos_shift
+    for t in (start, shift):
+        if t is not None:
+            _require_cuda(t)
+            if not (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == batch):
+                raise TypeError(f"kv_start / pos_shift must be contiguous int32 tensors of [{batch}], got {t.dtype} {tuple(t.shape)}")
+    return start, sinks, shift
+
+
 def _ring_start(kv, window):
     """``kv.kv_start`` of a rolling cache (utils.RollingKvCacheInt4) for a call with ``window`` -- the call then takes the _ring entry
     points --, None for every other cache.  A rolling cache has released the pages behind ITS window: an un-windowed call, or one with
@@ -725,13 +774,17 @@ def _window_arg(window):
     return window
 
 
-def decode_splits(batch: int, kv, num_qo_heads: int = None, window: int = None) -> int:
+def decode_splits(batch: int, kv, num_qo_heads: int = None, window: int = None, sinks: int = None) -> int:
     """How many partial states per (sequence, head) batch_decode_i4 produces for this cache (1: none; small batches: one per workgroup of
     four KV-split waves).  ``num_qo_heads``: the query heads of a grouped-query call (default: the cache's head count).  ``window``:
     of the sliding-window call (atom_batch_decode_gqa_i4_win_splits, the grouped-query plan at every head ratio; on a rolling cache
-    atom_batch_decode_gqa_i4_ring_splits, and a call without a window or with one wider than the cache's is a ``ValueError``)."""
+    atom_batch_decode_gqa_i4_ring_splits, and a call without a window or with one wider than the cache's is a ``ValueError``).
+    ``sinks``: of the attention-sink call (atom_batch_decode_gqa_i4_sink_splits)."""
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     max_pages = int(getattr(kv, "max_pages", 0))
+    if _sink_args(kv, _window_arg(window), sinks, None, int(batch)) is not None:
+        nq = num_heads if num_qo_heads is None else _qo_heads(int(num_qo_heads), num_heads)
+        return int(L.lib().atom_batch_decode_gqa_i4_sink_splits(int(batch), nq, num_heads, page_size, max_pages, window))
     if head_dim == 64:                                       # one plan at every head ratio (atom_batch_decode_gqa_i4_d64_splits)
         if _window_arg(window) is not None:
             _refuse_d64(kv, "window=")
@@ -790,7 +843,8 @@ def _rope_args(rope_table, attn_scale, device, pairs=64):
 
 
 def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0, append_kv=None, merge=True,
-                    rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None):
+                    rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None, sinks: int = None,
+                    pos_shift: torch.Tensor = None):
     """Decode attention over the INT4 paged cache, RoPE fused.  Reference: punica/ops/__init__.py:21-30 ->
     FlashInferBatchDecodeKernel_i4 (rope_theta 1e4, rope_scale 1 hard-coded there).  q fp16 [batch, heads, 128].
     ``append_kv=(k_f32, v_f32)`` (round 6): quant_append_kv_i4 of this step's FP32 k / v projections inside the same launch
@@ -812,7 +866,13 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     arguments and ``kv.kv_start``: the same positions, masks and angles, read from a page list that starts at ``kv_start[b]``.
     ``window=None`` or a window wider than the cache's is a ``ValueError`` there.  Every other cache makes exactly the calls above.
     A cache of 64-wide heads (``kv.data`` [.., 32]; q [batch, heads, 64]) takes atom_batch_decode_gqa_i4_d64 at every head ratio:
-    ``rope_table`` is then float32 [32]; ``window=``, ``append_kv=``, ``merge=False`` and a rolling cache raise ``NotImplementedError``."""
+    ``rope_table`` is then float32 [32]; ``window=``, ``append_kv=``, ``merge=False`` and a rolling cache raise ``NotImplementedError``.
+    ``sinks`` (attention sinks, StreamingLLM; needs ``window``, else ``ValueError``): an int S in 1 .. 64 -- the query at position p sees
+    key j iff j <= p and (j < S or j > p - W).  ``pos_shift`` int32 [batch] on the device (None: the cache's ``pos_shift`` attribute where
+    it has one, else 0): the query rotates by p - shift, a key j >= S by j - shift, a key j < S by j; every other quantity stays
+    absolute.  atom_batch_decode_gqa_i4_sink runs -- on a rolling cache built with ``sinks=S`` over its sink pages and its ring, on any
+    other cache over a page list from position 0; ``merge=False`` takes its splits from ``decode_splits(..., window=W, sinks=S)``;
+    ``append_kv`` is refused.  ``sinks=None``: exactly the calls above; head size 64 raises ``NotImplementedError``."""
     _require_cuda_half(q, "q")
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
     batch = q.size(0)
@@ -821,7 +881,7 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
     assert q.shape == (batch, nq, head_dim)
     if head_dim == 64:
         # head size 64: atom_batch_decode_gqa_i4_d64 at every head ratio -- the prefill op's kernel with one query per sequence
-        for arg, name in ((window, "window="), (append_kv, "append_kv="), (None if merge else False, "merge=False"),
+        for arg, name in ((window, "window="), (sinks, "sinks="), (append_kv, "append_kv="), (None if merge else False, "merge=False"),
                           (getattr(kv, "kv_start", None), "a rolling cache")):
             if arg is not None:
                 _refuse_d64(kv, name)
@@ -837,6 +897,24 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
                                               max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
         L.check(st, "atom_batch_decode_gqa_i4_d64")
         return o
+    sink = _sink_args(kv, _window_arg(window), sinks, pos_shift, batch)
+    if sink is not None:
+        if append_kv is not None:
+            raise ValueError("append_kv= is not built for sliding-window attention (the fused append lives in the FP32 decode kernel): "
+                             "append with quant_append_kv_i4 first")
+        _require_cuda(kv.data, kv.param)
+        assert batch == kv.last_page_offset.numel()
+        ptrs, dims, max_pages = _kv_args(kv, layer_idx, nq)
+        lib = L.lib()
+        plan = (batch, nq, num_heads, page_size, max_pages, window)
+        ws_bytes = lib.atom_batch_decode_gqa_i4_sink_workspace_bytes(*plan)
+        o, ws, ret = _decode_outputs(q, merge, ws_bytes, None if merge else lib.atom_batch_decode_gqa_i4_sink_splits(*plan))
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_decode_gqa_i4_sink(L.ptr(o), q.data_ptr(), *ptrs, *dims, float(rope_theta), float(rope_scale), table, scale, window,
+                                               L.ptr(sink[0]), sink[1], L.ptr(sink[2]), max_pages, L.ptr(ws), ws_bytes,
+                                               L.current_stream(q.device))
+        L.check(st, "atom_batch_decode_gqa_i4_sink")
+        return ret
     start = _ring_start(kv, _window_arg(window))
     if start is not None:
         if append_kv is not None:
@@ -896,7 +974,8 @@ def batch_decode_i4(q: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 
 
 
 def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: int, *, rope_theta: float = 1e4, rope_scale: float = 1.0,
-                     max_q_len: int = None, rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None):
+                     max_q_len: int = None, rope_table: torch.Tensor = None, attn_scale: float = 1.0, window: int = None,
+                     sinks: int = None, pos_shift: torch.Tensor = None):
     """Prefill / chunked-prefill attention over the INT4 paged cache, causal, RoPE fused (atom_batch_prefill_i4).  q fp16
     [T, heads, 128] (not yet rotated); qo_indptr int32 [batch + 1] on the device: sequence b's queries are rows
     qo_indptr[b] .. qo_indptr[b+1] and its LAST positions in the cache (already written there, init_kv_i4).  ``max_q_len``: host-side
@@ -908,7 +987,8 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     without them).
     ``window``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_win) -- the bound of every query row from that row's own
     position; None: exactly the calls above.  A rolling cache takes atom_batch_prefill_gqa_i4_ring, as in ``batch_decode_i4``; a
-    chunk there is at most the cache's ``max_add`` tokens (what ``kv.step(add)`` admits)."""
+    chunk there is at most the cache's ``max_add`` tokens (what ``kv.step(add)`` admits).
+    ``sinks`` / ``pos_shift``: as in ``batch_decode_i4`` (atom_batch_prefill_gqa_i4_sink); all rows of a sequence share its shift."""
     _require_cuda_half(q, "q")
     _require_cuda(qo_indptr, kv.data, kv.param)
     num_layers, num_heads, page_size, head_dim = _kv_dims(kv)
@@ -922,7 +1002,7 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
     max_q = total if max_q_len is None else int(max_q_len)
     lib = L.lib()
     if head_dim == 64:                                      # head size 64: atom_batch_prefill_gqa_i4_d64
-        for arg, name in ((window, "window="), (getattr(kv, "kv_start", None), "a rolling cache")):
+        for arg, name in ((window, "window="), (sinks, "sinks="), (getattr(kv, "kv_start", None), "a rolling cache")):
             if arg is not None:
                 _refuse_d64(kv, name)
         ws_bytes = lib.atom_batch_prefill_gqa_i4_d64_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages)
@@ -932,6 +1012,17 @@ def batch_prefill_i4(q: torch.Tensor, qo_indptr: torch.Tensor, kv, layer_idx: in
         st = lib.atom_batch_prefill_gqa_i4_d64(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
                                                float(rope_scale), table, scale, max_pages, L.ptr(ws), ws_bytes, L.current_stream(q.device))
         L.check(st, "atom_batch_prefill_gqa_i4_d64")
+        return o
+    sink = _sink_args(kv, _window_arg(window), sinks, pos_shift, batch)
+    if sink is not None:
+        ws_bytes = lib.atom_batch_prefill_gqa_i4_sink_workspace_bytes(total, batch, nq, num_heads, page_size, max_q, max_pages, window)
+        ws = _workspace(q.device, ws_bytes) if ws_bytes else None
+        o = torch.empty_like(q)
+        table, scale = _rope_args(rope_table, attn_scale, q.device) or (None, 1.0)
+        st = lib.atom_batch_prefill_gqa_i4_sink(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), total, max_q, *ptrs, *dims, float(rope_theta),
+                                                float(rope_scale), table, scale, window, L.ptr(sink[0]), sink[1], L.ptr(sink[2]), max_pages,
+                                                L.ptr(ws), ws_bytes, L.current_stream(q.device))
+        L.check(st, "atom_batch_prefill_gqa_i4_sink")
         return o
     start = _ring_start(kv, _window_arg(window))
     if start is not None:

@@ -206,11 +206,16 @@ class RollingKvCacheInt4:
     window of the current length to the pool, takes fresh ones up to ``R`` per sequence (``RuntimeError`` before anything changes if
     the pool cannot give them), and lays each row out so that logical page g sits in slot g % R.  From then on the sequences' page
     lists are the rings, which no ``KvCacheInt4`` method understands: use the sequences again only after ``close()``.
-    ``max_add``: the most tokens one ``step`` may add (1: decode steps; q for chunks of q tokens); ``max_pages = R``."""
+    ``max_add``: the most tokens one ``step`` may add (1: decode steps; q for chunks of q tokens); ``max_pages = R``.
+    ``sinks=S`` (1 .. 64; attention sinks): the sequence's first ``SP = ceil(S / page_size)`` pages are kept for good in
+    slots 0 .. SP - 1 of its row, logical page g >= SP lives in slot ``SP + (g - SP) % R``, and only the pages wholly between the sinks
+    and the window go back to the pool: ``max_pages = SP + R``.  ``step`` is then ops.kv_step_sink_i4, which also writes ``pos_shift``
+    (int32 [batch]: what the attention ops' ``sinks=`` calls lower the RoPE positions by), and the ops refuse calls whose ``sinks``
+    differs from the cache's."""
 
     device_lengths = True      # the lengths live on the device: ``seqlens`` is stale between sync_host() calls (read by LlamaAttention)
 
-    def __init__(self, kv: Sequence[KvCacheInt4], window: int, max_add: int = 1):
+    def __init__(self, kv: Sequence[KvCacheInt4], window: int, max_add: int = 1, sinks: int = 0):
         assert len(kv) > 0
         pool = kv[0].pool
         assert all(c.pool is pool for c in kv)
@@ -219,21 +224,27 @@ class RollingKvCacheInt4:
             raise ValueError(f"window and max_add must be integers >= 1, got {window!r} and {max_add!r}")
         P, device = pool.block_len, pool.buf.device
         assert all(len(c.indicies) == -(-c.seqlen // P) for c in kv), "the sequences must hold no spare pages"
-        self.window, self.max_add = int(window), int(max_add)
+        if isinstance(sinks, bool) or int(sinks) != sinks or not 0 <= sinks <= 64:
+            raise ValueError(f"sinks must be an integer in 0 .. 64, got {sinks!r}")
+        self.window, self.max_add, self.sinks = int(window), int(max_add), int(sinks)
         R = -(-(self.window - 1 + self.max_add) // P) + 1
-        first = [max(0, c.seqlen - self.window) // P for c in kv]           # the first page a step to the current length lists
-        need = sum(R - (len(c.indicies) - f) for c, f in zip(kv, first))
-        if need > pool.num_free_blocks + sum(first):
-            raise RuntimeError(f"RollingKvCacheInt4: {need} more pages needed ({len(kv)} rings of {R}), {pool.num_free_blocks} free in "
-                               f"the pool and {sum(first)} behind the window")
+        SP = -(-self.sinks // P)                                            # pinned pages in front of the ring (0: the plain ring)
+        first = [max(SP, max(0, c.seqlen - self.window) // P) for c in kv]  # the first ring page a step to the current length lists
+        gone = [max(0, min(f, len(c.indicies)) - SP) for c, f in zip(kv, first)]          # pages wholly between the sinks and the window
+        need = sum(SP + R - (len(c.indicies) - g) for c, g in zip(kv, gone))
+        if need > pool.num_free_blocks + sum(gone):
+            raise RuntimeError(f"RollingKvCacheInt4: {need} more pages needed ({len(kv)} rings of {SP + R}), {pool.num_free_blocks} free "
+                               f"in the pool and {sum(gone)} behind the window")
         for c, f in zip(kv, first):                                         # every sequence first: the pool may need these pages back
-            for idx in c.indicies[:f]:
+            for idx in c.indicies[SP:f]:
                 pool.free_block(idx)
         rows = []
         for c, f in zip(kv, first):
-            live = {g % R: idx for g, idx in enumerate(c.indicies[f:], start=f)}
-            rows.append([live[s] if s in live else pool.alloc_block() for s in range(R)])
+            live = {g: idx for g, idx in enumerate(c.indicies[:SP])}
+            live.update({SP + (g - SP) % R: idx for g, idx in enumerate(c.indicies[f:], start=f)})
+            rows.append([live[s] if s in live else pool.alloc_block() for s in range(SP + R)])
             c._indicies[:] = rows[-1]                                       # what close() releases
+        R += SP
         self._kv = list(kv)
         batch = len(kv)
         self.data = pool.buf
@@ -249,6 +260,8 @@ class RollingKvCacheInt4:
         self.indicies = torch.zeros(batch * R, dtype=torch.int32, device=device)
         self.last_page_offset = torch.zeros(batch, dtype=torch.int32, device=device)
         self.kv_start = torch.zeros(batch, dtype=torch.int32, device=device)
+        if self.sinks:
+            self.pos_shift = torch.zeros(batch, dtype=torch.int32, device=device)
         self.step(0)
 
     @property
@@ -261,7 +274,7 @@ class RollingKvCacheInt4:
         if int(add) > self.max_add:
             raise ValueError(f"RollingKvCacheInt4: a step of {add} tokens on rings sized for max_add={self.max_add}")
         from .. import ops
-        ops.kv_step_ring_i4(self, add)
+        (ops.kv_step_sink_i4 if self.sinks else ops.kv_step_ring_i4)(self, add)
 
     def sync_host(self):
         """Read the lengths and the status word back (one copy, the only synchronisation) and bring ``seqlens`` and the sequences'

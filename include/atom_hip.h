@@ -591,6 +591,47 @@ int atom_batch_prefill_gqa_i4_ring(void *o, const void *q, const int32_t *qo_ind
                                    const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int max_pages_per_seq,
                                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* ATTENTION SINKS (StreamingLLM): the _ring entry points with `int sinks, const int32_t *pos_shift` inserted behind
+ * kv_start.  sinks = S, 1 <= S <= 64; window = W >= 1 counts the most recent keys, the query's own included; per sequence b the call
+ * takes a shift, shift_b = pos_shift[b] >= 0 (int32 [batch] on the device; NULL: 0 for every sequence).
+ *   - MASK: the query row at absolute position p sees key j iff j <= p and (j < S or j > p - W), the bound from each row's own position.
+ *   - ROPE: the query at p rotates by p - shift_b; a key j < S rotates by j; a key j >= S rotates by j - shift_b.
+ *   - shift_b is an INPUT: the kernel knows no policy.  atom_kv_step_sink_i4 writes shift_b = max(0, p0 - W + 1 - S), p0 the position of
+ *     the sequence's first query row of the step -- the number of keys evicted between the sinks and p0's window, so that the oldest
+ *     visible non-sink key rotates by a position >= S and a one-token step's query by S + W - 1 once anything has been evicted.  All
+ *     rows of a call share their sequence's shift: that is the definition for a step of several rows.
+ *   - Every other quantity stays ABSOLUTE: the length, the positions of the queries, the 64-key tile grid, both masks.
+ *   - kv_start == NULL: the page list starts at position 0 (a prompt prefilled into ordinary pages, shift 0).  Otherwise the list is
+ *     the sequence's SP = ceil(S / page_size) sink pages followed by the ring pages in logical order from start = kv_start[b] on,
+ *     start >= SP * page_size: key j < SP * page_size is read from list page j / page_size, key j >= start from list page
+ *     SP + (j - start) / page_size, anything between is not loaded and staged as zeros (it is always masked).  A list of at most SP
+ *     pages has no ring part; its length is (pages - 1) * page_size + last_page_offset, else start + (pages - SP - 1) * page_size +
+ *     last_page_offset.  No value of kv_start, pos_shift or sinks makes the kernel read outside the listed pages.
+ *   - A workgroup stages the sink tile (keys 0 .. 63) in front of its window's tiles, once where the window starts in it; the KV splits
+ *     divide that sequence of tiles.  Given equal contents, shifts and split count, the call on a ring list and the call with
+ *     kv_start == NULL on a list that released nothing perform the same operations in the same order: bit-identical results.
+ * Plan: the _ring plan with one more tile for the split policies (the sink tile), whether kv_start is given or not; queries of their
+ * own with the _ring queries' arguments.  The partial-state layout is unchanged (o == NULL on the decode entry feeds
+ * atom_gemm_w4a4_multi_merge_q).
+ * Errors: every fault of the _ring entries, in their order, except that a null kv_start is none; behind ALL of them sinks < 1 or
+ * sinks > 64 is ATOM_ERR_INVALID_ARG and a pos_shift off 4 bytes ATOM_ERR_ALIGN. */
+size_t atom_batch_decode_gqa_i4_sink_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq,
+                                                     int window);
+int atom_batch_decode_gqa_i4_sink_splits(int batch, int num_qo_heads, int num_kv_heads, int page_size, int max_pages_per_seq, int window);
+size_t atom_batch_prefill_gqa_i4_sink_workspace_bytes(int64_t total_q, int batch, int num_qo_heads, int num_kv_heads, int page_size,
+                                                      int max_q_len, int max_pages_per_seq, int window);
+int atom_batch_decode_gqa_i4_sink(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                  const int32_t *kv_indices, const int32_t *last_page_offset, int batch, int num_layers, int layer_idx,
+                                  int num_qo_heads, int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                  const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int sinks,
+                                  const int32_t *pos_shift, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
+int atom_batch_prefill_gqa_i4_sink(void *o, const void *q, const int32_t *qo_indptr, int64_t total_q, int max_q_len, const void *kv_data,
+                                   const void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                   const int32_t *last_page_offset, int batch, int num_layers, int layer_idx, int num_qo_heads,
+                                   int num_kv_heads, int page_size, int head_dim, float rope_theta, float rope_scale,
+                                   const float *rope_table, float attn_scale, int window, const int32_t *kv_start, int sinks,
+                                   const int32_t *pos_shift, int max_pages_per_seq, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Head size 64 (csrc/attn_d64.hip; Llama-3.2-1B, TinyLlama, SmolLM2: 64-wide heads).  Every entry point above keeps refusing
  * head_dim = 64 with ATOM_ERR_SHAPE; these take head_dim = 64 and refuse everything else the same way.  Argument order: that of the
  * 128 counterpart (atom_kv_quant_u4_f16, atom_kv_append_i4, atom_batch_prefill_gqa_i4_rope, atom_batch_decode_gqa_i4_rope).
@@ -696,6 +737,25 @@ int atom_kv_step_rows_i4(const int32_t *page_table, const int32_t *row_pages, in
 int atom_kv_step_ring_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
                          int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, int window,
                          int32_t *kv_start, void *stream);
+
+/* The ring step with PINNED SINK PAGES (attention sinks; the same kernel body): the arguments of
+ * atom_kv_step_ring_i4 plus `sinks` = S, 1 <= S <= 64, and a second output pos_shift int32 [batch].  SP = ceil(S / page_size).
+ *   - page_table[b]: slots 0 .. SP - 1 hold logical pages 0 .. SP - 1 and are never reused; logical page g >= SP lives in slot
+ *     SP + (g - SP) % R', R' = min(row_pages[b], cap) - SP (a ring of ceil((W - 1 + max_add) / page_size) + 1 slots serves steps of up
+ *     to max_add tokens).
+ * For the new length n = len_b + add:
+ *   - the live ring pages are f .. l, f = max(SP, max(0, n - max(add, 1) - W + 1) / page_size), l = (n - 1) / page_size;
+ *   - kv_indices lists the sink pages that exist (logical pages 0 .. min(SP, l + 1) - 1), then f .. l in logical order;
+ *   - kv_start[b] = f * page_size; pos_shift[b] = max(0, n - max(add, 1) - W + 1 - S) (what the _sink attention entries take);
+ *   - more live ring pages than R', or more sink pages than the row has slots: the sequence is NOT advanced, its tables are those of
+ *     a step of 0 tokens to its old length, and ATOM_KV_STEP_OVERFLOW is set; lengths are clamped and flagged as in the ring step (a
+ *     stored length that the slots cannot describe is listed by its last R' ring pages; the sequence is emptied where R' = 0 or the
+ *     sink pages do not fit).  No index from outside a row ever reaches kv_indices.
+ * Errors: as atom_kv_step_ring_i4, with ATOM_ERR_INVALID_ARG for sinks outside 1 .. 64 or a null pos_shift and ATOM_ERR_ALIGN for a
+ * pos_shift off 4 bytes. */
+int atom_kv_step_sink_i4(const int32_t *page_table, const int32_t *row_pages, int32_t *lens, int32_t *kv_indptr, int32_t *kv_indices,
+                         int32_t *last_page_offset, int32_t *state, int batch, int cap, int page_size, int add, int window, int sinks,
+                         int32_t *kv_start, int32_t *pos_shift, void *stream);
 
 /*
  * KV-cache fake quantisation of the simulated path: every 128-d head vector of x is quantised

@@ -1,13 +1,15 @@
 """Rolling KV cache of a sliding-window model: what the ring costs and what it saves.
 
-    python tools/ring_bench.py [--iters K] [--warmup W] [--only step|decode|generate]   (on the GPU box)
+    python tools/ring_bench.py [--iters K] [--warmup W] [--only step|decode|generate] [--sinks S]   (on the GPU box)
 
 step      ops.kv_step_ring_i4 against ops.kv_step_i4 on the same batch and row width: a rebuild (add = 0) of tables that list the
           same number of pages per sequence -- a static cache of W tokens, a rolling cache of 8 W tokens with window W.
 decode    atom_batch_decode_gqa_i4_ring against atom_batch_decode_gqa_i4_win at context 32,768, W = 4096, pages of 16, 32 / 8 heads,
           batch 1 / 16 / 64.  Both ops read the SAME pool bytes: the _win op through the full page list, the _ring op through the list
           of the last ceil(W / 16) + 1 pages with kv_start in front of them.  Timed in alternation, twice each: the two figures of an op
-          are the spread that the comparison is read against.
+          are the spread that the comparison is read against.  ``--sinks S``: atom_batch_decode_gqa_i4_sink too, on
+          the same ring list behind the sequence's first ceil(S / 16) pages, with the shift of a one-token step -- one more staged
+          tile per workgroup than the _ring op, timed in the same alternation.
 generate  tokens generated per pool page: generate(rolling_kv=True) against the default on a tiny windowed Llama (W = 4096), one
           prompt of 128 tokens, 8192 new tokens; the pages are the most the pool ever had out (counted in KvPoolInt4.alloc_block).
 One JSON line at the end."""
@@ -61,7 +63,7 @@ def step(iters, warmup):
     return out
 
 
-def decode(iters, warmup):
+def decode(iters, warmup, sinks=None):
     out = []
     pages = CTX // BLOCK
     R = -(-WINDOW // BLOCK) + 1
@@ -80,10 +82,24 @@ def decode(iters, warmup):
         r = {"batch": batch, "ctx": CTX, "window": WINDOW, "splits_win": ops.decode_splits(batch, full, NQ, window=WINDOW),
              "splits_ring": ops.decode_splits(batch, ring, NQ, window=WINDOW)}
         r["bit_identical"] = bool(torch.equal(ops.batch_decode_i4(q, full, 0, window=WINDOW), ops.batch_decode_i4(q, ring, 0, window=WINDOW)))
+        if sinks:
+            SP = -(-sinks // BLOCK)
+            both = torch.cat([full.indicies.view(batch, pages)[:, :SP], lists], dim=1).contiguous()
+            sink = types.SimpleNamespace(data=full.data, param=full.param, indicies=both.view(-1), last_page_offset=full.last_page_offset,
+                                         indptr=torch.arange(batch + 1, dtype=torch.int32, device=DEV) * (SP + cnt), max_pages=SP + R,
+                                         window=WINDOW, sinks=sinks, kv_start=ring.kv_start,
+                                         pos_shift=torch.full((batch,), CTX - WINDOW - sinks, dtype=torch.int32, device=DEV))
+            r["sinks"], r["splits_sink"] = sinks, ops.decode_splits(batch, sink, NQ, window=WINDOW, sinks=sinks)
         for rnd in (1, 2):
             r[f"win_us_{rnd}"] = _time(lambda: ops.batch_decode_i4(q, full, 0, window=WINDOW), iters, warmup)
             r[f"ring_us_{rnd}"] = _time(lambda: ops.batch_decode_i4(q, ring, 0, window=WINDOW), iters, warmup)
+            if sinks:
+                r[f"sink_us_{rnd}"] = _time(lambda: ops.batch_decode_i4(q, sink, 0, window=WINDOW, sinks=sinks), iters, warmup)
         r["ring_over_win"] = (r["ring_us_1"] + r["ring_us_2"]) / (r["win_us_1"] + r["win_us_2"])
+        if sinks:
+            r["sink_over_ring"] = (r["sink_us_1"] + r["sink_us_2"]) / (r["ring_us_1"] + r["ring_us_2"])
+            print(f"DECODE  b{batch:<3d} S {sinks}: _sink {r['sink_us_1']:8.1f} / {r['sink_us_2']:8.1f} us (splits {r['splits_sink']})   "
+                  f"sink / ring {r['sink_over_ring']:.3f}", flush=True)
         print(f"DECODE  b{batch:<3d} ctx {CTX} W {WINDOW}: _win {r['win_us_1']:8.1f} / {r['win_us_2']:8.1f} us (splits {r['splits_win']})   "
               f"_ring {r['ring_us_1']:8.1f} / {r['ring_us_2']:8.1f} us (splits {r['splits_ring']})   ring / win {r['ring_over_win']:.3f}   "
               f"bit-identical {r['bit_identical']}", flush=True)
@@ -135,12 +151,13 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default=None, choices=("step", "decode", "generate"))
+    ap.add_argument("--sinks", type=int, default=None, help="decode: time the attention-sink op with S sink tokens too")
     a = ap.parse_args()
     res = {}
     if a.only in (None, "step"):
         res["step"] = step(a.iters, a.warmup)
     if a.only in (None, "decode"):
-        res["decode"] = decode(a.iters, a.warmup)
+        res["decode"] = decode(a.iters, a.warmup, a.sinks)
     if a.only in (None, "generate"):
         res["generate"] = generate()
     print(json.dumps({"ring_bench": res}))
