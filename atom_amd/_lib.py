@@ -146,6 +146,11 @@ SIGNATURES = {
     "atom_guide_mask_f16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "atom_guide_advance": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "atom_guide_walk_rows": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp]),
+    # MXFP4 W4A4 (csrc/gemm_mxfp4.hip)
+    "atom_reorder_quant_mx_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "atom_quant_weight_mx_f16": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "atom_gemm_mxfp4_f16": (_int, [_vp] * 7 + [_i64, _i64, _i64, _vp]),
+    "atom_gemm_mxfp4_route": (_int, [_i64, _i64, _i64]),
 }
 
 _lib = None

@@ -7,3 +7,4 @@ from .generate import NgramDrafter, SpecDecodeGraph, SpecStats, SpeculativeParam
 from .guide import LogitGuide, TokenAutomaton  # noqa: F401
 from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4  # noqa: F401
 from .llama_lora import LlamaDecoderLayerWithLora, LlamaForCausalLMWithLora, LlamaModelWithLora  # noqa: F401
+from .mx import LinearMxfp4  # noqa: F401

@@ -1832,3 +1832,96 @@ def guide_walk_rows(state: torch.Tensor, adds: torch.Tensor, row_state: torch.Te
                                       indptr.numel() - 1, num_edges, 1 if force else 0, status.data_ptr(), L.current_stream(state.device))
     L.check(st, "atom_guide_walk_rows")
     return row_state
+
+
+# ------------------------------------------------------------------------------------------------ MXFP4 W4A4
+MxOperand = collections.namedtuple("MxOperand", "q4 sc q8 rows k")
+MxOperand.__doc__ = """An MXFP4 operand in the kernels' MFMA-fragment order (include/atom_hip.h, "MXFP4 W4A4"): q4 u8 [R, S, 64, 16] E2M1
+codes, sc u8 [R, S + 1, 64] E8M0 scale bytes, q8 u8 [R, 2, 64, 16] E4M3 keeper codes; R = ceil(rows / 16), S = k / 128 - 1."""
+
+
+def _mx_alloc(rows: int, k: int, device) -> MxOperand:
+    r, s = (rows + 15) // 16, k // GROUP_SIZE - 1
+    return MxOperand(torch.empty((r, s, 64, 16), dtype=torch.uint8, device=device), torch.empty((r, s + 1, 64), dtype=torch.uint8, device=device),
+                     torch.empty((r, 2, 64, 16), dtype=torch.uint8, device=device), rows, k)
+
+
+def reorder_quant_mx(x: torch.Tensor, reorder_index: torch.Tensor = None) -> MxOperand:
+    """NEW: gather fp16 ``x`` [M, K] by ``reorder_index`` (int16 [K], None = identity) and quantise it to the MX activation operand:
+    MXFP4 for the first K - 128 reordered channels, MXFP8 E4M3 for the last 128, one E8M0 scale per 32 channels."""
+    _require_cuda_half(x, "x")
+    m, k = x.shape
+    if reorder_index is not None and not (reorder_index.is_cuda and reorder_index.dtype == torch.int16 and tuple(reorder_index.shape) == (k,)
+                                          and reorder_index.is_contiguous()):
+        raise TypeError(f"reorder_index must be a contiguous int16 tensor of [{k}] on the GPU")
+    o = _mx_alloc(m, k, x.device)
+    st = L.lib().atom_reorder_quant_mx_f16(x.data_ptr(), L.ptr(reorder_index), m, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
+                                           L.current_stream(x.device))
+    L.check(st, "atom_reorder_quant_mx_f16")
+    return o
+
+
+def quant_weight_mx(weight: torch.Tensor) -> MxOperand:
+    """NEW: quantise an already column-reordered fp16 weight [N, K] to the MX weight operand (same arithmetic as ``reorder_quant_mx``)."""
+    _require_cuda_half(weight, "weight")
+    n, k = weight.shape
+    o = _mx_alloc(n, k, weight.device)
+    st = L.lib().atom_quant_weight_mx_f16(weight.data_ptr(), n, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(weight.device))
+    L.check(st, "atom_quant_weight_mx_f16")
+    return o
+
+
+def gemm_mxfp4_route(m: int, n: int, k: int) -> str:
+    """The geometry ``gemm_mxfp4`` runs a shape on: "decode" (M <= 16), "tile" (128 x 128), or None for an unsupported shape."""
+    return {0: None, 1: "decode", 2: "tile"}[L.lib().atom_gemm_mxfp4_route(m, n, k)]
+
+
+def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand) -> torch.Tensor:
+    """NEW: out fp16 [M, N] = a_mx @ w_mx^T on v_mfma_scale_f32_16x16x128_f8f6f4 with the operands' own block scales (FP32
+    accumulation, the keeper as one more K step).  One launch, no workspace: capturable."""
+    if not (a_mx.q4.is_cuda and w_mx.q4.is_cuda):
+        raise L.AtomHipError("MX operands must live on the GPU: the MXFP4 GEMM has no CPU fallback")
+    if a_mx.k != w_mx.k:
+        raise ValueError(f"operands disagree on K: {a_mx.k} vs {w_mx.k}")
+    m, n, k = a_mx.rows, w_mx.rows, a_mx.k
+    for o in (a_mx, w_mx):
+        r, s = (o.rows + 15) // 16, k // GROUP_SIZE - 1
+        if (tuple(o.q4.shape), tuple(o.sc.shape), tuple(o.q8.shape)) != ((r, s, 64, 16), (r, s + 1, 64), (r, 2, 64, 16)) or not (
+                o.q4.is_contiguous() and o.sc.is_contiguous() and o.q8.is_contiguous() and o.q4.dtype == o.sc.dtype == o.q8.dtype == torch.uint8):
+            raise ValueError("not a native MX operand (see ops.mx_from_plain)")
+    out = torch.empty((m, n), dtype=torch.float16, device=a_mx.q4.device)
+    st = L.lib().atom_gemm_mxfp4_f16(a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), w_mx.q4.data_ptr(), w_mx.sc.data_ptr(),
+                                     w_mx.q8.data_ptr(), out.data_ptr(), m, n, k, L.current_stream(out.device))
+    L.check(st, "atom_gemm_mxfp4_f16")
+    return out
+
+
+def mx_from_plain(codes: torch.Tensor, scales: torch.Tensor, keeper_codes: torch.Tensor, keeper_scales: torch.Tensor) -> MxOperand:
+    """Plain layout -> native operand, by indexing alone (any device).  codes u8 [rows, (K - 128) / 2] (even channel in the low
+    nibble), scales u8 [rows, (K - 128) / 32], keeper_codes u8 [rows, 128], keeper_scales u8 [rows, 4].  Rows are padded to a multiple
+    of 16 with zero codes and scale byte 127."""
+    rows, s = codes.shape[0], codes.shape[1] // 64
+    if (codes.shape[1] != 64 * s or s < 1 or tuple(scales.shape) != (rows, 4 * s) or tuple(keeper_codes.shape) != (rows, 128)
+            or tuple(keeper_scales.shape) != (rows, 4) or any(t.dtype != torch.uint8 for t in (codes, scales, keeper_codes, keeper_scales))):
+        raise ValueError("plain MX operand: u8 [rows, 64 S], [rows, 4 S], [rows, 128], [rows, 4]")
+    r = (rows + 15) // 16
+
+    def pad(t, fill):
+        return torch.cat([t, t.new_full((16 * r - rows, t.shape[1]), fill)]) if rows != 16 * r else t
+    # [tile, row, step, block, byte] -> [tile, step, lane = row + 16 block, byte]
+    q4 = pad(codes, 0).view(r, 16, s, 4, 16).permute(0, 2, 3, 1, 4).reshape(r, s, 64, 16)
+    sc4 = pad(scales, 127).view(r, 16, s, 4).permute(0, 2, 3, 1).reshape(r, s, 64)
+    sc8 = pad(keeper_scales, 127).view(r, 16, 4).permute(0, 2, 1).reshape(r, 1, 64)
+    # [tile, row, half, group, byte] -> [tile, half, lane = row + 16 group, byte]: keeper channel 64 half + 16 group + byte
+    q8 = pad(keeper_codes, 0).view(r, 16, 2, 4, 16).permute(0, 2, 3, 1, 4).reshape(r, 2, 64, 16)
+    return MxOperand(q4.contiguous(), torch.cat([sc4, sc8], dim=1).contiguous(), q8.contiguous(), rows, 128 * (s + 1))
+
+
+def mx_to_plain(o: MxOperand):
+    """Native operand -> (codes, scales, keeper_codes, keeper_scales) in the plain layout: the inverse of ``mx_from_plain``."""
+    r, s = o.q4.shape[0], o.q4.shape[1]
+    codes = o.q4.view(r, s, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(16 * r, 64 * s)
+    scales = o.sc[:, :s].reshape(r, s, 4, 16).permute(0, 3, 1, 2).reshape(16 * r, 4 * s)
+    k8 = o.q8.view(r, 2, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(16 * r, 128)
+    s8 = o.sc[:, s].reshape(r, 4, 16).permute(0, 2, 1).reshape(16 * r, 4)
+    return tuple(t[: o.rows].contiguous() for t in (codes, scales, k8, s8))

@@ -1234,6 +1234,44 @@ int atom_guide_walk_rows(int32_t *state, const int32_t *adds, int32_t *row_state
                          int64_t rows, const int32_t *indptr, const int32_t *edge_tok, const int32_t *edge_next, int64_t num_states,
                          int64_t num_edges, int32_t force, int32_t *status, void *stream);
 
+/*
+ * MXFP4 W4A4 (csrc/gemm_mxfp4.hip): the mixed-precision linear layer on OCP microscaling operands.  After the channel
+ * reorder the first K - 128 channels are MXFP4 (E2M1 codes), the last 128 (the keeper) MXFP8 (OCP E4M3, no infinities); both carry
+ * one E8M0 scale byte per block of 32 channels along K, applied inside v_mfma_scale_f32_16x16x128_f8f6f4.
+ *
+ * Quantisation of one block of 32 values v (fp16 input, FP32 arithmetic, every step exact but the one rounding):
+ *   amax = max |v|.  amax == 0: scale byte 127, codes 0.  Otherwise e = clamp(floor(log2(amax)) - emax, -127, 127) with emax = 2
+ *   (E2M1) or 8 (E4M3); scale byte = e + 127; code = |v| / 2^e rounded to nearest, ties to even, on the element grid (E2M1: 0, 0.5,
+ *   1, 1.5, 2, 3, 4, 6; E4M3: subnormal step 2^-9 below 2^-6, 3 mantissa bits above), saturated at 6 / 448; the sign bit (8 / 0x80)
+ *   is set exactly where v < 0 (so -0.0 and an all-zero block give code 0, a negative value that rounds to zero gives the
+ *   negative-zero code).  A NaN input is outside the contract.
+ *
+ * Plain layout (interchange; atom_amd.ops.mx_from_plain / mx_to_plain convert):
+ *   codes u8 [rows, (K - 128) / 2] (even channel in the low nibble), scales u8 [rows, (K - 128) / 32], keeper codes u8 [rows, 128],
+ *   keeper scales u8 [rows, 4]; a weight is the same with rows = N.
+ * Native layout (what the three entry points read and write): MFMA-fragment order.  R = ceil(rows / 16) row tiles, S = K / 128 - 1
+ * FP4 steps, lane = (row % 16) + 16 * (block % 4) -- the lane of the MFMA that holds that row's block:
+ *   q4 u8 [R][S][64 lanes][16]   the lane's 32 E2M1 codes of K step s: channels 128 s + 32 (lane / 16) .. + 31 of row 16 r + lane % 16
+ *   q8 u8 [R][2][64 lanes][16]   keeper channels 64 h + 16 (lane / 16) .. + 15 of row 16 r + lane % 16 in half h (the instruction's
+ *                                E4M3 operand order: a lane's registers 0 .. 3 and 4 .. 7)
+ *   sc u8 [R][S + 1][64 lanes]   the lane's scale byte of each K step (step S = the keeper)
+ * Rows beyond `rows` in the last tile hold zero codes and scale byte 127.  Bytes: 1024 R S, 2048 R, 64 R (S + 1).
+ *
+ * GEMM: out[m][n] = fp16( sum over blocks of 2^(ea - 127) 2^(eb - 127) sum_32 a b ), accumulated in FP32 in the MFMA accumulator, the
+ * keeper as one more K step of the same instruction.  Two geometries; atom_gemm_mxfp4_route tells which (1: decode, M <= 16, one
+ * 16-feature tile per workgroup, the K steps dealt to 8 waves and summed in wave order; 2: 128 x 128 tiles, K steps in order; 0: a
+ * shape the entry point refuses).  Shapes: M >= 1, N a multiple of 64, K a multiple of 128 and >= 256 (all below 2^31, K <= 2^20).
+ * Errors (checked before the launch): ATOM_ERR_INVALID_ARG for a null pointer (reorder_index may be null: identity), ATOM_ERR_SHAPE,
+ * ATOM_ERR_ALIGN for a pointer off 16 bytes.  One launch each, no workspace, nothing read back: capturable.
+ * reorder_index values must lie in [0, K); a value outside is clamped into the row, never followed.
+ */
+int atom_reorder_quant_mx_f16(const void *x_f16, const int16_t *reorder_index, int64_t M, int64_t K, void *q4, void *sc, void *q8,
+                              void *stream);
+int atom_quant_weight_mx_f16(const void *w_f16, int64_t N, int64_t K, void *q4, void *sc, void *q8, void *stream);
+int atom_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                        void *out_f16, int64_t M, int64_t N, int64_t K, void *stream);
+int atom_gemm_mxfp4_route(int64_t M, int64_t N, int64_t K);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,93 @@
+"""MXFP4 W4A4 against the shipped INT4 / BF6 routes on one GPU (profiles/mxfp4/README.md).
+
+  python tools/mx_bench.py [--reps 5] [--iters 50]
+
+Every figure is the median over --reps repetitions of the mean time of --iters replays of a captured graph holding one launch (hot:
+operands stay in L2 / MALL where they fit), the two sides of a comparison alternating inside one repetition; the spread printed beside
+a median is (max - min) over the repetitions of the same binary.  Prints one JSON line per measurement."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from atom_amd import ops  # noqa: E402
+
+
+def graph_of(fn):
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = fn()
+    return g, out
+
+
+def time_graphs(graphs, reps, iters):
+    """[median us, spread us] per graph; the graphs alternate inside a repetition"""
+    t = [[] for _ in graphs]
+    for g, _ in graphs:
+        for _ in range(5):
+            g.replay()
+    for _ in range(reps):
+        for i, (g, _) in enumerate(graphs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                g.replay()
+            b.record()
+            b.synchronize()
+            t[i].append(a.elapsed_time(b) * 1e3 / iters)
+    return [(statistics.median(x), max(x) - min(x)) for x in t]
+
+
+def operands(M, N, K, dev):
+    g = torch.Generator(device=dev).manual_seed(M + N + K)
+    x = torch.randn((M, K), generator=g, device=dev, dtype=torch.float16)
+    x[:, -128:] *= 20
+    w = (torch.randn((N, K), generator=g, device=dev, dtype=torch.float16) * 0.05)
+    return x, w
+
+
+def gemm_pair(M, N, K, dev):
+    """(MX GEMM, the shipped route on its fastest operand form for the shape) as callables"""
+    x, w = operands(M, N, K, dev)
+    a_mx, w_mx = ops.reorder_quant_mx(x), ops.quant_weight_mx(w)
+    b4, b8, sb, sb8 = ops.quant_weight_w4(w)
+    o8, o4, s8, s4 = ops.reorder_fp16_i4(x, None, scale_layout="plain")
+    if M > 256:                                                # prefill: both operands in the BF6 form (the headline kernel's own)
+        a6, w6 = ops.repack_act_f6(o4.view(torch.uint8), s4, scale_layout="plain"), ops.repack_weight_f6(b4, sb)
+        ref = lambda: ops.dense_layer_gemm_i4_fp16(a6, w6, s4, sb, o8, b8, s8, sb8, scale_layout="plain", a_wide="f6")   # noqa: E731
+    else:
+        ref = lambda: ops.dense_layer_gemm_i4_fp16(o4, b4, s4, sb, o8, b8, s8, sb8, scale_layout="plain")   # noqa: E731
+    return (lambda: ops.gemm_mxfp4(a_mx, w_mx)), ref
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mx_bench needs a GPU: nothing is measured without one")
+    dev = torch.device("cuda:0")
+    for M, N, K in [(4096, 4096, 4096), (1, 4096, 4096), (16, 4096, 4096), (256, 4096, 4096)]:
+        mx, ref = gemm_pair(M, N, K, dev)
+        # the same MX graph twice: the spread of two runs of the same binary beside the difference
+        (t_mx, s_mx), (t_ref, s_ref), (t_mx2, _) = time_graphs([graph_of(mx), graph_of(ref), graph_of(mx)], args.reps, args.iters)
+        print(json.dumps({"what": "gemm", "M": M, "N": N, "K": K, "route": ops.gemm_mxfp4_route(M, N, K), "mx_us": round(t_mx, 2),
+                          "mx_spread_us": round(s_mx, 2), "mx_again_us": round(t_mx2, 2), "shipped_us": round(t_ref, 2),
+                          "shipped_spread_us": round(s_ref, 2), "mx_tflops": round(2.0 * M * N * K / t_mx * 1e-6, 1)}))
+    x, _ = operands(2048, 64, 4096, dev)
+    idx = torch.randperm(4096, device=dev).to(torch.int16)
+    (t_mx, s_mx), (t_ref, s_ref) = time_graphs([graph_of(lambda: ops.reorder_quant_mx(x, idx)),
+                                                graph_of(lambda: ops.reorder_fp16_i4(x, idx, scale_layout="plain"))], args.reps, args.iters)
+    print(json.dumps({"what": "quantiser", "M": 2048, "K": 4096, "mx_us": round(t_mx, 2), "mx_spread_us": round(s_mx, 2),
+                      "reorder_fp16_i4_us": round(t_ref, 2), "shipped_spread_us": round(s_ref, 2)}))
+
+
+if __name__ == "__main__":
+    main()
