@@ -151,6 +151,9 @@ SIGNATURES = {
     "atom_quant_weight_mx_f16": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "atom_gemm_mxfp4_f16": (_int, [_vp] * 7 + [_i64, _i64, _i64, _vp]),
     "atom_gemm_mxfp4_route": (_int, [_i64, _i64, _i64]),
+    # MoE on MX operands (csrc/moe_mxfp4.hip)
+    "atom_moe_gemm_mxfp4_f16": (_int, [_vp] * 13 + [_i64, _i64, _int, _i64, _int, _i64, _vp]),
+    "atom_silu_mul_quant_mx_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -8,11 +8,13 @@
 // instruction with format code 0: one more K step.  Weights are the first operand, activations the second, so that a lane ends up
 // with 4 consecutive output features of one token (one 8-byte store).
 //
-//   mx_quant_kernel         both quantisers: one wave per row, 8 channels per lane and trip, block maximum across 4 lanes
+//   mx_quant_kernel         the quantisers: one wave per row, 8 channels per lane and trip, block maximum across 4 lanes; the 8 values
+//                           are the row's own (gathered by the reorder index or not) or silu(gate) * up of two rows, kept in FP32
 //   gemm_mxfp4_tile_kernel  128 x 128 tiles, 4 waves of 64 x 64, operands and scale bytes through a 3-stage LDS ring by LDS-DMA
 //   gemm_mxfp4_dec_kernel   M <= 16: one 16-feature tile per workgroup, weight fragments straight into registers, the K steps dealt
 //                           to 8 waves and summed through LDS in wave order
 #include "mx_math.h"
+#include "quant_math.h"
 
 namespace atom {
 namespace {
@@ -34,8 +36,11 @@ constexpr int FMT_E2M1 = 4, FMT_E4M3 = 0;
 // ------------------------------------------------------------------------------------------------------------------ quantiser
 // Row `row` of the padded operand (rows >= M are written as zero blocks), every lane 8 channels of a block per trip: lanes 4 b .. 4 b + 3
 // share block b of the trip's 16.  The lane's codes go to its 4 (E2M1) or 8 (E4M3) bytes of the MFMA lane that holds those channels.
-__global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict__ x, const int16_t *__restrict__ idx, int M, int rows_pad,
-                                                       int K, uint8_t *__restrict__ q4, uint8_t *__restrict__ sc, uint8_t *__restrict__ q8) {
+// SILU: the values are silu_mul<false>(x, up) of quant_math.h (x = gate; no reorder: the producer's rows are stored in channel order).
+template <bool SILU>
+__global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict__ x, const half_t *__restrict__ up, const int16_t *__restrict__ idx,
+                                                       int M, int rows_pad, int K, uint8_t *__restrict__ q4, uint8_t *__restrict__ sc,
+                                                       uint8_t *__restrict__ q8) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows_pad) return;
   const int S = K / 128 - 1, rt = row >> 4, r = row & 15;
@@ -43,7 +48,13 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict_
   for (int c0 = lane * 8; c0 < K; c0 += 512) {
     float v[8];
     if (row < M) {
-      if (idx) {
+      if constexpr (SILU) {
+        const v4u gv = *reinterpret_cast<const v4u *>(xr + c0), uv = *reinterpret_cast<const v4u *>(up + (int64_t)row * K + c0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          v[i] = silu_mul<false>(h2f(__builtin_bit_cast(half_t, (unsigned short)((gv[i >> 1] >> (16 * (i & 1))) & 0xffffu))),
+                                 h2f(__builtin_bit_cast(half_t, (unsigned short)((uv[i >> 1] >> (16 * (i & 1))) & 0xffffu))));
+      } else if (idx) {
         const v4u iv = *reinterpret_cast<const v4u *>(idx + c0);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -243,13 +254,14 @@ __global__ __launch_bounds__(64 * MXD_WAVES) void gemm_mxfp4_dec_kernel(MxGemmPa
 
 bool mx_shape_ok(int64_t rows, int64_t K) { return rows >= 1 && rows < (1ll << 31) - 16 && K >= 256 && (K % 128) == 0 && K <= (1 << 20); }
 
-int launch_mx_quant(const void *x, const int16_t *idx, int64_t rows, int64_t K, void *q4, void *sc, void *q8, void *stream) {
-  if (!x || !q4 || !sc || !q8) return ATOM_ERR_INVALID_ARG;
+template <bool SILU>
+int launch_mx_quant(const void *x, const void *up, const int16_t *idx, int64_t rows, int64_t K, void *q4, void *sc, void *q8, void *stream) {
+  if (!x || (SILU && !up) || !q4 || !sc || !q8) return ATOM_ERR_INVALID_ARG;
   if (!mx_shape_ok(rows, K)) return ATOM_ERR_SHAPE;
-  if (!aligned16(x) || !aligned16(idx) || !aligned16(q4) || !aligned16(sc) || !aligned16(q8)) return ATOM_ERR_ALIGN;
+  if (!aligned16(x) || !aligned16(up) || !aligned16(idx) || !aligned16(q4) || !aligned16(sc) || !aligned16(q8)) return ATOM_ERR_ALIGN;
   const int64_t pad = (rows + 15) / 16 * 16;
-  hipLaunchKernelGGL(mx_quant_kernel, dim3((unsigned)(pad / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x, idx,
-                     (int)rows, (int)pad, (int)K, (uint8_t *)q4, (uint8_t *)sc, (uint8_t *)q8);
+  hipLaunchKernelGGL(mx_quant_kernel<SILU>, dim3((unsigned)(pad / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x,
+                     (const half_t *)up, idx, (int)rows, (int)pad, (int)K, (uint8_t *)q4, (uint8_t *)sc, (uint8_t *)q8);
   return check_launch();
 }
 
@@ -263,12 +275,16 @@ extern "C" {
 int atom_reorder_quant_mx_f16(const void *x_f16, const int16_t *reorder_index, int64_t M, int64_t K, void *q4, void *sc, void *q8,
                               void *stream) {
   if (K > 32768 && reorder_index) return ATOM_ERR_SHAPE;   // int16 indices
-  return launch_mx_quant(x_f16, reorder_index, M, K, q4, sc, q8, stream);
+  return launch_mx_quant<false>(x_f16, nullptr, reorder_index, M, K, q4, sc, q8, stream);
+}
+
+int atom_silu_mul_quant_mx_f16(const void *gate_f16, const void *up_f16, int64_t rows, int64_t K, void *q4, void *sc, void *q8, void *stream) {
+  return launch_mx_quant<true>(gate_f16, up_f16, nullptr, rows, K, q4, sc, q8, stream);
 }
 
 int atom_quant_weight_mx_f16(const void *w_f16, int64_t N, int64_t K, void *q4, void *sc, void *q8, void *stream) {
   if (w_f16 && q4 && sc && q8 && (N < 64 || (N % 64) != 0)) return ATOM_ERR_SHAPE;
-  return launch_mx_quant(w_f16, nullptr, N, K, q4, sc, q8, stream);
+  return launch_mx_quant<false>(w_f16, nullptr, nullptr, N, K, q4, sc, q8, stream);
 }
 
 // 0: not a shape of the GEMM; 1: the decode geometry; 2: 128 x 128 tiles

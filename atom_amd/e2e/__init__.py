@@ -5,6 +5,6 @@ from .llama import (LinearInt4, LlamaAttention, LlamaDecoderLayer, LlamaForCausa
 from .generate import BeamDecodeGraph, BeamHypothesis, DecodeGraph, LogitPenalties, Sampler, SamplingParams, StreamingParams, TokenLogprobs, backtrack_beams, beam_search, generate, perplexity, score  # noqa: F401
 from .generate import NgramDrafter, SpecDecodeGraph, SpecStats, SpeculativeParams  # noqa: F401
 from .guide import LogitGuide, TokenAutomaton  # noqa: F401
-from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4  # noqa: F401
+from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4, MixtralSparseMoeMxfp4  # noqa: F401
 from .llama_lora import LlamaDecoderLayerWithLora, LlamaForCausalLMWithLora, LlamaModelWithLora  # noqa: F401
 from .mx import LinearMxfp4  # noqa: F401

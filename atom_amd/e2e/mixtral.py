@@ -65,9 +65,55 @@ class MixtralSparseMoeInt4(nn.Module):
         return ops.moe_combine(y, route, residual)
 
 
+class MixtralSparseMoeMxfp4(nn.Module):
+    """The block on MX operands: MXFP4 channels and an MXFP8 keeper with their own E8M0 scales, multiplied on the
+    block-scaled MFMA.  The experts' weights are ``ops.quant_weight_mx`` operands stacked: ``w13_*`` = gate (w1) rows then up (w3)
+    rows of each expert, ``w2_*`` = down.  Same router, tables and combine as ``MixtralSparseMoeInt4``."""
+
+    def __init__(self, config):
+        super().__init__()
+        h, f = config.hidden_size, config.intermediate_size
+        e = self.num_experts = int(config.num_local_experts)
+        self.top_k = int(config.num_experts_per_tok)
+        self.hidden_size, self.intermediate_size = h, f
+        if h % GROUP or f % GROUP or h < 2 * GROUP or f < 2 * GROUP:
+            raise ValueError("hidden_size and intermediate_size must be multiples of 128, at least 256")
+        if not (2 <= e <= 64 and 1 <= self.top_k <= min(8, e)):
+            raise ValueError(f"{e} experts, top-{self.top_k}: the router takes 2..64 experts and top-1..8")
+        self.gate = nn.Linear(h, e, bias=False, dtype=torch.float16)
+        par = lambda *shape: nn.Parameter(torch.empty(*shape, dtype=torch.uint8), requires_grad=False)
+        for name, n, k in (("w13", 2 * f, h), ("w2", h, f)):
+            setattr(self, name + "_fp4", par(e, n // 16, k // GROUP - 1, 64, 16))
+            setattr(self, name + "_scale", par(e, n // 16, k // GROUP, 64))
+            setattr(self, name + "_fp8", par(e, n // 16, 2, 64, 16))
+
+    @torch.no_grad()
+    def load_expert_fp16(self, j: int, w1: torch.Tensor, w3: torch.Tensor, w2: torch.Tensor):
+        """Fill expert ``j`` from its (column-reordered) fp16 weights: w1 / w3 [F, H] (gate / up), w2 [H, F] (down)."""
+        f, h = self.intermediate_size, self.hidden_size
+        assert w1.shape == (f, h) and w3.shape == (f, h) and w2.shape == (h, f)
+        for name, w in (("w13", torch.cat([w1, w3], 0)), ("w2", w2)):
+            o = ops.quant_weight_mx(w.contiguous())
+            getattr(self, name + "_fp4").data[j].copy_(o.q4)
+            getattr(self, name + "_scale").data[j].copy_(o.sc)
+            getattr(self, name + "_fp8").data[j].copy_(o.q8)
+        return self
+
+    def forward(self, x: torch.Tensor, reorder_index: torch.Tensor, residual: torch.Tensor = None) -> torch.Tensor:
+        """``x`` fp16 [T, H]: the post-norm states, un-quantised -- the router's input and, reordered by ``reorder_index`` (int16 [H])
+        and quantised to MX, the experts'; ``residual`` fp16 [T, H] or None.  Returns residual + moe(x) fp16 [T, H]."""
+        route = ops.moe_route_topk(nn.functional.linear(x, self.gate.weight), self.top_k)
+        x_mx = ops.reorder_quant_mx(x, reorder_index)
+        gate, up = ops.moe_gemm_mxfp4(x_mx, (self.w13_fp4, self.w13_scale, self.w13_fp8), route, gather=True, nseg=2)
+        (y,) = ops.moe_gemm_mxfp4(ops.silu_mul_quant_mx(gate, up), (self.w2_fp4, self.w2_scale, self.w2_fp8), route, gather=False)
+        return ops.moe_combine(y, route, residual)
+
+
 class MixtralDecoderLayer(nn.Module):
     """reference qMixtralLayer.py:353-436: Llama's attention block (grouped-query), then the sparse MoE block on the quantised
-    post-attention norm; the router's input is the same norm un-quantised (its gate is a QLinearLayer with enable_quant=False)."""
+    post-attention norm; the router's input is the same norm un-quantised (its gate is a QLinearLayer with enable_quant=False).
+    ``config.expert_format = "mxfp4"`` (default "int4") builds the experts on MX operands: that block quantises the un-quantised norm
+    itself, in the post-attention norm's channel order; attention stays on the INT4 path."""
 
     def __init__(self, config, layer_idx: int, fusion: DecodeFusion = None):
         super().__init__()
@@ -77,7 +123,10 @@ class MixtralDecoderLayer(nn.Module):
         self.self_attn = LlamaAttention(config=config, layer_idx=layer_idx, fusion=fusion)
         if self.self_attn.head_dim != 128:
             raise NotImplementedError(f"the Mixtral classes are built for head_dim 128, got {self.self_attn.head_dim}")
-        self.block_sparse_moe = MixtralSparseMoeInt4(config)
+        fmt = getattr(config, "expert_format", "int4")
+        if fmt not in ("int4", "mxfp4"):
+            raise ValueError(f"config.expert_format must be \"int4\" or \"mxfp4\", got {fmt!r}")
+        self.block_sparse_moe = MixtralSparseMoeMxfp4(config) if fmt == "mxfp4" else MixtralSparseMoeInt4(config)
         self.input_layernorm = LlamaRMSNormInt4(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = LlamaRMSNormInt4(config.hidden_size, eps=config.rms_norm_eps)
 
@@ -88,6 +137,8 @@ class MixtralDecoderLayer(nn.Module):
         h = residual.float()                                     # LlamaRMSNorm's arithmetic: fp32 statistics, weight after the cast back
         h = h * torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + pl.variance_epsilon)
         gate_in = pl.weight * h.to(residual.dtype)
+        if isinstance(self.block_sparse_moe, MixtralSparseMoeMxfp4):
+            return self.block_sparse_moe(gate_in, pl.reorder_index, residual)
         return self.block_sparse_moe(normed, gate_in, residual)
 
 

@@ -1896,6 +1896,57 @@ def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand) -> torch.Tensor:
     return out
 
 
+def _mx_native(o: MxOperand) -> bool:
+    r, s = (o.rows + 15) // 16, o.k // GROUP_SIZE - 1
+    return (tuple(o.q4.shape), tuple(o.sc.shape), tuple(o.q8.shape)) == ((r, s, 64, 16), (r, s + 1, 64), (r, 2, 64, 16)) and (
+        o.q4.is_contiguous() and o.sc.is_contiguous() and o.q8.is_contiguous() and o.q4.dtype == o.sc.dtype == o.q8.dtype == torch.uint8)
+
+
+def silu_mul_quant_mx(gate: torch.Tensor, up: torch.Tensor) -> MxOperand:
+    """NEW: the MX activation operand of silu(gate) * up (fp16 [rows, K] each; the product stays in FP32 up to the codes), no reorder:
+    what the routed down projection of ``MixtralSparseMoeMxfp4`` reads."""
+    _require_cuda_half(gate, "gate")
+    _require_cuda_half(up, "up")
+    if gate.dim() != 2 or gate.shape != up.shape:
+        raise ValueError(f"gate and up must be [rows, K] of one shape, got {tuple(gate.shape)} and {tuple(up.shape)}")
+    rows, k = gate.shape
+    o = _mx_alloc(rows, k, gate.device)
+    st = L.lib().atom_silu_mul_quant_mx_f16(gate.data_ptr(), up.data_ptr(), rows, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
+                                            L.current_stream(gate.device))
+    L.check(st, "atom_silu_mul_quant_mx_f16")
+    return o
+
+
+def moe_gemm_mxfp4(a_mx: MxOperand, experts, route: MoeRoute, *, gather: bool, nseg=1):
+    """NEW: the routed GEMM on MX operands: every routed row of ``route`` times ITS expert's weight, one launch for all experts.
+    ``experts`` = (q4 u8 [E, N/16, S, 64, 16], sc u8 [E, N/16, S+1, 64], q8 u8 [E, N/16, 2, 64, 16]): ``quant_weight_mx`` operands
+    stacked.  ``gather=True``: ``a_mx`` holds one quantised row per TOKEN and row r reads token route.row_token[r]; ``gather=False``:
+    it holds the routed rows themselves.  Returns ``nseg`` (1 or 2) tensors fp16 [rows, N / nseg].  Bit-identical to ``gemm_mxfp4``'s
+    tile geometry on each expert's rows."""
+    q4, sc, q8 = experts
+    for t in (a_mx.q4, q4, sc, q8):
+        if not t.is_cuda:
+            raise L.AtomHipError("MX operands must live on the GPU: the routed MXFP4 GEMM has no CPU fallback")
+    e, nfr, s = q4.shape[:3]
+    n, k, rows = 16 * nfr, a_mx.k, route.rows
+    if not _mx_native(a_mx) or a_mx.rows != (route.tokens if gather else rows):
+        raise ValueError(f"a_mx: a native MX operand of {route.tokens if gather else rows} rows")
+    if (tuple(q4.shape), tuple(sc.shape), tuple(q8.shape)) != ((e, nfr, s, 64, 16), (e, nfr, s + 1, 64), (e, nfr, 2, 64, 16)) or not (
+            q4.is_contiguous() and sc.is_contiguous() and q8.is_contiguous() and q4.dtype == sc.dtype == q8.dtype == torch.uint8):
+        raise ValueError("experts: stacked native MX weight operands (q4, sc, q8)")
+    if e != route.experts or GROUP_SIZE * (s + 1) != k or nseg not in (1, 2) or n % nseg:
+        raise ValueError(f"experts [{e}, {n}, {GROUP_SIZE * (s + 1)}] do not fit {route.experts} routed experts, K = {k}, nseg = {nseg}")
+    n_seg = n // nseg
+    outs = [torch.empty((rows, n_seg), dtype=torch.float16, device=q4.device) for _ in range(nseg)]
+    st = L.lib().atom_moe_gemm_mxfp4_f16(a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), q4.data_ptr(), sc.data_ptr(), q8.data_ptr(),
+                                         route.row_token.data_ptr() if gather else None, route.expert_indptr.data_ptr(),
+                                         route.tile_expert.data_ptr(), route.tile_row0.data_ptr(), route.n_tiles.data_ptr(),
+                                         outs[0].data_ptr(), outs[1].data_ptr() if nseg > 1 else None, a_mx.rows, rows, e, n_seg, nseg, k,
+                                         L.current_stream(q4.device))
+    L.check(st, "atom_moe_gemm_mxfp4_f16")
+    return tuple(outs)
+
+
 def mx_from_plain(codes: torch.Tensor, scales: torch.Tensor, keeper_codes: torch.Tensor, keeper_scales: torch.Tensor) -> MxOperand:
     """Plain layout -> native operand, by indexing alone (any device).  codes u8 [rows, (K - 128) / 2] (even channel in the low
     nibble), scales u8 [rows, (K - 128) / 32], keeper_codes u8 [rows, 128], keeper_scales u8 [rows, 4].  Rows are padded to a multiple

@@ -1272,6 +1272,42 @@ int atom_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8, co
                         void *out_f16, int64_t M, int64_t N, int64_t K, void *stream);
 int atom_gemm_mxfp4_route(int64_t M, int64_t N, int64_t K);
 
+/*
+ * Sparse mixture of experts on MXFP4 (csrc/moe_mxfp4.hip): the routed GEMM of the block above on MX operands, between
+ * the same router (atom_moe_route_topk) and the same combine (atom_moe_combine_f16), and the SiLU x up quantiser that feeds its down
+ * projection.
+ *
+ * atom_moe_gemm_mxfp4_f16: for every routed row r of expert e (expert_indptr[e] <= r < expert_indptr[e+1]) and segment s < nseg
+ *     out_s[r, :] = a[src(r)] . W_e[s N_seg : (s + 1) N_seg, :]^T        out_s fp16 [R, N_seg], contiguous
+ *   Activation: ONE native MX operand q4 [Ra, S, 64, 16], sc [Ra, S + 1, 64], q8 [Ra, 2, 64, 16], Ra = ceil(A_rows / 16).  With
+ *   row_index (the router's row_token) src(r) = row_index[r] and A_rows = T: one quantised row per token (gate / up).  With row_index
+ *   NULL src(r) = r and A_rows = R (down).  Expert segments are NOT aligned to 16 rows in either case: a routed row's 16 code bytes of
+ *   block b are those of lane src % 16 + 16 b of fragment src / 16, its scale byte that lane's.
+ *   Weights: the dense weight operand per expert, stacked: q4 [E, N / 16, S, 64, 16], sc [E, N / 16, S + 1, 64], q8 [E, N / 16, 2, 64,
+ *   16]; N = nseg N_seg, nseg 1 or 2 (gate rows, then up rows), N_seg % 64 == 0; K a multiple of 128, at least 256.
+ *   Every output element is ONE MFMA accumulation chain -- K steps 0 .. S - 1 in order, then the keeper step -- as in the dense
+ *   128 x 128 geometry: the bits of a row do not depend on the tile it lands in, on its expert's row count or on the gather, and
+ *   equal atom_gemm_mxfp4_f16's (route 2) for the same row and weight.
+ *   Tables: those of atom_moe_route_topk (a router tile = up to 64 routed rows of one expert), or any of that form.  An entry the
+ *   router did not write never becomes an address: an expert outside 0 .. E - 1 or a row0 outside its expert's segment ends the
+ *   workgroup, source rows are clamped to A_rows - 1; rows at or past the segment's end (and >= R) are never stored.
+ *   Grid: atom_moe_max_tiles(R, E) * (N / 64) workgroups sized on the host from R alone; those beyond *n_tiles leave before touching
+ *   memory.  Nothing is read back: capturable.
+ *   Errors, before any launch: ATOM_ERR_INVALID_ARG for a null operand, table or out0, nseg outside 1 .. 2, a null out1 with nseg 2;
+ *   ATOM_ERR_SHAPE unless 1 <= E <= 64, 1 <= R < 2^31, 1 <= A_rows <= 2^24, N_seg a multiple of 64, K as above, and the activation
+ *   codes below 4 GiB (32-bit lane offsets); ATOM_ERR_ALIGN for an operand or output off 16 bytes or a table off 4.
+ *
+ * atom_silu_mul_quant_mx_f16: gate, up fp16 [rows, K] -> the MX activation operand of v = silu(gate) * up, v the FP32 value
+ *   g * rcp(1 + exp2(-g log2 e)) * u with the hardware exp2 / rcp (no rounding to half in between), codes and scales of v by the block
+ *   rule above; no channel reorder.  Shapes, errors and padding rows as atom_reorder_quant_mx_f16.
+ */
+int atom_moe_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                            const int32_t *row_index, const int32_t *expert_indptr, const int32_t *tile_expert, const int32_t *tile_row0,
+                            const int32_t *n_tiles, void *out0, void *out1, int64_t A_rows, int64_t R, int E, int64_t N_seg, int nseg,
+                            int64_t K, void *stream);
+int atom_silu_mul_quant_mx_f16(const void *gate_f16, const void *up_f16, int64_t rows, int64_t K, void *q4, void *sc, void *q8,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

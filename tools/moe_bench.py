@@ -3,6 +3,7 @@ the library could write before the routed kernels existed: the reference's per-e
 over ops.dense_layer_gemm_i4_fp16 with gathers and index_add_.
 
     python tools/moe_bench.py [tokens,tokens,...] [--blocks N] [--out FILE]
+    python tools/moe_bench.py --mx [tokens,...] [--blocks N] [--reps R] [--out FILE]      the MX block against the INT4 block (below)
 
 Per token count (default 1, 16, 64, 2048), us per block:
     new/graph   MixtralSparseMoeInt4.forward captured in a HIP graph and replayed (router matmul + 5 launches, no host work)
@@ -11,7 +12,12 @@ Per token count (default 1, 16, 64, 2048), us per block:
 each "hot" (one block's weights in every call: what fits stays in the Infinity Cache) and "cold" (cycling through N distinct blocks,
 N x 0.69 GB of expert weights, so every call streams its experts from HBM).  Launch counts: calls into libatom_hip.so and torch
 operators dispatched per block call.  Also prints the largest difference between the two outputs on the same inputs (the loop's dense
-GEMMs may sum the K steps in another order at prefill sizes: include/atom_hip.h, atom_gemm_w4a4_packed_order)."""
+GEMMs may sum the K steps in another order at prefill sizes: include/atom_hip.h, atom_gemm_w4a4_packed_order).
+
+--mx (default tokens 1, 16, 2048): MixtralSparseMoeMxfp4 against MixtralSparseMoeInt4 in one process, each captured in a HIP graph that
+cycles through the N blocks (cold: every call streams its experts from HBM); the two graphs are replayed in turn R times and the table
+gives the median and the range of the R replays per format, and the ratio of the medians.  The INT4 block gets its operand quantised
+outside the timed graph (in the model the fused norm kernel produces it); the MX block's timed graph includes reorder_quant_mx."""
 import argparse
 import os
 import sys
@@ -24,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from atom_amd import _lib as L  # noqa: E402
 from atom_amd import ops  # noqa: E402
-from atom_amd.e2e import MixtralSparseMoeInt4  # noqa: E402
+from atom_amd.e2e import MixtralSparseMoeInt4, MixtralSparseMoeMxfp4  # noqa: E402
 
 H, F, E, K = 4096, 14336, 8, 2
 dev = torch.device("cuda", 0)
@@ -142,13 +148,96 @@ def graph_time(fns, iters):
     return best
 
 
+def make_mx_block(seed):
+    """random codes, scale bytes 2^-14 .. 2^-10 (outputs stay finite in fp16), E4M3 keeper codes without the NaN pattern"""
+    cfg = types.SimpleNamespace(hidden_size=H, intermediate_size=F, num_local_experts=E, num_experts_per_tok=K)
+    moe = MixtralSparseMoeMxfp4(cfg).to(dev)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    for name, p in moe.named_parameters():
+        if name.endswith("_scale"):
+            p.data.copy_(torch.randint(113, 118, p.shape, device=dev, generator=g, dtype=torch.uint8))
+        elif name.endswith("_fp8"):
+            p.data.copy_(torch.randint(0, 256, p.shape, device=dev, generator=g, dtype=torch.uint8) & 0xBF)
+        elif p.dtype == torch.uint8:
+            p.data.copy_(torch.randint(0, 256, p.shape, device=dev, generator=g, dtype=torch.uint8))
+        else:
+            p.data.copy_((torch.randn(p.shape, device=dev, generator=g) * 0.1).half())
+    return moe
+
+
+def alternating_graph_times(fn_lists, iters, reps):
+    """one graph per list (its calls in turn, `iters` of them), replayed alternately `reps` times: us per call of every replay"""
+    graphs = []
+    for fns in fn_lists:
+        for f in fns:
+            f()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for i in range(iters):
+                fns[i % len(fns)]()
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    times = [[] for _ in graphs]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(reps):
+        for g, t in zip(graphs, times):
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1) * 1e3 / iters)
+    return times
+
+
+def main_mx(a):
+    int4, mx = [make_block(s) for s in range(a.blocks)], [make_mx_block(s) for s in range(a.blocks)]
+    gb = lambda m: sum(p.numel() * p.element_size() for p in m.parameters()) / 1e9   # noqa: E731
+    lines = [f"# sparse MoE block, H {H} F {F} E {E} top-{K}: MXFP4 against INT4, us per block, graph replay cycling through {a.blocks} blocks "
+             f"({gb(mx[0]):.2f} / {gb(int4[0]):.2f} GB each), {a.reps} alternating replays: median [min .. max]",
+             "| tokens | int4 | mxfp4 | mxfp4 / int4 (medians) | active experts |", "|---|---|---|---|---|"]
+    print("\n".join(lines), flush=True)
+    for T in (int(v) for v in a.tokens.split(",")):
+        g = torch.Generator(device=dev).manual_seed(T)
+        x = torch.randn((T, H), device=dev, generator=g)
+        x[:, -128:] *= 10
+        x = x.half()
+        residual = torch.randn((T, H), device=dev, generator=g).half()
+        idx = torch.randperm(H, device=dev, generator=g).to(torch.int16)
+        for m in int4 + mx:                                    # one routing for both formats
+            m.gate.weight.data.copy_(int4[0].gate.weight.data)
+        xq = ops.reorder_fp16_i4(x, idx)
+        iters = max(a.blocks, 16 if T <= 64 else 4)
+        iters -= iters % a.blocks
+        ti, tm = alternating_graph_times([[lambda m=m: m(xq, x, residual) for m in int4], [lambda m=m: m(x, idx, residual) for m in mx]],
+                                         iters, a.reps)
+        med = lambda t: sorted(t)[len(t) // 2]                 # noqa: E731
+        active = int((ops.moe_route_topk(torch.nn.functional.linear(x, int4[0].gate.weight), K).expert_indptr.diff() > 0).sum())
+        row = (f"| {T} | {med(ti):.1f} [{min(ti):.1f} .. {max(ti):.1f}] | {med(tm):.1f} [{min(tm):.1f} .. {max(tm):.1f}] | "
+               f"{med(tm) / med(ti):.3f} | {active} |")
+        print(row, flush=True)
+        lines.append(row)
+    return lines
+
+
 @torch.no_grad()
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("tokens", nargs="?", default="1,16,64,2048")
+    ap.add_argument("tokens", nargs="?", default=None)
     ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--mx", action="store_true")
+    ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.tokens = a.tokens or ("1,16,2048" if a.mx else "1,16,64,2048")
+    if a.mx:
+        lines = main_mx(a)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     blocks = [make_block(s) for s in range(a.blocks)]
     lines = [f"# sparse MoE block, H {H} F {F} E {E} top-{K}; us per block; cold = cycling through {a.blocks} blocks "
              f"({a.blocks} x {sum(p.numel() * p.element_size() for p in blocks[0].parameters()) / 1e9:.2f} GB)",
