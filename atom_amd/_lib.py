@@ -154,6 +154,12 @@ SIGNATURES = {
     # MoE on MX operands (csrc/moe_mxfp4.hip)
     "atom_moe_gemm_mxfp4_f16": (_int, [_vp] * 13 + [_i64, _i64, _int, _i64, _int, _i64, _vp]),
     "atom_silu_mul_quant_mx_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    # dense Llama on MX operands (csrc/llama_mxfp4.hip; the add form of the GEMM: csrc/gemm_mxfp4.hip)
+    "atom_gemm_mxfp4_silu_mul_quant": (_int, [_vp] * 9 + [_i64, _i64, _i64, _vp]),
+    "atom_gemm_mxfp4_silu_mul_quant_route": (_int, [_i64, _i64, _i64]),
+    "atom_rmsnorm_quant_mx_f16": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "atom_add_rmsnorm_quant_mx_f16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "atom_gemm_mxfp4_add_f16": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp]),
 }
 
 _lib = None

@@ -7,4 +7,4 @@ from .generate import NgramDrafter, SpecDecodeGraph, SpecStats, SpeculativeParam
 from .guide import LogitGuide, TokenAutomaton  # noqa: F401
 from .mixtral import MixtralDecoderLayer, MixtralForCausalLM, MixtralModel, MixtralSparseMoeInt4, MixtralSparseMoeMxfp4  # noqa: F401
 from .llama_lora import LlamaDecoderLayerWithLora, LlamaForCausalLMWithLora, LlamaModelWithLora  # noqa: F401
-from .mx import LinearMxfp4  # noqa: F401
+from .mx import LinearMxfp4, LlamaAttentionMxfp4, LlamaDecoderLayerMxfp4, LlamaMLPMxfp4  # noqa: F401

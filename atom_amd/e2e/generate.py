@@ -669,6 +669,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, pool:
     ``rolling_kv`` itself.  ``streaming=None`` is the code above, launch for launch."""
     _check_combination(caches, return_logits, sampling, logprobs, num_beams, speculative, drafter, return_spec_stats, guide, rolling_kv,
                        streaming)
+    if (rolling_kv or streaming is not None) and getattr(getattr(model, "config", None), "linear_format", "int4") != "int4":
+        raise NotImplementedError("generate: rolling_kv and streaming are not built for config.linear_format = \"mxfp4\"")
     args = (model, prompts, max_new_tokens, pool, eos_token_id, caches, return_logits, sampling, logprobs, num_beams, speculative, drafter,
             return_spec_stats, guide)
     if streaming is None:

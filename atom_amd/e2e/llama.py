@@ -615,8 +615,22 @@ class LlamaModel(nn.Module):
         super().__init__()
         self.config = config
         self.embed_tokens = nn.Embedding(config.vocab_size, config.hidden_size, getattr(config, "pad_token_id", None), dtype=torch.float16)
-        self.layers = nn.ModuleList([self.layer_class(config, i) for i in range(config.num_hidden_layers)])
+        self.layers = nn.ModuleList([self._layer_class(config)(config, i) for i in range(config.num_hidden_layers)])
         self.norm = LlamaRMSNorm(config.hidden_size, eps=config.rms_norm_eps)
+
+    @classmethod
+    def _layer_class(cls, config):
+        """``config.linear_format``: "int4" (default: ``layer_class``) or "mxfp4" (the dense MX decoder layer of e2e/mx.py, DESIGN.md
+        4.28; ``NotImplementedError`` on the subclasses that stack another layer: Mixtral, LoRA)."""
+        fmt = getattr(config, "linear_format", "int4")
+        if fmt not in ("int4", "mxfp4"):
+            raise ValueError(f"config.linear_format must be \"int4\" or \"mxfp4\", got {fmt!r}")
+        if fmt == "int4":
+            return cls.layer_class
+        if cls.layer_class is not LlamaDecoderLayer:
+            raise NotImplementedError(f"config.linear_format = \"mxfp4\" is not built for {cls.__name__}")
+        from .mx import LlamaDecoderLayerMxfp4
+        return LlamaDecoderLayerMxfp4
 
     @torch.no_grad()
     def forward(self, input_ids, blen: BatchLenInfo, prefill_kv, decode_kv) -> torch.Tensor:
@@ -646,8 +660,9 @@ class LlamaForCausalLM(nn.Module):
         (``pos_shift``: a ``RollingKvCacheInt4(sinks=...)`` writes it).  A streaming layer attends through the ops in prefill and in
         decode, as a windowed layer does.  ``set_streaming(None)`` clears.  ``ValueError`` on a model whose layers carry a trained window
         (that model uses ``generate(rolling_kv=True)``); ``NotImplementedError`` at head size 64 and on the Mixtral and LoRA classes."""
-        if type(self) is not LlamaForCausalLM:
-            raise NotImplementedError(f"attention sinks are not built for {type(self).__name__}")
+        if type(self) is not LlamaForCausalLM or getattr(self.config, "linear_format", "int4") != "int4":
+            raise NotImplementedError(f"attention sinks are not built for {type(self).__name__}" +
+                                      ("" if type(self) is not LlamaForCausalLM else " with config.linear_format = \"mxfp4\""))
         if sinks is not None:
             for name, v, hi in (("sinks", sinks, 64), ("window", window, None)):
                 if isinstance(v, bool) or not isinstance(v, int) or v < 1 or (hi is not None and v > hi):

@@ -1876,23 +1876,28 @@ def gemm_mxfp4_route(m: int, n: int, k: int) -> str:
     return {0: None, 1: "decode", 2: "tile"}[L.lib().atom_gemm_mxfp4_route(m, n, k)]
 
 
-def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand) -> torch.Tensor:
+def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand, add: torch.Tensor = None) -> torch.Tensor:
     """NEW: out fp16 [M, N] = a_mx @ w_mx^T on v_mfma_scale_f32_16x16x128_f8f6f4 with the operands' own block scales (FP32
-    accumulation, the keeper as one more K step).  One launch, no workspace: capturable."""
+    accumulation, the keeper as one more K step).  ``add`` (fp16 [M, N]): out = half(sum + float(add)) in the same store -- the
+    residual stream of o_proj / down_proj without an elementwise launch.  One launch, no workspace: capturable."""
     if not (a_mx.q4.is_cuda and w_mx.q4.is_cuda):
         raise L.AtomHipError("MX operands must live on the GPU: the MXFP4 GEMM has no CPU fallback")
     if a_mx.k != w_mx.k:
         raise ValueError(f"operands disagree on K: {a_mx.k} vs {w_mx.k}")
     m, n, k = a_mx.rows, w_mx.rows, a_mx.k
-    for o in (a_mx, w_mx):
-        r, s = (o.rows + 15) // 16, k // GROUP_SIZE - 1
-        if (tuple(o.q4.shape), tuple(o.sc.shape), tuple(o.q8.shape)) != ((r, s, 64, 16), (r, s + 1, 64), (r, 2, 64, 16)) or not (
-                o.q4.is_contiguous() and o.sc.is_contiguous() and o.q8.is_contiguous() and o.q4.dtype == o.sc.dtype == o.q8.dtype == torch.uint8):
-            raise ValueError("not a native MX operand (see ops.mx_from_plain)")
+    if not (_mx_native(a_mx) and _mx_native(w_mx)):
+        raise ValueError("not a native MX operand (see ops.mx_from_plain)")
     out = torch.empty((m, n), dtype=torch.float16, device=a_mx.q4.device)
-    st = L.lib().atom_gemm_mxfp4_f16(a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), w_mx.q4.data_ptr(), w_mx.sc.data_ptr(),
-                                     w_mx.q8.data_ptr(), out.data_ptr(), m, n, k, L.current_stream(out.device))
-    L.check(st, "atom_gemm_mxfp4_f16")
+    ptrs = (a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), w_mx.q4.data_ptr(), w_mx.sc.data_ptr(), w_mx.q8.data_ptr())
+    if add is None:
+        st = L.lib().atom_gemm_mxfp4_f16(*ptrs, out.data_ptr(), m, n, k, L.current_stream(out.device))
+        L.check(st, "atom_gemm_mxfp4_f16")
+    else:
+        _require_cuda_half(add, "add")
+        if tuple(add.shape) != (m, n) or not add.is_contiguous():
+            raise ValueError(f"add must be a contiguous fp16 [{m}, {n}], got {tuple(add.shape)}")
+        st = L.lib().atom_gemm_mxfp4_add_f16(*ptrs, add.data_ptr(), out.data_ptr(), m, n, k, L.current_stream(out.device))
+        L.check(st, "atom_gemm_mxfp4_add_f16")
     return out
 
 
@@ -1914,6 +1919,81 @@ def silu_mul_quant_mx(gate: torch.Tensor, up: torch.Tensor) -> MxOperand:
     st = L.lib().atom_silu_mul_quant_mx_f16(gate.data_ptr(), up.data_ptr(), rows, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
                                             L.current_stream(gate.device))
     L.check(st, "atom_silu_mul_quant_mx_f16")
+    return o
+
+
+def fuse_gate_up_mx(gate_mx: MxOperand, up_mx: MxOperand) -> MxOperand:
+    """NEW: the weight operand of ``gate_up_silu_quant_mx``: gate_proj and up_proj (native MX weight operands [F, K]) interleaved in
+    pairs of 16-row fragments, [g0 g1 u0 u1 g2 g3 u2 u3 ...] -- four consecutive fragments hold gate and up of the same 32 output
+    channels, one MX block of the output.  Indexing on the row-tile dimension alone (any device)."""
+    if (gate_mx.rows, gate_mx.k) != (up_mx.rows, up_mx.k) or gate_mx.rows % 32 or not (_mx_native(gate_mx) and _mx_native(up_mx)):
+        raise ValueError("gate and up: native MX weight operands of one shape, rows a multiple of 32")
+    pairs = gate_mx.rows // 32
+
+    def mix(g, u):
+        return torch.stack([g.reshape(pairs, 2, *g.shape[1:]), u.reshape(pairs, 2, *u.shape[1:])], dim=1).reshape(4 * pairs, *g.shape[1:]).contiguous()
+    return MxOperand(mix(gate_mx.q4, up_mx.q4), mix(gate_mx.sc, up_mx.sc), mix(gate_mx.q8, up_mx.q8), 2 * gate_mx.rows, gate_mx.k)
+
+
+def gate_up_silu_quant_mx_route(m: int, f: int, k: int) -> str:
+    """The geometry ``gate_up_silu_quant_mx`` runs a shape on: "decode" (M <= 16), "tile", or None for an unsupported shape."""
+    return {0: None, 1: "decode", 2: "tile"}[L.lib().atom_gemm_mxfp4_silu_mul_quant_route(m, f, k)]
+
+
+def gate_up_silu_quant_mx(a_mx: MxOperand, gu_mx: MxOperand) -> MxOperand:
+    """NEW: gate_proj + up_proj + SiLU x up + MX quantiser in ONE launch: ``a_mx`` [M, K] times the fused weight of
+    ``fuse_gate_up_mx`` (2 F rows) -> the MX activation operand [M, F] of silu(gate) * up that down_proj reads, taken from the FP32
+    sums (no fp16 gate / up in memory).  Capturable."""
+    if not (a_mx.q4.is_cuda and gu_mx.q4.is_cuda):
+        raise L.AtomHipError("MX operands must live on the GPU: the fused gate/up launch has no CPU fallback")
+    if a_mx.k != gu_mx.k or gu_mx.rows % 2 or not (_mx_native(a_mx) and _mx_native(gu_mx)):
+        raise ValueError("a_mx [M, K] and the fused gate/up operand [2 F, K] of ops.fuse_gate_up_mx, both native")
+    m, f, k = a_mx.rows, gu_mx.rows // 2, a_mx.k
+    if L.lib().atom_gemm_mxfp4_silu_mul_quant_route(m, f, k) == 0:
+        raise ValueError(f"gate_up_silu_quant_mx: M = {m}, F = {f}, K = {k} is not a shape of the kernel (F a multiple of 128, >= 256)")
+    o = _mx_alloc(m, f, a_mx.q4.device)
+    st = L.lib().atom_gemm_mxfp4_silu_mul_quant(a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), gu_mx.q4.data_ptr(),
+                                                gu_mx.sc.data_ptr(), gu_mx.q8.data_ptr(), o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
+                                                m, f, k, L.current_stream(a_mx.q4.device))
+    L.check(st, "atom_gemm_mxfp4_silu_mul_quant")
+    return o
+
+
+def _rmsnorm_mx_args(x, weight, reorder_index):
+    _require_cuda_half(x, "x")
+    _require_cuda_half(weight, "weight")
+    m, k = x.shape
+    if tuple(weight.shape) != (k,) or not (x.is_contiguous() and weight.is_contiguous()):
+        raise ValueError(f"x must be a contiguous [M, K] and weight [K], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    if reorder_index is not None and not (reorder_index.is_cuda and reorder_index.dtype == torch.int16 and tuple(reorder_index.shape) == (k,)
+                                          and reorder_index.is_contiguous()):
+        raise TypeError(f"reorder_index must be a contiguous int16 tensor of [{k}] on the GPU")
+    return m, k
+
+
+def rmsnorm_quant_mx(x: torch.Tensor, weight: torch.Tensor, reorder_index: torch.Tensor = None, eps: float = 1e-6) -> MxOperand:
+    """NEW: RMSNorm + channel reorder + MX activation quantiser in one launch: the operand of (x * w) / rms(x), gathered by
+    ``reorder_index``, quantised from the FP32 value (no rounding to half in front of the codes)."""
+    m, k = _rmsnorm_mx_args(x, weight, reorder_index)
+    o = _mx_alloc(m, k, x.device)
+    st = L.lib().atom_rmsnorm_quant_mx_f16(x.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps, o.q4.data_ptr(), o.sc.data_ptr(),
+                                           o.q8.data_ptr(), L.current_stream(x.device))
+    L.check(st, "atom_rmsnorm_quant_mx_f16")
+    return o
+
+
+def add_rmsnorm_quant_mx(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, reorder_index: torch.Tensor = None,
+                         eps: float = 1e-6) -> MxOperand:
+    """NEW: ``residual += x`` (in place: the new residual stream, one fp16 add per element), then ``rmsnorm_quant_mx`` of it, in one
+    launch."""
+    m, k = _rmsnorm_mx_args(x, weight, reorder_index)
+    _require_cuda_half(residual, "residual")
+    if residual.shape != x.shape or not residual.is_contiguous():
+        raise ValueError(f"residual must be a contiguous fp16 {tuple(x.shape)}, got {tuple(residual.shape)}")
+    o = _mx_alloc(m, k, x.device)
+    st = L.lib().atom_add_rmsnorm_quant_mx_f16(x.data_ptr(), residual.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps,
+                                               o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(x.device))
+    L.check(st, "atom_add_rmsnorm_quant_mx_f16")
     return o
 
 

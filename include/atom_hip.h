@@ -1308,6 +1308,48 @@ int atom_moe_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8
 int atom_silu_mul_quant_mx_f16(const void *gate_f16, const void *up_f16, int64_t rows, int64_t K, void *q4, void *sc, void *q8,
                                void *stream);
 
+/*
+ * Dense Llama on MXFP4 (csrc/llama_mxfp4.hip, csrc/gemm_mxfp4.hip): what stands between the MXFP4 GEMMs of a dense
+ * decoder layer, so that no fp16 intermediate of the MLP and no separate quantiser or residual launch remains.
+ *
+ * atom_gemm_mxfp4_silu_mul_quant: gate_proj + up_proj + SiLU x up + MX quantiser in one launch.
+ *   a: a native MX activation operand [M, K].  w: the FUSED gate / up weight operand of 2 F rows: the two projections' native
+ *   operands interleaved in pairs of 16-row fragments along the row-tile dimension, [g0 g1 u0 u1 g2 g3 u2 u3 ...]
+ *   (atom_amd.ops.fuse_gate_up_mx), so that fused fragments 4 q .. 4 q + 3 are gate and up of output channels 32 q .. 32 q + 31.
+ *   out: the native MX activation operand [M, F] the down projection reads (q4 [R][S'][64][16], sc [R][S' + 1][64],
+ *   q8 [R][2][64][16], R = ceil(M / 16), S' = F / 128 - 1).  No fp16 gate or up reaches memory.
+ *   g, u = the FP32 accumulators of atom_gemm_mxfp4_f16's chain for the same geometry (route 1: K steps dealt to 8 waves, each in
+ *   order, the keeper as step S, the 8 partial sums added in wave order; route 2: K steps 0 .. S - 1 in order, then the keeper),
+ *   NOT rounded to half; v = g * rcp(1 + exp2(-g log2 e)) * u in FP32 (atom_silu_mul_quant_mx_f16's expression); v is quantised by the
+ *   block rule above: output channels < F - 128 as E2M1 blocks, the last 128 as E4M3 in the keeper's lane layout.  Rows M ..
+ *   16 ceil(M / 16) - 1 of the last row tile are written as zero blocks (codes 0, scale byte 127).  Both geometries are deterministic;
+ *   they sum in different orders, so a row's codes may differ between M <= 16 and M > 16.
+ *   atom_gemm_mxfp4_silu_mul_quant_route(M, F, K): 0 a shape the entry point refuses, 1 the decode geometry (M <= 16: a workgroup owns
+ *   one output block), 2 the 128 x 128 tile geometry on the fused operand (a workgroup owns 2 output blocks of 128 tokens).
+ *   Shapes: M >= 1, K as above, F a multiple of 128 and >= 256 (<= 2^20).  Errors, before any launch: ATOM_ERR_INVALID_ARG for a null
+ *   pointer, ATOM_ERR_SHAPE, ATOM_ERR_ALIGN for a pointer off 16 bytes.  One launch, no workspace: capturable.
+ *
+ * atom_rmsnorm_quant_mx_f16 / atom_add_rmsnorm_quant_mx_f16: RMSNorm + channel reorder + MX activation quantiser of x fp16 [M, K].
+ *   add form: s = half(x + residual) first (one fp16 add per element), written back to residual_inout as the new residual stream;
+ *   otherwise s = x.  rinv = 1 / sqrt(mean(s^2) + eps) by the fixed-shape FP32 sum of squares over the row in memory order and the
+ *   correctly rounded divide / root of the INT4 RMSNorm quantisers (the reorder index does not enter).  The value of reordered channel c
+ *   is (s[idx[c]] * w[idx[c]]) * rinv, two FP32 products, NOT rounded to half; codes, scale bytes, keeper layout and padding rows as
+ *   atom_reorder_quant_mx_f16.  The row is read from memory once.  Shapes: M >= 1, K a multiple of 128, 256 <= K <= 16384; eps >= 0.
+ *   Errors as above (reorder_index may be null: identity; the add form needs residual_inout).
+ *
+ * atom_gemm_mxfp4_add_f16: atom_gemm_mxfp4_f16 with out = half(acc + float(residual)), acc the FP32 sum, residual fp16 [M, N] (it may
+ *   be `out`).  Same routes, shapes and errors; a null residual is ATOM_ERR_INVALID_ARG.
+ */
+int atom_gemm_mxfp4_silu_mul_quant(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                                   void *out_q4, void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, void *stream);
+int atom_gemm_mxfp4_silu_mul_quant_route(int64_t M, int64_t F, int64_t K);
+int atom_rmsnorm_quant_mx_f16(const void *x_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M, int64_t K, float eps, void *q4,
+                              void *sc, void *q8, void *stream);
+int atom_add_rmsnorm_quant_mx_f16(const void *x_f16, void *residual_inout_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M,
+                                  int64_t K, float eps, void *q4, void *sc, void *q8, void *stream);
+int atom_gemm_mxfp4_add_f16(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                            const void *residual_f16, void *out_f16, int64_t M, int64_t N, int64_t K, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

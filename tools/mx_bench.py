@@ -1,6 +1,7 @@
 """MXFP4 W4A4 against the shipped INT4 / BF6 routes on one GPU (profiles/mxfp4/README.md).
 
   python tools/mx_bench.py [--reps 5] [--iters 50]
+  python tools/mx_bench.py --mlp       the fused gate/up SiLU-quantising launch against gemm_mxfp4 x 2 + silu_mul_quant_mx
 
 Every figure is the median over --reps repetitions of the mean time of --iters replays of a captured graph holding one launch (hot:
 operands stay in L2 / MALL where they fit), the two sides of a comparison alternating inside one repetition; the spread printed beside
@@ -66,14 +67,33 @@ def gemm_pair(M, N, K, dev):
     return (lambda: ops.gemm_mxfp4(a_mx, w_mx)), ref
 
 
+def mlp(args, dev):
+    """Llama-7B MLP shapes: one fused launch against the three launches it replaces, on the same operands"""
+    K, F = 4096, 11008
+    for M in (1, 16, 256, 2048):
+        x, wg = operands(M, F, K, dev)
+        _, wu = operands(M + 1, F, K, dev)
+        a_mx, g_mx, u_mx = ops.reorder_quant_mx(x), ops.quant_weight_mx(wg), ops.quant_weight_mx(wu)
+        gu_mx = ops.fuse_gate_up_mx(g_mx, u_mx)
+        fused = lambda: ops.gate_up_silu_quant_mx(a_mx, gu_mx)                                                          # noqa: E731
+        three = lambda: ops.silu_mul_quant_mx(ops.gemm_mxfp4(a_mx, g_mx), ops.gemm_mxfp4(a_mx, u_mx))                   # noqa: E731
+        (t_f, s_f), (t_3, s_3), (t_f2, _) = time_graphs([graph_of(fused), graph_of(three), graph_of(fused)], args.reps, args.iters)
+        print(json.dumps({"what": "mlp gate/up", "M": M, "F": F, "K": K, "route": ops.gate_up_silu_quant_mx_route(M, F, K),
+                          "fused_us": round(t_f, 2), "fused_spread_us": round(s_f, 2), "fused_again_us": round(t_f2, 2),
+                          "three_launches_us": round(t_3, 2), "three_spread_us": round(s_3, 2), "ratio": round(t_f / t_3, 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--mlp", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mx_bench needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
+    if args.mlp:
+        return mlp(args, dev)
     for M, N, K in [(4096, 4096, 4096), (1, 4096, 4096), (16, 4096, 4096), (256, 4096, 4096)]:
         mx, ref = gemm_pair(M, N, K, dev)
         # the same MX graph twice: the spread of two runs of the same binary beside the difference
