@@ -160,6 +160,12 @@ SIGNATURES = {
     "atom_rmsnorm_quant_mx_f16": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "atom_add_rmsnorm_quant_mx_f16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "atom_gemm_mxfp4_add_f16": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp]),
+    # MXFP6 activations, W4A6 (csrc/gemm_mxfp4.hip, csrc/llama_mxfp4.hip)
+    "atom_reorder_quant_mx6_f16": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "atom_rmsnorm_quant_mx6_f16": (_int, [_vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "atom_add_rmsnorm_quant_mx6_f16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "atom_gemm_mxfp4_a6_f16": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp]),
+    "atom_gemm_mxfp4_a6_silu_mul_quant": (_int, [_vp] * 9 + [_i64, _i64, _i64, _int, _int, _vp]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@
 //   gemm_mxfp4_tile_kernel  128 x 128 tiles, 4 waves of 64 x 64, operands and scale bytes through a 3-stage LDS ring by LDS-DMA
 //   gemm_mxfp4_dec_kernel   M <= 16: one 16-feature tile per workgroup, weight fragments straight into registers, the K steps dealt
 //                           to 8 waves and summed through LDS in wave order
+// Every kernel is templated on the format of the activation's bulk codes: MxE2M1 (W4A4) or MxE2M3 (W4A6, DESIGN.md 4.29: the MXFP6
+// activation in 6 registers per lane against the same E2M1 weight, at the same MFMA rate).
 #include "mx_gemm.h"
 #include "quant_math.h"
 
@@ -42,7 +44,7 @@ __device__ __forceinline__ void mx_store4(const MxGemmParams &p, int64_t off, v4
 // Row `row` of the padded operand (rows >= M are written as zero blocks), every lane 8 channels of a block per trip: lanes 4 b .. 4 b + 3
 // share block b of the trip's 16.  The lane's codes go to its 4 (E2M1) or 8 (E4M3) bytes of the MFMA lane that holds those channels.
 // SILU: the values are silu_mul<false>(x, up) of quant_math.h (x = gate; no reorder: the producer's rows are stored in channel order).
-template <bool SILU>
+template <bool SILU, class AF>
 __global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict__ x, const half_t *__restrict__ up, const int16_t *__restrict__ idx,
                                                        int M, int rows_pad, int K, uint8_t *__restrict__ q4, uint8_t *__restrict__ sc,
                                                        uint8_t *__restrict__ q8) {
@@ -75,20 +77,20 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict_
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = 0.f;
     }
-    mx_quant_store8(v, c0, rt, r, S, q4, sc, q8);
+    mx_quant_store8<AF>(v, c0, rt, r, S, q4, sc, q8);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------- 128 x 128 tiles
 // (ring and K loop: mx_tile_accumulate of mx_gemm.h)
-template <bool ADD>
+template <bool ADD, class AF>
 __global__ __launch_bounds__(256) void gemm_mxfp4_tile_kernel(MxGemmParams p) {
-  __shared__ __attribute__((aligned(16))) char lds[MXT_LDS];
+  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF>::LDS];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int wt0 = blockIdx.x * 8, at0 = blockIdx.y * 8;     // first fragment (16 features / 16 tokens) of the tile
   const int wn = w & 1, wm = w >> 1;
   v4f acc[4][4];
-  mx_tile_accumulate(p.a, p.w, p.S, wt0, at0, lds, acc);
+  mx_tile_accumulate<AF>(p.a, p.w, p.S, wt0, at0, lds, acc);
   // lane l: token l % 16 of activation fragment i, features 4 (l / 16) .. + 3 of weight fragment j
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -106,13 +108,13 @@ __global__ __launch_bounds__(256) void gemm_mxfp4_tile_kernel(MxGemmParams p) {
 // (16 features), wave w = K steps w, w + 8, ... (the keeper counts as step S); the 8 partial tiles are summed in wave order.
 constexpr int MXD_WAVES = 8;
 
-template <bool ADD>
+template <bool ADD, class AF>
 __global__ __launch_bounds__(64 * MXD_WAVES) void gemm_mxfp4_dec_kernel(MxGemmParams p) {
   __shared__ v4f part[MXD_WAVES][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int64_t ct = blockIdx.x;
   v4f acc1[1];
-  mx_dec_accumulate<1, MXD_WAVES>(p.a, p.w, p.S, ct, w, l, acc1);
+  mx_dec_accumulate<AF, 1, MXD_WAVES>(p.a, p.w, p.S, ct, w, l, acc1);
   const v4f acc = acc1[0];
   part[w][l] = acc;
   __syncthreads();
@@ -125,13 +127,13 @@ __global__ __launch_bounds__(64 * MXD_WAVES) void gemm_mxfp4_dec_kernel(MxGemmPa
   }
 }
 
-template <bool SILU>
+template <bool SILU, class AF = MxE2M1>
 int launch_mx_quant(const void *x, const void *up, const int16_t *idx, int64_t rows, int64_t K, void *q4, void *sc, void *q8, void *stream) {
   if (!x || (SILU && !up) || !q4 || !sc || !q8) return ATOM_ERR_INVALID_ARG;
   if (!mx_shape_ok(rows, K)) return ATOM_ERR_SHAPE;
   if (!aligned16(x) || !aligned16(up) || !aligned16(idx) || !aligned16(q4) || !aligned16(sc) || !aligned16(q8)) return ATOM_ERR_ALIGN;
   const int64_t pad = (rows + 15) / 16 * 16;
-  hipLaunchKernelGGL(mx_quant_kernel<SILU>, dim3((unsigned)(pad / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x,
+  hipLaunchKernelGGL((mx_quant_kernel<SILU, AF>), dim3((unsigned)(pad / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x,
                      (const half_t *)up, idx, (int)rows, (int)pad, (int)K, (uint8_t *)q4, (uint8_t *)sc, (uint8_t *)q8);
   return check_launch();
 }
@@ -142,7 +144,7 @@ int launch_mx_quant(const void *x, const void *up, const int16_t *idx, int64_t r
 using namespace atom;
 
 namespace {
-template <bool ADD>
+template <bool ADD, class AF = MxE2M1>
 int launch_mx_gemm(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8, const void *add,
                    void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
   if (!a_q4 || !a_sc || !a_q8 || !w_q4 || !w_sc || !w_q8 || !out_f16 || (ADD && !add)) return ATOM_ERR_INVALID_ARG;
@@ -156,9 +158,9 @@ int launch_mx_gemm(const void *a_q4, const void *a_sc, const void *a_q8, const v
                  (half_t *)out_f16, (const half_t *)add, (int)M, (int)N, (int)(K / 128 - 1)};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (route == 1) {
-    hipLaunchKernelGGL(gemm_mxfp4_dec_kernel<ADD>, dim3((unsigned)(N / 16)), dim3(64 * MXD_WAVES), 0, s, p);
+    hipLaunchKernelGGL((gemm_mxfp4_dec_kernel<ADD, AF>), dim3((unsigned)(N / 16)), dim3(64 * MXD_WAVES), 0, s, p);
   } else {
-    hipLaunchKernelGGL(gemm_mxfp4_tile_kernel<ADD>, dim3((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gemm_mxfp4_tile_kernel<ADD, AF>), dim3((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
   }
   return check_launch();
 }
@@ -198,6 +200,19 @@ int atom_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8, co
 int atom_gemm_mxfp4_add_f16(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
                             const void *residual_f16, void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
   return launch_mx_gemm<true>(a_q4, a_sc, a_q8, w_q4, w_sc, w_q8, residual_f16, out_f16, M, N, K, stream);
+}
+
+// ---- W4A6: the same launches on an MXFP6 (E2M3) activation operand, q6 [R][S][96][16]
+int atom_reorder_quant_mx6_f16(const void *x_f16, const int16_t *reorder_index, int64_t M, int64_t K, void *q6, void *sc, void *q8,
+                               void *stream) {
+  if (K > 32768 && reorder_index) return ATOM_ERR_SHAPE;   // int16 indices
+  return launch_mx_quant<false, MxE2M3>(x_f16, nullptr, reorder_index, M, K, q6, sc, q8, stream);
+}
+
+int atom_gemm_mxfp4_a6_f16(const void *a_q6, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                           const void *add_f16, void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
+  return add_f16 ? launch_mx_gemm<true, MxE2M3>(a_q6, a_sc, a_q8, w_q4, w_sc, w_q8, add_f16, out_f16, M, N, K, stream)
+                 : launch_mx_gemm<false, MxE2M3>(a_q6, a_sc, a_q8, w_q4, w_sc, w_q8, nullptr, out_f16, M, N, K, stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,9 @@
 //       decode (M <= 16) a workgroup owns four consecutive fused fragments (one output block); 8 waves take K steps w, w + 8, ... with
 //                        the weights streamed straight into registers (mx_dec_accumulate<4>), the 8 x 4 partial tiles are summed through
 //                        LDS in wave order by wave 0, which runs the epilogue on the sums.
-//   rmsnorm_quant_mx_kernel<ADD>   RMSNorm (optionally x + residual first, written back) + channel reorder + MX quantiser: one workgroup
+//     Either launch reads an E2M1 or an E2M3 activation (AF) and writes E2M1 or E2M3 bulk blocks (OF): an E2M3 block is
+//     the lane's two 24-bit code quartets gathered the same way and written as the 16-byte head and 8-byte tail of its MFMA lane.
+//   rmsnorm_quant_mx_kernel<ADD, AF>   RMSNorm (optionally x + residual first, written back) + channel reorder + MX quantiser: one workgroup
 //     of 256 per row; the row goes to LDS once while its squares are summed in quant_math.h's fixed shape, the gather reads LDS.
 #include "mx_gemm.h"
 #include "quant_math.h"
@@ -32,7 +34,8 @@ struct MxGuParams {
 // Output block q (channels 32 q .. + 31) of the 16 tokens of output row tile rt.  g0 g1 u0 u1: the sums of fused fragments 4 q .. 4 q + 3;
 // lane l holds token l % 16, block channels 4 (l / 16) .. + 3 (g0, u0) and 16 + 4 (l / 16) .. + 3 (g1, u1).  row_live: the lane's token
 // exists (a padding row is a zero block); store: rt is a tile of the output (wave-uniform); owner: the lane group that writes.
-// Every lane of the wave must be here (exchanges).
+// Every lane of the wave must be here (exchanges).  OF: the format of the output's bulk blocks.
+template <class OF>
 __device__ __forceinline__ void gu_block_store(const v4f &g0, const v4f &g1, const v4f &u0, const v4f &u1, bool row_live, bool store, int owner,
                                                int rt, int q, int l, const MxGuParams &p) {
   float v[8];
@@ -50,18 +53,39 @@ __device__ __forceinline__ void gu_block_store(const v4f &g0, const v4f &g1, con
   const bool mine = store && (l >> 4) == owner;
   const int64_t scrow = (int64_t)rt * (Sp + 1);
   if (step < Sp) {                                           // (uniform over the workgroup: F - 128 is a multiple of 128)
-    const int sb = mx_scale_byte<MxE2M1>(amax);
-    const float inv = mx_inv_scale(sb);
-    unsigned pk = 0;                                         // low half: the lane's 4 codes of g0 / u0, high half: of g1 / u1
+    if constexpr (std::is_same_v<OF, MxE2M3>) {
+      const int sb = mx_scale_byte<MxE2M3>(amax);
+      const float inv = mx_inv_scale(sb);
+      unsigned pa = 0, pb = 0;                               // 24 bits each: block channels 4 g .. 4 g + 3 and 16 + 4 g .. + 3
 #pragma unroll
-    for (int i = 0; i < 8; ++i) pk |= mx_code<MxE2M1>(v[i], inv) << (4 * i);
-    const unsigned p0 = __shfl(pk, r), p1 = __shfl(pk, r + 16), p2 = __shfl(pk, r + 32), p3 = __shfl(pk, r + 48);
-    if (mine) {
-      // byte c / 2 of the block's 16 holds channels c, c + 1: lane group g's halves are bytes 2 g, 2 g + 1 and 8 + 2 g, 9 + 2 g
-      const v4u d = {(p0 & 0xffffu) | (p1 << 16), (p2 & 0xffffu) | (p3 << 16), (p0 >> 16) | (p1 & 0xffff0000u), (p2 >> 16) | (p3 & 0xffff0000u)};
-      const int ml = r + 16 * (q & 3);
-      *reinterpret_cast<v4u *>(p.q4 + (((int64_t)rt * Sp + step) * 64 + ml) * 16) = d;
-      p.sc[(scrow + step) * 64 + ml] = (uint8_t)sb;
+      for (int e = 0; e < 4; ++e) {
+        pa |= mx_code<MxE2M3>(v[e], inv) << (6 * e);
+        pb |= mx_code<MxE2M3>(v[4 + e], inv) << (6 * e);
+      }
+      const unsigned a0 = __shfl(pa, r), a1 = __shfl(pa, r + 16), a2 = __shfl(pa, r + 32), a3 = __shfl(pa, r + 48);
+      const unsigned b0 = __shfl(pb, r), b1 = __shfl(pb, r + 16), b2 = __shfl(pb, r + 32), b3 = __shfl(pb, r + 48);
+      if (mine) {
+        // the block's 192 bits = the four groups' low quartets (channels 0 .. 15), then their high quartets: head 16 bytes, tail 8
+        const int ml = r + 16 * (q & 3);
+        uint8_t *o = p.q4 + ((int64_t)rt * Sp + step) * 1536;
+        *reinterpret_cast<v4u *>(o + ml * 16) = v4u{a0 | (a1 << 24), (a1 >> 8) | (a2 << 16), (a2 >> 16) | (a3 << 8), b0 | (b1 << 24)};
+        *reinterpret_cast<v2u *>(o + 1024 + ml * 8) = v2u{(b1 >> 8) | (b2 << 16), (b2 >> 16) | (b3 << 8)};
+        p.sc[(scrow + step) * 64 + ml] = (uint8_t)sb;
+      }
+    } else {
+      const int sb = mx_scale_byte<MxE2M1>(amax);
+      const float inv = mx_inv_scale(sb);
+      unsigned pk = 0;                                       // low half: codes of g0 / u0, high half: of g1 / u1
+#pragma unroll
+      for (int i = 0; i < 8; ++i) pk |= mx_code<MxE2M1>(v[i], inv) << (4 * i);
+      const unsigned p0 = __shfl(pk, r), p1 = __shfl(pk, r + 16), p2 = __shfl(pk, r + 32), p3 = __shfl(pk, r + 48);
+      if (mine) {
+        // byte c / 2 of the block's 16 holds channels c, c + 1: lane group g's halves are bytes 2 g, 2 g + 1 and 8 + 2 g, 9 + 2 g
+        const v4u d = {(p0 & 0xffffu) | (p1 << 16), (p2 & 0xffffu) | (p3 << 16), (p0 >> 16) | (p1 & 0xffff0000u), (p2 >> 16) | (p3 & 0xffff0000u)};
+        const int ml = r + 16 * (q & 3);
+        *reinterpret_cast<v4u *>(p.q4 + (((int64_t)rt * Sp + step) * 64 + ml) * 16) = d;
+        p.sc[(scrow + step) * 64 + ml] = (uint8_t)sb;
+      }
     }
   } else {
     const int sb = mx_scale_byte<MxE4M3>(amax);
@@ -84,28 +108,30 @@ __device__ __forceinline__ void gu_block_store(const v4f &g0, const v4f &g1, con
   }
 }
 
+template <class AF, class OF>
 __global__ __launch_bounds__(256) void gu_mxfp4_tile_kernel(MxGuParams p) {
-  __shared__ __attribute__((aligned(16))) char lds[MXT_LDS];
+  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF>::LDS];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int wt0 = blockIdx.x * 8, at0 = blockIdx.y * 8;
   v4f acc[4][4];
-  mx_tile_accumulate(p.a, p.w, p.S, wt0, at0, lds, acc);
+  mx_tile_accumulate<AF>(p.a, p.w, p.S, wt0, at0, lds, acc);
   const int q = blockIdx.x * 2 + (w & 1);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int rt = at0 + (w >> 1) * 4 + i;
-    gu_block_store(acc[i][0], acc[i][1], acc[i][2], acc[i][3], rt * 16 + (l & 15) < p.M, rt < p.a.tiles, i, rt, q, l, p);
+    gu_block_store<OF>(acc[i][0], acc[i][1], acc[i][2], acc[i][3], rt * 16 + (l & 15) < p.M, rt < p.a.tiles, i, rt, q, l, p);
   }
 }
 
 constexpr int GUD_WAVES = 8;
 
+template <class AF, class OF>
 __global__ __launch_bounds__(64 * GUD_WAVES) void gu_mxfp4_dec_kernel(MxGuParams p) {
   __shared__ v4f part[GUD_WAVES][4][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int q = blockIdx.x;
   v4f acc[4];
-  mx_dec_accumulate<4, GUD_WAVES>(p.a, p.w, p.S, (int64_t)q * 4, w, l, acc);
+  mx_dec_accumulate<AF, 4, GUD_WAVES>(p.a, p.w, p.S, (int64_t)q * 4, w, l, acc);
 #pragma unroll
   for (int j = 0; j < 4; ++j) part[w][j][l] = acc[j];
   __syncthreads();
@@ -117,7 +143,7 @@ __global__ __launch_bounds__(64 * GUD_WAVES) void gu_mxfp4_dec_kernel(MxGuParams
 #pragma unroll
       for (int i = 1; i < GUD_WAVES; ++i) s[j] += part[i][j][l];
     }
-    gu_block_store(s[0], s[1], s[2], s[3], (l & 15) < p.M, true, 0, 0, q, l, p);
+    gu_block_store<OF>(s[0], s[1], s[2], s[3], (l & 15) < p.M, true, 0, 0, q, l, p);
   }
 }
 
@@ -128,7 +154,7 @@ __global__ __launch_bounds__(64 * GUD_WAVES) void gu_mxfp4_dec_kernel(MxGuParams
 // FP32 throughout, by mx_quant_kernel's lines (mx_quant_store8).
 constexpr int RQ_MAX_K = 16384;                              // the row in LDS: 32 KiB
 
-template <bool ADD>
+template <bool ADD, class AF>
 __global__ __launch_bounds__(256) void rmsnorm_quant_mx_kernel(const half_t *__restrict__ x, half_t *__restrict__ res, const half_t *__restrict__ wgt,
                                                                const int16_t *__restrict__ idx, int M, int K, float eps, uint8_t *__restrict__ q4,
                                                                uint8_t *__restrict__ sc, uint8_t *__restrict__ q8) {
@@ -173,11 +199,11 @@ __global__ __launch_bounds__(256) void rmsnorm_quant_mx_kernel(const half_t *__r
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = 0.f;
     }
-    mx_quant_store8(v, c0, row >> 4, row & 15, S, q4, sc, q8);
+    mx_quant_store8<AF>(v, c0, row >> 4, row & 15, S, q4, sc, q8);
   }
 }
 
-template <bool ADD>
+template <bool ADD, class AF = MxE2M1>
 int launch_rmsnorm_quant_mx(const void *x, void *res, const void *wgt, const int16_t *idx, int64_t M, int64_t K, float eps, void *q4, void *sc,
                             void *q8, void *stream) {
   if (!x || (ADD && !res) || !wgt || !q4 || !sc || !q8) return ATOM_ERR_INVALID_ARG;
@@ -185,7 +211,7 @@ int launch_rmsnorm_quant_mx(const void *x, void *res, const void *wgt, const int
   if (!aligned16(x) || !aligned16(res) || !aligned16(wgt) || !aligned16(idx) || !aligned16(q4) || !aligned16(sc) || !aligned16(q8))
     return ATOM_ERR_ALIGN;
   const int64_t pad = (M + 15) / 16 * 16;
-  hipLaunchKernelGGL(rmsnorm_quant_mx_kernel<ADD>, dim3((unsigned)pad), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x,
+  hipLaunchKernelGGL((rmsnorm_quant_mx_kernel<ADD, AF>), dim3((unsigned)pad), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const half_t *)x,
                      (half_t *)res, (const half_t *)wgt, idx, (int)M, (int)K, eps, (uint8_t *)q4, (uint8_t *)sc, (uint8_t *)q8);
   return check_launch();
 }
@@ -194,6 +220,29 @@ int launch_rmsnorm_quant_mx(const void *x, void *res, const void *wgt, const int
 }  // namespace atom
 
 using namespace atom;
+
+namespace {
+template <class AF, class OF>
+int launch_gu(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8, void *out_q4, void *out_sc,
+              void *out_q8, int64_t M, int64_t F, int64_t K, void *stream) {
+  if (!a_q4 || !a_sc || !a_q8 || !w_q4 || !w_sc || !w_q8 || !out_q4 || !out_sc || !out_q8) return ATOM_ERR_INVALID_ARG;
+  const int route = atom_gemm_mxfp4_silu_mul_quant_route(M, F, K);
+  if (!route) return ATOM_ERR_SHAPE;
+  if (!aligned16(a_q4) || !aligned16(a_sc) || !aligned16(a_q8) || !aligned16(w_q4) || !aligned16(w_sc) || !aligned16(w_q8) ||
+      !aligned16(out_q4) || !aligned16(out_sc) || !aligned16(out_q8))
+    return ATOM_ERR_ALIGN;
+  MxGuParams p{{(const uint8_t *)a_q4, (const uint8_t *)a_sc, (const uint8_t *)a_q8, (int)((M + 15) / 16)},
+               {(const uint8_t *)w_q4, (const uint8_t *)w_sc, (const uint8_t *)w_q8, (int)(F / 8)},
+               (uint8_t *)out_q4, (uint8_t *)out_sc, (uint8_t *)out_q8, (int)M, (int)(K / 128 - 1), (int)(F / 128 - 1)};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (route == 1) {
+    hipLaunchKernelGGL((gu_mxfp4_dec_kernel<AF, OF>), dim3((unsigned)(F / 32)), dim3(64 * GUD_WAVES), 0, s, p);
+  } else {
+    hipLaunchKernelGGL((gu_mxfp4_tile_kernel<AF, OF>), dim3((unsigned)(F / 64), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
+  }
+  return check_launch();
+}
+}  // namespace
 
 extern "C" {
 
@@ -206,22 +255,19 @@ int atom_gemm_mxfp4_silu_mul_quant_route(int64_t M, int64_t F, int64_t K) {
 
 int atom_gemm_mxfp4_silu_mul_quant(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
                                    void *out_q4, void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, void *stream) {
-  if (!a_q4 || !a_sc || !a_q8 || !w_q4 || !w_sc || !w_q8 || !out_q4 || !out_sc || !out_q8) return ATOM_ERR_INVALID_ARG;
-  const int route = atom_gemm_mxfp4_silu_mul_quant_route(M, F, K);
-  if (!route) return ATOM_ERR_SHAPE;
-  if (!aligned16(a_q4) || !aligned16(a_sc) || !aligned16(a_q8) || !aligned16(w_q4) || !aligned16(w_sc) || !aligned16(w_q8) ||
-      !aligned16(out_q4) || !aligned16(out_sc) || !aligned16(out_q8))
-    return ATOM_ERR_ALIGN;
-  MxGuParams p{{(const uint8_t *)a_q4, (const uint8_t *)a_sc, (const uint8_t *)a_q8, (int)((M + 15) / 16)},
-               {(const uint8_t *)w_q4, (const uint8_t *)w_sc, (const uint8_t *)w_q8, (int)(F / 8)},
-               (uint8_t *)out_q4, (uint8_t *)out_sc, (uint8_t *)out_q8, (int)M, (int)(K / 128 - 1), (int)(F / 128 - 1)};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (route == 1) {
-    hipLaunchKernelGGL(gu_mxfp4_dec_kernel, dim3((unsigned)(F / 32)), dim3(64 * GUD_WAVES), 0, s, p);
-  } else {
-    hipLaunchKernelGGL(gu_mxfp4_tile_kernel, dim3((unsigned)(F / 64), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
-  }
-  return check_launch();
+  return launch_gu<MxE2M1, MxE2M1>(a_q4, a_sc, a_q8, w_q4, w_sc, w_q8, out_q4, out_sc, out_q8, M, F, K, stream);
+}
+
+// act_bits / out_bits: 4 (E2M1 bulk codes, [R][S][64][16]) or 6 (E2M3, [R][S][96][16]) for the activation read and the operand written
+int atom_gemm_mxfp4_a6_silu_mul_quant(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                                      void *out_q, void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, int act_bits, int out_bits,
+                                      void *stream) {
+  if ((act_bits != 4 && act_bits != 6) || (out_bits != 4 && out_bits != 6)) return ATOM_ERR_INVALID_ARG;
+  if (act_bits == 6)
+    return out_bits == 6 ? launch_gu<MxE2M3, MxE2M3>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream)
+                         : launch_gu<MxE2M3, MxE2M1>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
+  return out_bits == 6 ? launch_gu<MxE2M1, MxE2M3>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream)
+                       : launch_gu<MxE2M1, MxE2M1>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
 }
 
 int atom_rmsnorm_quant_mx_f16(const void *x_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M, int64_t K, float eps, void *q4,
@@ -232,6 +278,16 @@ int atom_rmsnorm_quant_mx_f16(const void *x_f16, const void *weight_f16, const i
 int atom_add_rmsnorm_quant_mx_f16(const void *x_f16, void *residual_inout_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M,
                                   int64_t K, float eps, void *q4, void *sc, void *q8, void *stream) {
   return launch_rmsnorm_quant_mx<true>(x_f16, residual_inout_f16, weight_f16, reorder_index, M, K, eps, q4, sc, q8, stream);
+}
+
+int atom_rmsnorm_quant_mx6_f16(const void *x_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M, int64_t K, float eps, void *q6,
+                               void *sc, void *q8, void *stream) {
+  return launch_rmsnorm_quant_mx<false, MxE2M3>(x_f16, nullptr, weight_f16, reorder_index, M, K, eps, q6, sc, q8, stream);
+}
+
+int atom_add_rmsnorm_quant_mx6_f16(const void *x_f16, void *residual_inout_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M,
+                                   int64_t K, float eps, void *q6, void *sc, void *q8, void *stream) {
+  return launch_rmsnorm_quant_mx<true, MxE2M3>(x_f16, residual_inout_f16, weight_f16, reorder_index, M, K, eps, q6, sc, q8, stream);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // these plus its own value source or epilogue; the arithmetic and the accumulation chain exist once.
 #pragma once
 #include "mx_math.h"
+#include <type_traits>
 
 namespace atom {
 
@@ -13,7 +14,15 @@ struct MxOperand {
   int tiles;   // row tiles of 16
 };
 
-constexpr int FMT_E2M1 = 4, FMT_E4M3 = 0;
+constexpr int FMT_E2M1 = 4, FMT_E4M3 = 0, FMT_E2M3 = 2;   // the instruction's cbsz / blgp codes
+
+// The bulk-code fragment (16 rows x one K step) of an activation operand by format.  E2M1: [64 lanes][16 bytes].  E2M3: a lane's 32
+// codes are 24 bytes = 6 registers, stored as a head [64 lanes][16 bytes] (registers 0 .. 3) and a tail [64 lanes][8 bytes] (registers
+// 4, 5): 1024 + 512 bytes, every access a whole 16- or 8-byte piece at its natural alignment.  (A 12-byte LDS-DMA piece lands at a
+// 16-byte lane stride -- measured, DESIGN.md 4.29 -- so planes of 12 bytes would cost 2 KiB of LDS per fragment.)
+template <class AF> struct MxAct;
+template <> struct MxAct<MxE2M1> { static constexpr int FMT = FMT_E2M1, FRAG = 1024, TAIL = 0; };
+template <> struct MxAct<MxE2M3> { static constexpr int FMT = FMT_E2M3, FRAG = 1536, TAIL = 512; };
 
 inline bool mx_shape_ok(int64_t rows, int64_t K) { return rows >= 1 && rows < (1ll << 31) - 16 && K >= 256 && (K % 128) == 0 && K <= (1 << 20); }
 
@@ -21,6 +30,9 @@ inline bool mx_shape_ok(int64_t rows, int64_t K) { return rows >= 1 && rows < (1
 // The 8 values of channels c0 .. c0 + 7 of row 16 rt + r (S = the operand's FP4 steps): lanes 4 b .. 4 b + 3 of the wave hold block b of
 // the trip, so the block maximum is two exchanges; the lane's codes go to its 4 (E2M1) or 8 (E4M3) bytes of the MFMA lane that holds
 // those channels.  Every lane of such a group of 4 must be here.
+// AF = MxE2M3: the lane's 8 bulk codes are bits 48 j .. 48 j + 47 of the block's 192; after three exchanges lane 0 of the group
+// writes the head's 16 bytes and lane 2 the tail's 8.
+template <class AF = MxE2M1>
 __device__ __forceinline__ void mx_quant_store8(const float (&v)[8], int c0, int rt, int r, int S, uint8_t *__restrict__ q4,
                                                 uint8_t *__restrict__ sc, uint8_t *__restrict__ q8) {
   float amax = 0.f;
@@ -31,12 +43,27 @@ __device__ __forceinline__ void mx_quant_store8(const float (&v)[8], int c0, int
   const int kb = c0 >> 5, j = (c0 >> 3) & 3;          // block of the row, the lane's quarter of it
   const int step = kb >> 2, ml = r + 16 * (kb & 3);   // K step, MFMA lane
   if (step < S) {
-    const int sb = mx_scale_byte<MxE2M1>(amax);
+    const int sb = mx_scale_byte<AF>(amax);
     const float inv = mx_inv_scale(sb);
-    unsigned pk = 0;
+    if constexpr (std::is_same_v<AF, MxE2M3>) {
+      unsigned lo = 0, hi = 0;                                // codes 0 .. 4 and the low 2 bits of code 5; the rest of 5, codes 6, 7
 #pragma unroll
-    for (int i = 0; i < 8; ++i) pk |= mx_code<MxE2M1>(v[i], inv) << (4 * i);
-    *reinterpret_cast<unsigned *>(q4 + (((int64_t)rt * S + step) * 64 + ml) * 16 + 4 * j) = pk;
+      for (int i = 0; i < 8; ++i) {
+        const unsigned c = mx_code<MxE2M3>(v[i], inv);
+        if (6 * i < 32) lo |= c << (6 * i);
+        if (6 * i + 6 > 32) hi |= 6 * i >= 32 ? c << (6 * i - 32) : c >> (32 - 6 * i);
+      }
+      const unsigned olo = __shfl_xor(lo, 1), ohi = __shfl_xor(hi, 1), lo2 = __shfl_xor(lo, 2);
+      uint8_t *frag = q4 + ((int64_t)rt * S + step) * 1536;
+      const unsigned mid = hi | (olo << 16), top = (olo >> 16) | (ohi << 16);   // bits 32 .. 95 of the lane pair's 96
+      if (j == 0) *reinterpret_cast<v4u *>(frag + ml * 16) = v4u{lo, mid, top, lo2};
+      if (j == 2) *reinterpret_cast<v2u *>(frag + 1024 + ml * 8) = v2u{mid, top};
+    } else {
+      unsigned pk = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) pk |= mx_code<MxE2M1>(v[i], inv) << (4 * i);
+      *reinterpret_cast<unsigned *>(q4 + (((int64_t)rt * S + step) * 64 + ml) * 16 + 4 * j) = pk;
+    }
     if (j == 0) sc[((int64_t)rt * (S + 1) + step) * 64 + ml] = (uint8_t)sb;
   } else {
     const int sb = mx_scale_byte<MxE4M3>(amax);
@@ -53,11 +80,20 @@ __device__ __forceinline__ void mx_quant_store8(const float (&v)[8], int c0, int
 }
 
 // ------------------------------------------------------------------------------------------------------------- 128 x 128 tiles
-// A ring slot: 8 weight fragments, 8 activation fragments (1 KiB each), their scale bytes (8 x 64 + 8 x 64).  A stage is one FP4 K step
-// or one half of the keeper step (stages S and S + 1, consumed together); every wave requests 5 pieces of every stage (fragments w and
-// w + 4 of either operand with 16 bytes per lane, a quarter of the scale bytes with 4), so the waits count stages.
-constexpr int MXT_NS = 3, MXT_FRAG = 1024, MXT_A = 8 * MXT_FRAG, MXT_SC = 16 * MXT_FRAG, MXT_STAGE = MXT_SC + 1024, MXT_PPW = 5;
-constexpr int MXT_LDS = MXT_NS * MXT_STAGE;
+// A ring slot: 8 weight fragments (1 KiB each), 8 activation fragments (MxAct<AF>::FRAG each), their scale bytes (8 x 64 + 8 x 64).  A
+// stage is one bulk K step or one half of the keeper step (stages S and S + 1, consumed together; their activation fragments are
+// 1 KiB whatever AF is).  The activation region is the 8 fragments' first KiB at 1 KiB strides, then (E2M3) their 512-byte tails in
+// the order 0 4 1 5 2 6 3 7.  Every wave requests PPW pieces of a bulk stage -- the first KiB of fragments w and w + 4 of either
+// operand with 16 bytes per lane, (E2M3) the tails of activation fragments w and w + 4 as ONE 16-byte piece (lanes 0 .. 31 / 32 .. 63:
+// they are neighbours in the tail order), a quarter of the scale bytes with 4 -- and PPW8 = 5 of a keeper stage; the waits count stages.
+// E2M1: 17 KiB per stage, 51 KiB per workgroup, 3 workgroups per CU.  E2M3: 21 KiB, 63 KiB, 2 workgroups per CU (three would need
+// 189 KiB of the CU's 160; a 2-stage ring would fit three but cannot keep a stage in flight while one is read).
+constexpr int MXT_NS = 3, MXT_FRAG = 1024, MXT_A = 8 * MXT_FRAG;
+template <class AF>
+struct MxRing {
+  static constexpr int SC = MXT_A + 8 * MxAct<AF>::FRAG, STAGE = SC + 1024, LDS = MXT_NS * STAGE;
+  static constexpr int PPW = MxAct<AF>::TAIL ? 6 : 5, PPW8 = 5;
+};
 
 __device__ __forceinline__ v8i_t mx_frag4(const char *p) {
   const v4i f = *reinterpret_cast<const v4i *>(p);
@@ -67,13 +103,28 @@ __device__ __forceinline__ v8i_t mx_frag8(const char *p0, const char *p1) {
   const v4i f = *reinterpret_cast<const v4i *>(p0), g = *reinterpret_cast<const v4i *>(p1);
   return v8i_t{f.x, f.y, f.z, f.w, g.x, g.y, g.z, g.w};
 }
+// a lane's registers of an activation fragment (LDS or memory): its 16 bytes of the head (at head + 16 l) and, E2M3, its 8 of the tail
+// (at tail + 8 l)
+template <class AF>
+__device__ __forceinline__ v8i_t mx_frag_act(const char *head_l, const char *tail_l) {
+  if constexpr (std::is_same_v<AF, MxE2M3>) {
+    const v4i a = *reinterpret_cast<const v4i *>(head_l);
+    const v2u b = *reinterpret_cast<const v2u *>(tail_l);
+    return v8i_t{a.x, a.y, a.z, a.w, (int)b.x, (int)b.y, 0, 0};
+  } else {
+    return mx_frag4(head_l);
+  }
+}
 
 // The tile's sums: weight fragments wt0 .. wt0 + 7 times activation fragments at0 .. at0 + 7, 4 waves of 64 x 64 (wave w: features
 // 64 (w & 1) .., tokens 64 (w >> 1) ..).  acc[i][j], lane l: token l % 16 of the wave's activation fragment i, features 4 (l / 16) .. + 3
-// of its weight fragment j.  Every element is one chain: K steps 0 .. S - 1 in order, then the keeper.  `lds`: MXT_LDS bytes, 16-aligned.
+// of its weight fragment j.  Every element is one chain: K steps 0 .. S - 1 in order, then the keeper.  `lds`: MxRing<AF>::LDS bytes,
+// 16-aligned.  AF: the format of the activation's bulk codes (the weight's are E2M1).
+template <class AF>
 __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const MxOperand &pw, int S, int wt0, int at0, char *lds, v4f (&acc)[4][4]) {
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int T = S + 1;
+  constexpr int AFRAG = MxAct<AF>::FRAG, MXT_SC = MxRing<AF>::SC, MXT_STAGE = MxRing<AF>::STAGE, PPW = MxRing<AF>::PPW, PPW8 = MxRing<AF>::PPW8;
   const unsigned lds0 = lds_addr(lds);
   // a tile may hang over the operand's last row tile: the fragments beyond are read from the last one and their results never stored
   const int wf0 = min(wt0 + w, pw.tiles - 1), wf1 = min(wt0 + w + 4, pw.tiles - 1);
@@ -90,8 +141,15 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
     const uint8_t *wb = k8 ? pw.q8 : pw.q4, *ab = k8 ? pa.q8 : pa.q4;
     lds_dma_at<16>(wb + ((int64_t)wf0 * per + at) * MXT_FRAG + l * 16, dst + w * MXT_FRAG);
     lds_dma_at<16>(wb + ((int64_t)wf1 * per + at) * MXT_FRAG + l * 16, dst + (w + 4) * MXT_FRAG);
-    lds_dma_at<16>(ab + ((int64_t)af0 * per + at) * MXT_FRAG + l * 16, dst + MXT_A + w * MXT_FRAG);
-    lds_dma_at<16>(ab + ((int64_t)af1 * per + at) * MXT_FRAG + l * 16, dst + MXT_A + (w + 4) * MXT_FRAG);
+    if (std::is_same_v<AF, MxE2M3> && !k8) {
+      const uint8_t *a0 = ab + ((int64_t)af0 * per + at) * AFRAG, *a1 = ab + ((int64_t)af1 * per + at) * AFRAG;
+      lds_dma_at<16>(a0 + l * 16, dst + MXT_A + w * MXT_FRAG);
+      lds_dma_at<16>(a1 + l * 16, dst + MXT_A + (w + 4) * MXT_FRAG);
+      lds_dma_at<16>((l < 32 ? a0 : a1) + MXT_FRAG + (l & 31) * 16, dst + MXT_A + 8 * MXT_FRAG + w * 1024);   // tails 2 w, 2 w + 1
+    } else {
+      lds_dma_at<16>(ab + ((int64_t)af0 * per + at) * MXT_FRAG + l * 16, dst + MXT_A + w * MXT_FRAG);
+      lds_dma_at<16>(ab + ((int64_t)af1 * per + at) * MXT_FRAG + l * 16, dst + MXT_A + (w + 4) * MXT_FRAG);
+    }
     lds_dma_at<4>(ssrc + min(st, S) * 64, dst + MXT_SC + w * 256);
   };
 
@@ -104,8 +162,10 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
   issue(0);
   issue(1);                                                  // S + 2 >= 3 stages
   for (int st = 0; st < S; ++st) {
-    // stage st has landed (one younger stage may be in flight), this wave's reads of the slot about to be refilled are done
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(MXT_PPW) : "memory");
+    // stage st has landed (one younger stage may be in flight: stage st + 1, a keeper half when st = S - 1), this wave's reads of
+    // the slot about to be refilled are done
+    if (PPW == PPW8 || st + 1 < S) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PPW) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PPW8) : "memory");
     __builtin_amdgcn_s_barrier();
     issue(st + 2);                                           // st + 2 <= S + 1: always a stage
     const char *slot = lds + (st % MXT_NS) * MXT_STAGE;
@@ -113,7 +173,7 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
     int sa[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      fa[i] = mx_frag4(slot + MXT_A + (wm * 4 + i) * MXT_FRAG + l * 16);
+      fa[i] = mx_frag_act<AF>(slot + MXT_A + (wm * 4 + i) * MXT_FRAG + l * 16, slot + MXT_A + 8 * MXT_FRAG + (2 * i + wm) * 512 + l * 8);
       sa[i] = *reinterpret_cast<const uint8_t *>(slot + MXT_SC + 512 + (wm * 4 + i) * 64 + l);
     }
 #pragma unroll
@@ -122,7 +182,7 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
       const int sw = *reinterpret_cast<const uint8_t *>(slot + MXT_SC + (wn * 4 + j) * 64 + l);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fa[i], acc[i][j], FMT_E2M1, FMT_E2M1, 0, sw, 0, sa[i]);
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fa[i], acc[i][j], FMT_E2M1, MxAct<AF>::FMT, 0, sw, 0, sa[i]);
     }
   }
   // the keeper: both halves have been requested; MXFP8 fragments are 32 bytes per lane, 16 from either slot
@@ -152,23 +212,25 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
 
 // One K-step share of the decode geometry (M <= 16: a single activation fragment per step, the weight read once): the sums of the NF
 // consecutive weight fragments from ct0 on, over this wave's K steps w, w + WAVES, ... (the keeper counts as step S), weights straight
-// into registers, non-temporal.  The caller sums the waves' tiles in wave order.
-template <int NF, int WAVES>
+// into registers, non-temporal.  The caller sums the waves' tiles in wave order.  AF: the format of the activation's bulk codes; its
+// fragment is 4 or 6 registers per lane, loaded straight from memory.
+template <class AF, int NF, int WAVES>
 __device__ __forceinline__ void mx_dec_accumulate(const MxOperand &pa, const MxOperand &pw, int S, int64_t ct0, int w, int l, v4f (&acc)[NF]) {
   const int T = S + 1;
   const uint8_t *wq = pw.q4 + ct0 * S * 1024 + l * 16, *wsc = pw.sc + ct0 * T * 64 + l;
-  const uint8_t *aq = pa.q4 + l * 16, *asc = pa.sc + l;
+  const uint8_t *aq = pa.q4 + l * 16, *at = pa.q4 + 1024 + l * 8, *asc = pa.sc + l;
 #pragma unroll
   for (int j = 0; j < NF; ++j) acc[j] = v4f{0.f, 0.f, 0.f, 0.f};
   for (int st = w; st < S; st += WAVES) {
-    const v4i fa = *reinterpret_cast<const v4i *>(aq + (int64_t)st * 1024);
+    const int64_t ao = (int64_t)st * MxAct<AF>::FRAG;
+    const v8i_t fa = mx_frag_act<AF>(reinterpret_cast<const char *>(aq) + ao, reinterpret_cast<const char *>(at) + ao);
     const int sa = asc[st * 64];
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
       const v4i fw = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(wq + ((int64_t)j * S + st) * 1024));
       const int sw = wsc[(j * T + st) * 64];
-      acc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(v8i_t{fw.x, fw.y, fw.z, fw.w, 0, 0, 0, 0}, v8i_t{fa.x, fa.y, fa.z, fa.w, 0, 0, 0, 0},
-                                                                acc[j], FMT_E2M1, FMT_E2M1, 0, sw, 0, sa);
+      acc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(v8i_t{fw.x, fw.y, fw.z, fw.w, 0, 0, 0, 0}, fa, acc[j], FMT_E2M1, MxAct<AF>::FMT, 0, sw,
+                                                                0, sa);
     }
   }
   if (w == S % WAVES) {

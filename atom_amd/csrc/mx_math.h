@@ -8,6 +8,7 @@ namespace atom {
 // element formats: mantissa bits, exponent bias, largest finite code, emax = exponent of the largest finite value
 struct MxE2M1 { static constexpr int MB = 1, BIAS = 1, MAXC = 7, EMAX = 2, SIGN = 8; };        // 0 .. 6
 struct MxE4M3 { static constexpr int MB = 3, BIAS = 7, MAXC = 0x7E, EMAX = 8, SIGN = 0x80; };   // 0 .. 448 (0x7F is NaN)
+struct MxE2M3 { static constexpr int MB = 3, BIAS = 1, MAXC = 31, EMAX = 2, SIGN = 0x20; };     // 0 .. 7.5 (the MXFP6 activation)
 
 // E8M0 scale byte of a block whose absolute maximum is amax (finite, from fp16 values: a normal FP32 number or 0)
 template <class F>

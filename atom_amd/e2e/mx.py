@@ -8,10 +8,14 @@ from .. import ops
 
 
 class LinearMxfp4(nn.Module):
-    """``forward(x_fp16, reorder_index)`` = quantise the reordered activation to MX, then the MXFP4 GEMM against the MX weight."""
+    """``forward(x_fp16, reorder_index)`` = quantise the reordered activation to MX, then the MXFP4 GEMM against the MX weight.
+    ``act_format``: "mxfp4" (W4A4) or "mxfp6" (W4A6: E2M3 activations, same weight)."""
 
-    def __init__(self, in_features, out_features):
+    def __init__(self, in_features, out_features, act_format="mxfp4"):
         super().__init__()
+        if act_format not in ("mxfp4", "mxfp6"):
+            raise ValueError(f"act_format must be \"mxfp4\" or \"mxfp6\", got {act_format!r}")
+        self.act_format = act_format
         if in_features % 128 or in_features < 256 or out_features % 64 or out_features < 64:
             raise ValueError("LinearMxfp4: in_features a multiple of 128 (>= 256), out_features a multiple of 64")
         self.in_features, self.out_features = in_features, out_features
@@ -34,7 +38,7 @@ class LinearMxfp4(nn.Module):
 
     def forward(self, x, reorder_index=None):
         lead = x.shape[:-1]
-        y = ops.gemm_mxfp4(ops.reorder_quant_mx(x.reshape(-1, self.in_features).contiguous(), reorder_index), self.weight_mx())
+        y = ops.gemm_mxfp4(ops.reorder_quant_mx(x.reshape(-1, self.in_features).contiguous(), reorder_index, self.act_format), self.weight_mx())
         return y.view(*lead, self.out_features)
 
 
@@ -55,6 +59,7 @@ class LlamaAttentionMxfp4(nn.Module):
         super().__init__()
         from .rope import rope_init
         self.config, self.layer_idx = config, layer_idx
+        self.act_format = getattr(config, "activation_format", "mxfp4")
         self.hidden_size, self.num_heads = config.hidden_size, config.num_attention_heads
         explicit = getattr(config, "head_dim", None)
         self.head_dim = self.hidden_size // self.num_heads if explicit is None else int(explicit)
@@ -119,7 +124,7 @@ class LlamaAttentionMxfp4(nn.Module):
             o = ops.batch_decode_i4(q[doff:], decode_kv, self.layer_idx, rope_theta=self.rope_theta, **self.rope_kw)
             outs.append(o.view(blen.decode, hs))
         attn = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-        return ops.gemm_mxfp4(ops.reorder_quant_mx(attn.contiguous(), self.reorder_index), self.o_proj.weight_mx())
+        return ops.gemm_mxfp4(ops.reorder_quant_mx(attn.contiguous(), self.reorder_index, self.act_format), self.o_proj.weight_mx())
 
 
 class LlamaMLPMxfp4(nn.Module):
@@ -129,6 +134,7 @@ class LlamaMLPMxfp4(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.hidden_size, self.intermediate_size = config.hidden_size, config.intermediate_size
+        self.act_format = getattr(config, "activation_format", "mxfp4")
         if self.intermediate_size % 128 or self.intermediate_size < 256:
             raise ValueError(f"the MXFP4 MLP needs intermediate_size a multiple of 128 (>= 256), got {self.intermediate_size}")
         self.gate_proj = LinearMxfp4(self.hidden_size, self.intermediate_size)
@@ -143,14 +149,16 @@ class LlamaMLPMxfp4(nn.Module):
         return self._gu[1]
 
     def forward(self, x_mx, residual):
-        return ops.gemm_mxfp4(ops.gate_up_silu_quant_mx(x_mx, self.gate_up_mx()), self.down_proj.weight_mx(), add=residual)
+        return ops.gemm_mxfp4(ops.gate_up_silu_quant_mx(x_mx, self.gate_up_mx(), self.act_format), self.down_proj.weight_mx(), add=residual)
 
 
 class LlamaDecoderLayerMxfp4(nn.Module):
     """The dense Llama decoder layer on MX operands (``config.linear_format = "mxfp4"``), launch by launch:
     rmsnorm_quant_mx -> gemm_mxfp4 (q | k | v) -> the INT4 paged-KV attention -> reorder_quant_mx -> gemm_mxfp4 (o_proj) ->
     add_rmsnorm_quant_mx (the residual add of the attention block; the stream is updated in place) -> gate_up_silu_quant_mx ->
-    gemm_mxfp4(add=residual).  No host work: a decode step captures.  ``hidden_states`` is overwritten with the post-attention stream."""
+    gemm_mxfp4(add=residual).  No host work: a decode step captures.  ``hidden_states`` is overwritten with the post-attention stream.
+    ``config.activation_format = "mxfp6"`` makes the four quantising launches (both norms, o_proj's reorder quantiser, the fused
+    gate/up output) write MXFP6 activations; every GEMM then runs W4A6."""
 
     def __init__(self, config, layer_idx: int, fusion=None):
         super().__init__()
@@ -158,6 +166,9 @@ class LlamaDecoderLayerMxfp4(nn.Module):
         if fusion is not None:
             raise NotImplementedError("DecodeFusion names launches of the INT4 routes; the MXFP4 decoder layer takes none")
         self.hidden_size = config.hidden_size
+        self.act_format = getattr(config, "activation_format", "mxfp4")
+        if self.act_format not in ("mxfp4", "mxfp6"):
+            raise ValueError(f"config.activation_format must be \"mxfp4\" or \"mxfp6\", got {self.act_format!r}")
         self.self_attn = LlamaAttentionMxfp4(config, layer_idx)
         self.mlp = LlamaMLPMxfp4(config)
         self.input_layernorm = LlamaRMSNormInt4(config.hidden_size, eps=config.rms_norm_eps)            # (its parameters; the MX ops read them)
@@ -166,6 +177,6 @@ class LlamaDecoderLayerMxfp4(nn.Module):
     def forward(self, hidden_states, blen, prefill_kv, decode_kv) -> torch.Tensor:
         il, pl = self.input_layernorm, self.post_attention_layernorm
         h = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
-        attn = self.self_attn(ops.rmsnorm_quant_mx(h, il.weight, il.reorder_index, il.variance_epsilon), blen, prefill_kv, decode_kv)
-        x_mx = ops.add_rmsnorm_quant_mx(attn, h, pl.weight, pl.reorder_index, pl.variance_epsilon)      # h += attn
+        attn = self.self_attn(ops.rmsnorm_quant_mx(h, il.weight, il.reorder_index, il.variance_epsilon, self.act_format), blen, prefill_kv, decode_kv)
+        x_mx = ops.add_rmsnorm_quant_mx(attn, h, pl.weight, pl.reorder_index, pl.variance_epsilon, self.act_format)      # h += attn
         return self.mlp(x_mx, h)

@@ -1837,27 +1837,50 @@ def guide_walk_rows(state: torch.Tensor, adds: torch.Tensor, row_state: torch.Te
 # ------------------------------------------------------------------------------------------------ MXFP4 W4A4
 MxOperand = collections.namedtuple("MxOperand", "q4 sc q8 rows k")
 MxOperand.__doc__ = """An MXFP4 operand in the kernels' MFMA-fragment order (include/atom_hip.h, "MXFP4 W4A4"): q4 u8 [R, S, 64, 16] E2M1
-codes, sc u8 [R, S + 1, 64] E8M0 scale bytes, q8 u8 [R, 2, 64, 16] E4M3 keeper codes; R = ceil(rows / 16), S = k / 128 - 1."""
+codes, sc u8 [R, S + 1, 64] E8M0 scale bytes, q8 u8 [R, 2, 64, 16] E4M3 keeper codes; R = ceil(rows / 16), S = k / 128 - 1.
+An MXFP6 activation ("MXFP6 activations, W4A6") is the same tuple with q4 u8 [R, S, 96, 16] E2M3 codes (per fragment 64 lanes x 16 bytes,
+then 64 lanes x 8): the shape tells the format."""
+
+_MX_ACT_FORMATS = ("mxfp4", "mxfp6")
 
 
-def _mx_alloc(rows: int, k: int, device) -> MxOperand:
+def _mx_format_arg(fmt: str, what: str) -> bool:
+    """True for "mxfp6" """
+    if fmt not in _MX_ACT_FORMATS:
+        raise ValueError(f"{what} must be \"mxfp4\" or \"mxfp6\", got {fmt!r}")
+    return fmt == "mxfp6"
+
+
+def _mx_bulk_shape(r: int, s: int, fp6: bool):
+    return (r, s, 96, 16) if fp6 else (r, s, 64, 16)
+
+
+def _mx_alloc(rows: int, k: int, device, fp6: bool = False) -> MxOperand:
     r, s = (rows + 15) // 16, k // GROUP_SIZE - 1
-    return MxOperand(torch.empty((r, s, 64, 16), dtype=torch.uint8, device=device), torch.empty((r, s + 1, 64), dtype=torch.uint8, device=device),
+    return MxOperand(torch.empty(_mx_bulk_shape(r, s, fp6), dtype=torch.uint8, device=device),
+                     torch.empty((r, s + 1, 64), dtype=torch.uint8, device=device),
                      torch.empty((r, 2, 64, 16), dtype=torch.uint8, device=device), rows, k)
 
 
-def reorder_quant_mx(x: torch.Tensor, reorder_index: torch.Tensor = None) -> MxOperand:
+def _mx_is_fp6(o: MxOperand) -> bool:
+    return o.q4.dim() == 4 and o.q4.shape[2] == 96
+
+
+def reorder_quant_mx(x: torch.Tensor, reorder_index: torch.Tensor = None, act_format: str = "mxfp4") -> MxOperand:
     """NEW: gather fp16 ``x`` [M, K] by ``reorder_index`` (int16 [K], None = identity) and quantise it to the MX activation operand:
-    MXFP4 for the first K - 128 reordered channels, MXFP8 E4M3 for the last 128, one E8M0 scale per 32 channels."""
+    MXFP4 (``act_format="mxfp6"``: MXFP6 E2M3) for the first K - 128 reordered channels, MXFP8 E4M3 for the last 128, one E8M0 scale
+    per 32 channels."""
+    fp6 = _mx_format_arg(act_format, "act_format")
     _require_cuda_half(x, "x")
     m, k = x.shape
     if reorder_index is not None and not (reorder_index.is_cuda and reorder_index.dtype == torch.int16 and tuple(reorder_index.shape) == (k,)
                                           and reorder_index.is_contiguous()):
         raise TypeError(f"reorder_index must be a contiguous int16 tensor of [{k}] on the GPU")
-    o = _mx_alloc(m, k, x.device)
-    st = L.lib().atom_reorder_quant_mx_f16(x.data_ptr(), L.ptr(reorder_index), m, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
-                                           L.current_stream(x.device))
-    L.check(st, "atom_reorder_quant_mx_f16")
+    o = _mx_alloc(m, k, x.device, fp6)
+    name = "atom_reorder_quant_mx6_f16" if fp6 else "atom_reorder_quant_mx_f16"
+    st = getattr(L.lib(), name)(x.data_ptr(), L.ptr(reorder_index), m, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
+                                L.current_stream(x.device))
+    L.check(st, name)
     return o
 
 
@@ -1879,7 +1902,8 @@ def gemm_mxfp4_route(m: int, n: int, k: int) -> str:
 def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand, add: torch.Tensor = None) -> torch.Tensor:
     """NEW: out fp16 [M, N] = a_mx @ w_mx^T on v_mfma_scale_f32_16x16x128_f8f6f4 with the operands' own block scales (FP32
     accumulation, the keeper as one more K step).  ``add`` (fp16 [M, N]): out = half(sum + float(add)) in the same store -- the
-    residual stream of o_proj / down_proj without an elementwise launch.  One launch, no workspace: capturable."""
+    residual stream of o_proj / down_proj without an elementwise launch.  One launch, no workspace: capturable.  ``a_mx`` may be an
+    MXFP6 activation (W4A6: the format is read off the operand); the weight is always MXFP4."""
     if not (a_mx.q4.is_cuda and w_mx.q4.is_cuda):
         raise L.AtomHipError("MX operands must live on the GPU: the MXFP4 GEMM has no CPU fallback")
     if a_mx.k != w_mx.k:
@@ -1887,24 +1911,32 @@ def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand, add: torch.Tensor = None) -> to
     m, n, k = a_mx.rows, w_mx.rows, a_mx.k
     if not (_mx_native(a_mx) and _mx_native(w_mx)):
         raise ValueError("not a native MX operand (see ops.mx_from_plain)")
+    if _mx_is_fp6(w_mx):
+        raise ValueError("the weight operand must be MXFP4: only activations may be MXFP6")
     out = torch.empty((m, n), dtype=torch.float16, device=a_mx.q4.device)
     ptrs = (a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), w_mx.q4.data_ptr(), w_mx.sc.data_ptr(), w_mx.q8.data_ptr())
-    if add is None:
-        st = L.lib().atom_gemm_mxfp4_f16(*ptrs, out.data_ptr(), m, n, k, L.current_stream(out.device))
-        L.check(st, "atom_gemm_mxfp4_f16")
-    else:
+    if add is not None:
         _require_cuda_half(add, "add")
         if tuple(add.shape) != (m, n) or not add.is_contiguous():
             raise ValueError(f"add must be a contiguous fp16 [{m}, {n}], got {tuple(add.shape)}")
+    if _mx_is_fp6(a_mx):
+        st = L.lib().atom_gemm_mxfp4_a6_f16(*ptrs, L.ptr(add), out.data_ptr(), m, n, k, L.current_stream(out.device))
+        L.check(st, "atom_gemm_mxfp4_a6_f16")
+    elif add is None:
+        st = L.lib().atom_gemm_mxfp4_f16(*ptrs, out.data_ptr(), m, n, k, L.current_stream(out.device))
+        L.check(st, "atom_gemm_mxfp4_f16")
+    else:
         st = L.lib().atom_gemm_mxfp4_add_f16(*ptrs, add.data_ptr(), out.data_ptr(), m, n, k, L.current_stream(out.device))
         L.check(st, "atom_gemm_mxfp4_add_f16")
     return out
 
 
 def _mx_native(o: MxOperand) -> bool:
+    """a native operand of either bulk format (``_mx_is_fp6`` tells which)"""
     r, s = (o.rows + 15) // 16, o.k // GROUP_SIZE - 1
-    return (tuple(o.q4.shape), tuple(o.sc.shape), tuple(o.q8.shape)) == ((r, s, 64, 16), (r, s + 1, 64), (r, 2, 64, 16)) and (
-        o.q4.is_contiguous() and o.sc.is_contiguous() and o.q8.is_contiguous() and o.q4.dtype == o.sc.dtype == o.q8.dtype == torch.uint8)
+    return (tuple(o.q4.shape) in (_mx_bulk_shape(r, s, False), _mx_bulk_shape(r, s, True))
+            and (tuple(o.sc.shape), tuple(o.q8.shape)) == ((r, s + 1, 64), (r, 2, 64, 16))
+            and o.q4.is_contiguous() and o.sc.is_contiguous() and o.q8.is_contiguous() and o.q4.dtype == o.sc.dtype == o.q8.dtype == torch.uint8)
 
 
 def silu_mul_quant_mx(gate: torch.Tensor, up: torch.Tensor) -> MxOperand:
@@ -1926,8 +1958,9 @@ def fuse_gate_up_mx(gate_mx: MxOperand, up_mx: MxOperand) -> MxOperand:
     """NEW: the weight operand of ``gate_up_silu_quant_mx``: gate_proj and up_proj (native MX weight operands [F, K]) interleaved in
     pairs of 16-row fragments, [g0 g1 u0 u1 g2 g3 u2 u3 ...] -- four consecutive fragments hold gate and up of the same 32 output
     channels, one MX block of the output.  Indexing on the row-tile dimension alone (any device)."""
-    if (gate_mx.rows, gate_mx.k) != (up_mx.rows, up_mx.k) or gate_mx.rows % 32 or not (_mx_native(gate_mx) and _mx_native(up_mx)):
-        raise ValueError("gate and up: native MX weight operands of one shape, rows a multiple of 32")
+    if ((gate_mx.rows, gate_mx.k) != (up_mx.rows, up_mx.k) or gate_mx.rows % 32 or not (_mx_native(gate_mx) and _mx_native(up_mx))
+            or _mx_is_fp6(gate_mx) or _mx_is_fp6(up_mx)):
+        raise ValueError("gate and up: native MXFP4 weight operands of one shape, rows a multiple of 32")
     pairs = gate_mx.rows // 32
 
     def mix(g, u):
@@ -1940,22 +1973,29 @@ def gate_up_silu_quant_mx_route(m: int, f: int, k: int) -> str:
     return {0: None, 1: "decode", 2: "tile"}[L.lib().atom_gemm_mxfp4_silu_mul_quant_route(m, f, k)]
 
 
-def gate_up_silu_quant_mx(a_mx: MxOperand, gu_mx: MxOperand) -> MxOperand:
+def gate_up_silu_quant_mx(a_mx: MxOperand, gu_mx: MxOperand, out_format: str = "mxfp4") -> MxOperand:
     """NEW: gate_proj + up_proj + SiLU x up + MX quantiser in ONE launch: ``a_mx`` [M, K] times the fused weight of
     ``fuse_gate_up_mx`` (2 F rows) -> the MX activation operand [M, F] of silu(gate) * up that down_proj reads, taken from the FP32
-    sums (no fp16 gate / up in memory).  Capturable."""
+    sums (no fp16 gate / up in memory).  Capturable.  ``a_mx`` may be MXFP4 or MXFP6 (read off the operand); ``out_format`` picks the
+    format written."""
+    out6 = _mx_format_arg(out_format, "out_format")
     if not (a_mx.q4.is_cuda and gu_mx.q4.is_cuda):
         raise L.AtomHipError("MX operands must live on the GPU: the fused gate/up launch has no CPU fallback")
-    if a_mx.k != gu_mx.k or gu_mx.rows % 2 or not (_mx_native(a_mx) and _mx_native(gu_mx)):
-        raise ValueError("a_mx [M, K] and the fused gate/up operand [2 F, K] of ops.fuse_gate_up_mx, both native")
+    if a_mx.k != gu_mx.k or gu_mx.rows % 2 or not (_mx_native(a_mx) and _mx_native(gu_mx)) or _mx_is_fp6(gu_mx):
+        raise ValueError("a_mx [M, K] and the fused MXFP4 gate/up operand [2 F, K] of ops.fuse_gate_up_mx, both native")
     m, f, k = a_mx.rows, gu_mx.rows // 2, a_mx.k
     if L.lib().atom_gemm_mxfp4_silu_mul_quant_route(m, f, k) == 0:
         raise ValueError(f"gate_up_silu_quant_mx: M = {m}, F = {f}, K = {k} is not a shape of the kernel (F a multiple of 128, >= 256)")
-    o = _mx_alloc(m, f, a_mx.q4.device)
-    st = L.lib().atom_gemm_mxfp4_silu_mul_quant(a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), gu_mx.q4.data_ptr(),
-                                                gu_mx.sc.data_ptr(), gu_mx.q8.data_ptr(), o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(),
-                                                m, f, k, L.current_stream(a_mx.q4.device))
-    L.check(st, "atom_gemm_mxfp4_silu_mul_quant")
+    o = _mx_alloc(m, f, a_mx.q4.device, out6)
+    ptrs = (a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), gu_mx.q4.data_ptr(), gu_mx.sc.data_ptr(), gu_mx.q8.data_ptr(),
+            o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr())
+    if _mx_is_fp6(a_mx) or out6:
+        st = L.lib().atom_gemm_mxfp4_a6_silu_mul_quant(*ptrs, m, f, k, 6 if _mx_is_fp6(a_mx) else 4, 6 if out6 else 4,
+                                                       L.current_stream(a_mx.q4.device))
+        L.check(st, "atom_gemm_mxfp4_a6_silu_mul_quant")
+    else:
+        st = L.lib().atom_gemm_mxfp4_silu_mul_quant(*ptrs, m, f, k, L.current_stream(a_mx.q4.device))
+        L.check(st, "atom_gemm_mxfp4_silu_mul_quant")
     return o
 
 
@@ -1971,29 +2011,34 @@ def _rmsnorm_mx_args(x, weight, reorder_index):
     return m, k
 
 
-def rmsnorm_quant_mx(x: torch.Tensor, weight: torch.Tensor, reorder_index: torch.Tensor = None, eps: float = 1e-6) -> MxOperand:
+def rmsnorm_quant_mx(x: torch.Tensor, weight: torch.Tensor, reorder_index: torch.Tensor = None, eps: float = 1e-6,
+                     act_format: str = "mxfp4") -> MxOperand:
     """NEW: RMSNorm + channel reorder + MX activation quantiser in one launch: the operand of (x * w) / rms(x), gathered by
-    ``reorder_index``, quantised from the FP32 value (no rounding to half in front of the codes)."""
+    ``reorder_index``, quantised from the FP32 value (no rounding to half in front of the codes).  ``act_format``: "mxfp4" or "mxfp6"."""
+    fp6 = _mx_format_arg(act_format, "act_format")
     m, k = _rmsnorm_mx_args(x, weight, reorder_index)
-    o = _mx_alloc(m, k, x.device)
-    st = L.lib().atom_rmsnorm_quant_mx_f16(x.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps, o.q4.data_ptr(), o.sc.data_ptr(),
-                                           o.q8.data_ptr(), L.current_stream(x.device))
-    L.check(st, "atom_rmsnorm_quant_mx_f16")
+    o = _mx_alloc(m, k, x.device, fp6)
+    name = "atom_rmsnorm_quant_mx6_f16" if fp6 else "atom_rmsnorm_quant_mx_f16"
+    st = getattr(L.lib(), name)(x.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps, o.q4.data_ptr(), o.sc.data_ptr(),
+                                o.q8.data_ptr(), L.current_stream(x.device))
+    L.check(st, name)
     return o
 
 
 def add_rmsnorm_quant_mx(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, reorder_index: torch.Tensor = None,
-                         eps: float = 1e-6) -> MxOperand:
+                         eps: float = 1e-6, act_format: str = "mxfp4") -> MxOperand:
     """NEW: ``residual += x`` (in place: the new residual stream, one fp16 add per element), then ``rmsnorm_quant_mx`` of it, in one
     launch."""
+    fp6 = _mx_format_arg(act_format, "act_format")
     m, k = _rmsnorm_mx_args(x, weight, reorder_index)
     _require_cuda_half(residual, "residual")
     if residual.shape != x.shape or not residual.is_contiguous():
         raise ValueError(f"residual must be a contiguous fp16 {tuple(x.shape)}, got {tuple(residual.shape)}")
-    o = _mx_alloc(m, k, x.device)
-    st = L.lib().atom_add_rmsnorm_quant_mx_f16(x.data_ptr(), residual.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps,
-                                               o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(x.device))
-    L.check(st, "atom_add_rmsnorm_quant_mx_f16")
+    o = _mx_alloc(m, k, x.device, fp6)
+    name = "atom_add_rmsnorm_quant_mx6_f16" if fp6 else "atom_add_rmsnorm_quant_mx_f16"
+    st = getattr(L.lib(), name)(x.data_ptr(), residual.data_ptr(), weight.data_ptr(), L.ptr(reorder_index), m, k, eps,
+                                o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(x.device))
+    L.check(st, name)
     return o
 
 
@@ -2009,8 +2054,8 @@ def moe_gemm_mxfp4(a_mx: MxOperand, experts, route: MoeRoute, *, gather: bool, n
             raise L.AtomHipError("MX operands must live on the GPU: the routed MXFP4 GEMM has no CPU fallback")
     e, nfr, s = q4.shape[:3]
     n, k, rows = 16 * nfr, a_mx.k, route.rows
-    if not _mx_native(a_mx) or a_mx.rows != (route.tokens if gather else rows):
-        raise ValueError(f"a_mx: a native MX operand of {route.tokens if gather else rows} rows")
+    if not _mx_native(a_mx) or _mx_is_fp6(a_mx) or a_mx.rows != (route.tokens if gather else rows):
+        raise ValueError(f"a_mx: a native MXFP4 operand of {route.tokens if gather else rows} rows (the routed GEMM reads no MXFP6)")
     if (tuple(q4.shape), tuple(sc.shape), tuple(q8.shape)) != ((e, nfr, s, 64, 16), (e, nfr, s + 1, 64), (e, nfr, 2, 64, 16)) or not (
             q4.is_contiguous() and sc.is_contiguous() and q8.is_contiguous() and q4.dtype == sc.dtype == q8.dtype == torch.uint8):
         raise ValueError("experts: stacked native MX weight operands (q4, sc, q8)")
@@ -2030,17 +2075,24 @@ def moe_gemm_mxfp4(a_mx: MxOperand, experts, route: MoeRoute, *, gather: bool, n
 def mx_from_plain(codes: torch.Tensor, scales: torch.Tensor, keeper_codes: torch.Tensor, keeper_scales: torch.Tensor) -> MxOperand:
     """Plain layout -> native operand, by indexing alone (any device).  codes u8 [rows, (K - 128) / 2] (even channel in the low
     nibble), scales u8 [rows, (K - 128) / 32], keeper_codes u8 [rows, 128], keeper_scales u8 [rows, 4].  Rows are padded to a multiple
-    of 16 with zero codes and scale byte 127."""
-    rows, s = codes.shape[0], codes.shape[1] // 64
-    if (codes.shape[1] != 64 * s or s < 1 or tuple(scales.shape) != (rows, 4 * s) or tuple(keeper_codes.shape) != (rows, 128)
-            or tuple(keeper_scales.shape) != (rows, 4) or any(t.dtype != torch.uint8 for t in (codes, scales, keeper_codes, keeper_scales))):
-        raise ValueError("plain MX operand: u8 [rows, 64 S], [rows, 4 S], [rows, 128], [rows, 4]")
+    of 16 with zero codes and scale byte 127.  An MXFP6 activation: codes u8 [rows, 24 (K - 128) / 32], every block's 32 E2M3 codes as
+    its 24-byte little-endian string; the width of ``codes`` against ``scales`` tells the format."""
+    rows, s = codes.shape[0], scales.shape[1] // 4 if scales.dim() == 2 else 0
+    fp6 = codes.dim() == 2 and s >= 1 and codes.shape[1] == 96 * s
+    if (codes.dim() != 2 or codes.shape[1] != (96 if fp6 else 64) * s or s < 1 or tuple(scales.shape) != (rows, 4 * s)
+            or tuple(keeper_codes.shape) != (rows, 128) or tuple(keeper_scales.shape) != (rows, 4)
+            or any(t.dtype != torch.uint8 for t in (codes, scales, keeper_codes, keeper_scales))):
+        raise ValueError("plain MX operand: u8 [rows, 64 S] (MXFP6: [rows, 96 S]), [rows, 4 S], [rows, 128], [rows, 4]")
     r = (rows + 15) // 16
 
     def pad(t, fill):
         return torch.cat([t, t.new_full((16 * r - rows, t.shape[1]), fill)]) if rows != 16 * r else t
     # [tile, row, step, block, byte] -> [tile, step, lane = row + 16 block, byte]
-    q4 = pad(codes, 0).view(r, 16, s, 4, 16).permute(0, 2, 3, 1, 4).reshape(r, s, 64, 16)
+    if fp6:   # [tile, row, step, block, 24 bytes] -> [tile, step, lane = row + 16 block, 24]: heads (bytes 0 .. 15), then tails
+        b = pad(codes, 0).view(r, 16, s, 4, 24).permute(0, 2, 3, 1, 4).reshape(r, s, 64, 24)
+        q4 = torch.cat([b[..., :16].reshape(r, s, 1024), b[..., 16:].reshape(r, s, 512)], dim=2).view(r, s, 96, 16)
+    else:
+        q4 = pad(codes, 0).view(r, 16, s, 4, 16).permute(0, 2, 3, 1, 4).reshape(r, s, 64, 16)
     sc4 = pad(scales, 127).view(r, 16, s, 4).permute(0, 2, 3, 1).reshape(r, s, 64)
     sc8 = pad(keeper_scales, 127).view(r, 16, 4).permute(0, 2, 1).reshape(r, 1, 64)
     # [tile, row, half, group, byte] -> [tile, half, lane = row + 16 group, byte]: keeper channel 64 half + 16 group + byte
@@ -2051,7 +2103,12 @@ def mx_from_plain(codes: torch.Tensor, scales: torch.Tensor, keeper_codes: torch
 def mx_to_plain(o: MxOperand):
     """Native operand -> (codes, scales, keeper_codes, keeper_scales) in the plain layout: the inverse of ``mx_from_plain``."""
     r, s = o.q4.shape[0], o.q4.shape[1]
-    codes = o.q4.view(r, s, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(16 * r, 64 * s)
+    if _mx_is_fp6(o):
+        flat = o.q4.view(r, s, 1536)
+        b = torch.cat([flat[..., :1024].view(r, s, 64, 16), flat[..., 1024:].view(r, s, 64, 8)], dim=3)
+        codes = b.view(r, s, 4, 16, 24).permute(0, 3, 1, 2, 4).reshape(16 * r, 96 * s)
+    else:
+        codes = o.q4.view(r, s, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(16 * r, 64 * s)
     scales = o.sc[:, :s].reshape(r, s, 4, 16).permute(0, 3, 1, 2).reshape(16 * r, 4 * s)
     k8 = o.q8.view(r, 2, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(16 * r, 128)
     s8 = o.sc[:, s].reshape(r, 4, 16).permute(0, 2, 1).reshape(16 * r, 4)

@@ -1273,6 +1273,37 @@ int atom_gemm_mxfp4_f16(const void *a_q4, const void *a_sc, const void *a_q8, co
 int atom_gemm_mxfp4_route(int64_t M, int64_t N, int64_t K);
 
 /*
+ * MXFP6 activations, W4A6: the activation operand of the block above with its first K - 128 reordered channels as
+ * E2M3 codes -- 1 sign, 2 exponent, 3 mantissa bits, bias 1: 0, 0.125 .. 0.875 (subnormal), 1 .. 7.5; no NaN / Inf -- against the same
+ * MXFP4 + MXFP8 weight.  The instruction takes a format per operand and lists FP6 at the FP4 rate.  Block rule as above with emax = 2:
+ * scale byte = clamp(floor(log2 amax) - 2, -127, 127) + 127, code = |v| / 2^e to nearest even on the grid, saturated at code 31 (7.5),
+ * sign bit 0x20 exactly where v < 0.  One E8M0 byte per 32 channels; the last 128 channels are the MXFP8 keeper, unchanged.
+ * A block's 32 codes are one 192-bit little-endian string, channel c of the block at bits 6 c .. 6 c + 5 (24 bytes).
+ * Plain layout: codes u8 [rows, 24 (K - 128) / 32] (the blocks' strings in order); scales, keeper codes, keeper scales as above.
+ * Native layout: q6 u8 [R][S][1536]: per row tile and K step the heads [64 lanes][16] -- bytes 0 .. 15 of the block's string of lane
+ *   (row % 16) + 16 (block % 4), its operand registers 0 .. 3 -- then the tails [64 lanes][8], bytes 16 .. 23 (registers 4, 5); held
+ *   as u8 [R][S][96][16].  sc and q8 as above.  Rows beyond `rows` in the last tile hold zero codes and scale byte 127.
+ * atom_reorder_quant_mx6_f16 / atom_rmsnorm_quant_mx6_f16 / atom_add_rmsnorm_quant_mx6_f16: atom_reorder_quant_mx_f16 /
+ *   atom_rmsnorm_quant_mx_f16 / atom_add_rmsnorm_quant_mx_f16 writing this operand: same values, shapes, errors and padding rows.
+ * atom_gemm_mxfp4_a6_f16: atom_gemm_mxfp4_f16 (add_f16 null) or atom_gemm_mxfp4_add_f16 (add_f16 the residual fp16 [M, N]) reading
+ *   this operand: same routes (atom_gemm_mxfp4_route), accumulation chains, shapes and errors.  The weight is an MXFP4 operand.
+ * atom_gemm_mxfp4_a6_silu_mul_quant: atom_gemm_mxfp4_silu_mul_quant with the format of the activation read (act_bits) and of the
+ *   operand written (out_bits), each 4 (E2M1 bulk codes) or 6 (E2M3); any other value is ATOM_ERR_INVALID_ARG.  Same routes
+ *   (atom_gemm_mxfp4_silu_mul_quant_route), sums, SiLU expression, shapes and errors; 4, 4 is atom_gemm_mxfp4_silu_mul_quant itself.
+ */
+int atom_reorder_quant_mx6_f16(const void *x_f16, const int16_t *reorder_index, int64_t M, int64_t K, void *q6, void *sc, void *q8,
+                               void *stream);
+int atom_rmsnorm_quant_mx6_f16(const void *x_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M, int64_t K, float eps, void *q6,
+                               void *sc, void *q8, void *stream);
+int atom_add_rmsnorm_quant_mx6_f16(const void *x_f16, void *residual_inout_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M,
+                                   int64_t K, float eps, void *q6, void *sc, void *q8, void *stream);
+int atom_gemm_mxfp4_a6_f16(const void *a_q6, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                           const void *add_f16, void *out_f16, int64_t M, int64_t N, int64_t K, void *stream);
+int atom_gemm_mxfp4_a6_silu_mul_quant(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8,
+                                      void *out_q, void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, int act_bits, int out_bits,
+                                      void *stream);
+
+/*
  * Sparse mixture of experts on MXFP4 (csrc/moe_mxfp4.hip): the routed GEMM of the block above on MX operands, between
  * the same router (atom_moe_route_topk) and the same combine (atom_moe_combine_f16), and the SiLU x up quantiser that feeds its down
  * projection.

@@ -2,6 +2,7 @@
 
   python tools/mx_bench.py [--reps 5] [--iters 50]
   python tools/mx_bench.py --mlp       the fused gate/up SiLU-quantising launch against gemm_mxfp4 x 2 + silu_mul_quant_mx
+  python tools/mx_bench.py --act mxfp6 MXFP6 activations (W4A6) against the MXFP4 ones: GEMM, fused gate/up, quantiser
 
 Every figure is the median over --reps repetitions of the mean time of --iters replays of a captured graph holding one launch (hot:
 operands stay in L2 / MALL where they fit), the two sides of a comparison alternating inside one repetition; the spread printed beside
@@ -83,15 +84,36 @@ def mlp(args, dev):
                           "three_launches_us": round(t_3, 2), "three_spread_us": round(s_3, 2), "ratio": round(t_f / t_3, 3)}))
 
 
+def act6(args, dev):
+    """W4A6 against W4A4 on the same data: the FP6-activation graph alternates with the FP4 one (the FP4 graph twice: its own spread)"""
+    def row(what, M, f4, f6, **kw):
+        (t4, s4), (t6, s6), (t4b, _) = time_graphs([graph_of(f4), graph_of(f6), graph_of(f4)], args.reps, args.iters)
+        print(json.dumps({"what": what, "M": M, **kw, "mxfp4_us": round(t4, 2), "mxfp4_spread_us": round(s4, 2), "mxfp4_again_us": round(t4b, 2),
+                          "mxfp6_us": round(t6, 2), "mxfp6_spread_us": round(s6, 2), "ratio": round(t6 / t4, 3)}))
+    N = K = 4096
+    for M in (4096, 256, 16, 1):
+        x, w = operands(M, N, K, dev)
+        w_mx, a4, a6 = ops.quant_weight_mx(w), ops.reorder_quant_mx(x), ops.reorder_quant_mx(x, act_format="mxfp6")
+        row("gemm a6", M, lambda: ops.gemm_mxfp4(a4, w_mx), lambda: ops.gemm_mxfp4(a6, w_mx), N=N, K=K, route=ops.gemm_mxfp4_route(M, N, K))
+        gu_mx = ops.fuse_gate_up_mx(w_mx, ops.quant_weight_mx(operands(M + 1, N, K, dev)[1]))
+        row("gate/up a6", M, lambda: ops.gate_up_silu_quant_mx(a4, gu_mx), lambda: ops.gate_up_silu_quant_mx(a6, gu_mx, out_format="mxfp6"), F=N, K=K)
+    x, _ = operands(2048, 64, 4096, dev)
+    idx = torch.randperm(4096, device=dev).to(torch.int16)
+    row("quantiser a6", 2048, lambda: ops.reorder_quant_mx(x, idx), lambda: ops.reorder_quant_mx(x, idx, act_format="mxfp6"), K=4096)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--mlp", action="store_true")
+    ap.add_argument("--act", choices=["mxfp4", "mxfp6"], default="mxfp4")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mx_bench needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
+    if args.act == "mxfp6":
+        return act6(args, dev)
     if args.mlp:
         return mlp(args, dev)
     for M, N, K in [(4096, 4096, 4096), (1, 4096, 4096), (16, 4096, 4096), (256, 4096, 4096)]:
