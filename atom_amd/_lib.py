@@ -166,6 +166,10 @@ SIGNATURES = {
     "atom_add_rmsnorm_quant_mx6_f16": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "atom_gemm_mxfp4_a6_f16": (_int, [_vp] * 8 + [_i64, _i64, _i64, _vp]),
     "atom_gemm_mxfp4_a6_silu_mul_quant": (_int, [_vp] * 9 + [_i64, _i64, _i64, _int, _int, _vp]),
+    # MXFP6 weights, W6A4 / W6A6 (csrc/gemm_mxfp4.hip, csrc/llama_mxfp4.hip)
+    "atom_quant_weight_mx6_f16": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "atom_gemm_mx_f16": (_int, [_vp] * 8 + [_i64, _i64, _i64, _int, _int, _vp]),
+    "atom_gemm_mx_silu_mul_quant": (_int, [_vp] * 9 + [_i64, _i64, _i64, _int, _int, _int, _vp]),
 }
 
 _lib = None

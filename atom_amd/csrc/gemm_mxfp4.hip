@@ -14,7 +14,8 @@
 //   gemm_mxfp4_dec_kernel   M <= 16: one 16-feature tile per workgroup, weight fragments straight into registers, the K steps dealt
 //                           to 8 waves and summed through LDS in wave order
 // Every kernel is templated on the format of the activation's bulk codes: MxE2M1 (W4A4) or MxE2M3 (W4A6, DESIGN.md 4.29: the MXFP6
-// activation in 6 registers per lane against the same E2M1 weight, at the same MFMA rate).
+// activation in 6 registers per lane against the same E2M1 weight, at the same MFMA rate); the GEMM kernels also on the weight's
+// (W6A4 / W6A6, DESIGN.md 4.30: a 1536-byte weight fragment through its own ring arithmetic, 1.5 x the weight stream at decode).
 #include "mx_gemm.h"
 #include "quant_math.h"
 
@@ -83,14 +84,14 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const half_t *__restrict_
 
 // ------------------------------------------------------------------------------------------------------------- 128 x 128 tiles
 // (ring and K loop: mx_tile_accumulate of mx_gemm.h)
-template <bool ADD, class AF>
+template <bool ADD, class AF, class WF>
 __global__ __launch_bounds__(256) void gemm_mxfp4_tile_kernel(MxGemmParams p) {
-  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF>::LDS];
+  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF, WF>::LDS];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int wt0 = blockIdx.x * 8, at0 = blockIdx.y * 8;     // first fragment (16 features / 16 tokens) of the tile
   const int wn = w & 1, wm = w >> 1;
   v4f acc[4][4];
-  mx_tile_accumulate<AF>(p.a, p.w, p.S, wt0, at0, lds, acc);
+  mx_tile_accumulate<AF, WF>(p.a, p.w, p.S, wt0, at0, lds, acc);
   // lane l: token l % 16 of activation fragment i, features 4 (l / 16) .. + 3 of weight fragment j
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -108,13 +109,13 @@ __global__ __launch_bounds__(256) void gemm_mxfp4_tile_kernel(MxGemmParams p) {
 // (16 features), wave w = K steps w, w + 8, ... (the keeper counts as step S); the 8 partial tiles are summed in wave order.
 constexpr int MXD_WAVES = 8;
 
-template <bool ADD, class AF>
+template <bool ADD, class AF, class WF>
 __global__ __launch_bounds__(64 * MXD_WAVES) void gemm_mxfp4_dec_kernel(MxGemmParams p) {
   __shared__ v4f part[MXD_WAVES][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int64_t ct = blockIdx.x;
   v4f acc1[1];
-  mx_dec_accumulate<AF, 1, MXD_WAVES>(p.a, p.w, p.S, ct, w, l, acc1);
+  mx_dec_accumulate<AF, 1, MXD_WAVES, WF>(p.a, p.w, p.S, ct, w, l, acc1);
   const v4f acc = acc1[0];
   part[w][l] = acc;
   __syncthreads();
@@ -144,7 +145,7 @@ int launch_mx_quant(const void *x, const void *up, const int16_t *idx, int64_t r
 using namespace atom;
 
 namespace {
-template <bool ADD, class AF = MxE2M1>
+template <bool ADD, class AF = MxE2M1, class WF = MxE2M1>
 int launch_mx_gemm(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8, const void *add,
                    void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
   if (!a_q4 || !a_sc || !a_q8 || !w_q4 || !w_sc || !w_q8 || !out_f16 || (ADD && !add)) return ATOM_ERR_INVALID_ARG;
@@ -158,11 +159,18 @@ int launch_mx_gemm(const void *a_q4, const void *a_sc, const void *a_q8, const v
                  (half_t *)out_f16, (const half_t *)add, (int)M, (int)N, (int)(K / 128 - 1)};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (route == 1) {
-    hipLaunchKernelGGL((gemm_mxfp4_dec_kernel<ADD, AF>), dim3((unsigned)(N / 16)), dim3(64 * MXD_WAVES), 0, s, p);
+    hipLaunchKernelGGL((gemm_mxfp4_dec_kernel<ADD, AF, WF>), dim3((unsigned)(N / 16)), dim3(64 * MXD_WAVES), 0, s, p);
   } else {
-    hipLaunchKernelGGL((gemm_mxfp4_tile_kernel<ADD, AF>), dim3((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gemm_mxfp4_tile_kernel<ADD, AF, WF>),dim3((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
   }
   return check_launch();
+}
+
+template <class AF, class WF>
+int launch_mx_gemm_add(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, const void *add,
+                       void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
+  return add ? launch_mx_gemm<true, AF, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, add, out_f16, M, N, K, stream)
+             : launch_mx_gemm<false, AF, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, nullptr, out_f16, M, N, K, stream);
 }
 }  // namespace
 
@@ -213,6 +221,23 @@ int atom_gemm_mxfp4_a6_f16(const void *a_q6, const void *a_sc, const void *a_q8,
                            const void *add_f16, void *out_f16, int64_t M, int64_t N, int64_t K, void *stream) {
   return add_f16 ? launch_mx_gemm<true, MxE2M3>(a_q6, a_sc, a_q8, w_q4, w_sc, w_q8, add_f16, out_f16, M, N, K, stream)
                  : launch_mx_gemm<false, MxE2M3>(a_q6, a_sc, a_q8, w_q4, w_sc, w_q8, nullptr, out_f16, M, N, K, stream);
+}
+
+// ---- MXFP6 weights, W6A4 / W6A6: the weight operand's bulk codes as E2M3, wq [N/16][S][96][16]
+// (any N >= 1: rows beyond N in the last 16-row tile are zero blocks, as in an activation operand; the GEMMs ask for N % 64 == 0)
+int atom_quant_weight_mx6_f16(const void *w_f16, int64_t N, int64_t K, void *q6, void *sc, void *q8, void *stream) {
+  return launch_mx_quant<false, MxE2M3>(w_f16, nullptr, nullptr, N, K, q6, sc, q8, stream);
+}
+
+// the one entry for every pair of bulk formats: act_bits / w_bits 4 (E2M1) or 6 (E2M3); add_f16 null or the residual
+int atom_gemm_mx_f16(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, const void *add_f16,
+                     void *out_f16, int64_t M, int64_t N, int64_t K, int act_bits, int w_bits, void *stream) {
+  if ((act_bits != 4 && act_bits != 6) || (w_bits != 4 && w_bits != 6)) return ATOM_ERR_INVALID_ARG;
+  if (w_bits == 6)
+    return act_bits == 6 ? launch_mx_gemm_add<MxE2M3, MxE2M3>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, add_f16, out_f16, M, N, K, stream)
+                         : launch_mx_gemm_add<MxE2M1, MxE2M3>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, add_f16, out_f16, M, N, K, stream);
+  return act_bits == 6 ? launch_mx_gemm_add<MxE2M3, MxE2M1>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, add_f16, out_f16, M, N, K, stream)
+                       : launch_mx_gemm_add<MxE2M1, MxE2M1>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, add_f16, out_f16, M, N, K, stream);
 }
 
 }  // extern "C"

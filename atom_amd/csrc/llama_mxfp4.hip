@@ -17,6 +17,8 @@
 //                        LDS in wave order by wave 0, which runs the epilogue on the sums.
 //     Either launch reads an E2M1 or an E2M3 activation (AF) and writes E2M1 or E2M3 bulk blocks (OF): an E2M3 block is
 //     the lane's two 24-bit code quartets gathered the same way and written as the 16-byte head and 8-byte tail of its MFMA lane.
+//     WF is the format of the fused weight's bulk codes (E2M3: DESIGN.md 4.30; the decode launch then holds four 6-register weight
+//     fragments per K step); the epilogue does not depend on it.
 //   rmsnorm_quant_mx_kernel<ADD, AF>   RMSNorm (optionally x + residual first, written back) + channel reorder + MX quantiser: one workgroup
 //     of 256 per row; the row goes to LDS once while its squares are summed in quant_math.h's fixed shape, the gather reads LDS.
 #include "mx_gemm.h"
@@ -108,13 +110,13 @@ __device__ __forceinline__ void gu_block_store(const v4f &g0, const v4f &g1, con
   }
 }
 
-template <class AF, class OF>
+template <class AF, class OF, class WF>
 __global__ __launch_bounds__(256) void gu_mxfp4_tile_kernel(MxGuParams p) {
-  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF>::LDS];
+  __shared__ __attribute__((aligned(16))) char lds[MxRing<AF, WF>::LDS];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int wt0 = blockIdx.x * 8, at0 = blockIdx.y * 8;
   v4f acc[4][4];
-  mx_tile_accumulate<AF>(p.a, p.w, p.S, wt0, at0, lds, acc);
+  mx_tile_accumulate<AF, WF>(p.a, p.w, p.S, wt0, at0, lds, acc);
   const int q = blockIdx.x * 2 + (w & 1);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -125,13 +127,13 @@ __global__ __launch_bounds__(256) void gu_mxfp4_tile_kernel(MxGuParams p) {
 
 constexpr int GUD_WAVES = 8;
 
-template <class AF, class OF>
+template <class AF, class OF, class WF>
 __global__ __launch_bounds__(64 * GUD_WAVES) void gu_mxfp4_dec_kernel(MxGuParams p) {
   __shared__ v4f part[GUD_WAVES][4][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int q = blockIdx.x;
   v4f acc[4];
-  mx_dec_accumulate<AF, 4, GUD_WAVES>(p.a, p.w, p.S, (int64_t)q * 4, w, l, acc);
+  mx_dec_accumulate<AF, 4, GUD_WAVES, WF>(p.a, p.w, p.S, (int64_t)q * 4, w, l, acc);
 #pragma unroll
   for (int j = 0; j < 4; ++j) part[w][j][l] = acc[j];
   __syncthreads();
@@ -222,7 +224,7 @@ int launch_rmsnorm_quant_mx(const void *x, void *res, const void *wgt, const int
 using namespace atom;
 
 namespace {
-template <class AF, class OF>
+template <class AF, class OF, class WF = MxE2M1>
 int launch_gu(const void *a_q4, const void *a_sc, const void *a_q8, const void *w_q4, const void *w_sc, const void *w_q8, void *out_q4, void *out_sc,
               void *out_q8, int64_t M, int64_t F, int64_t K, void *stream) {
   if (!a_q4 || !a_sc || !a_q8 || !w_q4 || !w_sc || !w_q8 || !out_q4 || !out_sc || !out_q8) return ATOM_ERR_INVALID_ARG;
@@ -236,11 +238,21 @@ int launch_gu(const void *a_q4, const void *a_sc, const void *a_q8, const void *
                (uint8_t *)out_q4, (uint8_t *)out_sc, (uint8_t *)out_q8, (int)M, (int)(K / 128 - 1), (int)(F / 128 - 1)};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (route == 1) {
-    hipLaunchKernelGGL((gu_mxfp4_dec_kernel<AF, OF>), dim3((unsigned)(F / 32)), dim3(64 * GUD_WAVES), 0, s, p);
+    hipLaunchKernelGGL((gu_mxfp4_dec_kernel<AF, OF, WF>), dim3((unsigned)(F / 32)), dim3(64 * GUD_WAVES), 0, s, p);
   } else {
-    hipLaunchKernelGGL((gu_mxfp4_tile_kernel<AF, OF>), dim3((unsigned)(F / 64), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gu_mxfp4_tile_kernel<AF, OF, WF>), dim3((unsigned)(F / 64), (unsigned)((M + 127) / 128)), dim3(256), 0, s, p);
   }
   return check_launch();
+}
+
+template <class WF>
+int launch_gu_bits(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, void *out_q, void *out_sc,
+                   void *out_q8, int64_t M, int64_t F, int64_t K, int act_bits, int out_bits, void *stream) {
+  if (act_bits == 6)
+    return out_bits == 6 ? launch_gu<MxE2M3, MxE2M3, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream)
+                         : launch_gu<MxE2M3, MxE2M1, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
+  return out_bits == 6 ? launch_gu<MxE2M1, MxE2M3, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream)
+                       : launch_gu<MxE2M1, MxE2M1, WF>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
 }
 }  // namespace
 
@@ -268,6 +280,14 @@ int atom_gemm_mxfp4_a6_silu_mul_quant(const void *a_q, const void *a_sc, const v
                          : launch_gu<MxE2M3, MxE2M1>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
   return out_bits == 6 ? launch_gu<MxE2M1, MxE2M3>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream)
                        : launch_gu<MxE2M1, MxE2M1>(a_q, a_sc, a_q8, w_q4, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, stream);
+}
+
+// the one fused entry for every format triple: w_bits 6 reads the fused operand of two MXFP6 weights, [F/8][S][96][16]
+int atom_gemm_mx_silu_mul_quant(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, void *out_q,
+                                void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, int act_bits, int w_bits, int out_bits, void *stream) {
+  if ((act_bits != 4 && act_bits != 6) || (w_bits != 4 && w_bits != 6) || (out_bits != 4 && out_bits != 6)) return ATOM_ERR_INVALID_ARG;
+  return w_bits == 6 ? launch_gu_bits<MxE2M3>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, act_bits, out_bits, stream)
+                     : launch_gu_bits<MxE2M1>(a_q, a_sc, a_q8, w_q, w_sc, w_q8, out_q, out_sc, out_q8, M, F, K, act_bits, out_bits, stream);
 }
 
 int atom_rmsnorm_quant_mx_f16(const void *x_f16, const void *weight_f16, const int16_t *reorder_index, int64_t M, int64_t K, float eps, void *q4,

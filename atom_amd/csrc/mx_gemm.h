@@ -16,10 +16,11 @@ struct MxOperand {
 
 constexpr int FMT_E2M1 = 4, FMT_E4M3 = 0, FMT_E2M3 = 2;   // the instruction's cbsz / blgp codes
 
-// The bulk-code fragment (16 rows x one K step) of an activation operand by format.  E2M1: [64 lanes][16 bytes].  E2M3: a lane's 32
+// The bulk-code fragment (16 rows x one K step) of an operand, activation or weight, by format.  E2M1: [64 lanes][16 bytes].  E2M3: a lane's 32
 // codes are 24 bytes = 6 registers, stored as a head [64 lanes][16 bytes] (registers 0 .. 3) and a tail [64 lanes][8 bytes] (registers
 // 4, 5): 1024 + 512 bytes, every access a whole 16- or 8-byte piece at its natural alignment.  (A 12-byte LDS-DMA piece lands at a
-// 16-byte lane stride -- measured, DESIGN.md 4.29 -- so planes of 12 bytes would cost 2 KiB of LDS per fragment.)
+// 16-byte lane stride -- measured, DESIGN.md 4.29 -- so planes of 12 bytes would cost 2 KiB of LDS per fragment.)  The instruction reads
+// an E2M3 first operand (cbsz = 2) in the same lane and bit order as a second one (blgp = 2): measured, DESIGN.md 4.30.
 template <class AF> struct MxAct;
 template <> struct MxAct<MxE2M1> { static constexpr int FMT = FMT_E2M1, FRAG = 1024, TAIL = 0; };
 template <> struct MxAct<MxE2M3> { static constexpr int FMT = FMT_E2M3, FRAG = 1536, TAIL = 512; };
@@ -80,19 +81,22 @@ __device__ __forceinline__ void mx_quant_store8(const float (&v)[8], int c0, int
 }
 
 // ------------------------------------------------------------------------------------------------------------- 128 x 128 tiles
-// A ring slot: 8 weight fragments (1 KiB each), 8 activation fragments (MxAct<AF>::FRAG each), their scale bytes (8 x 64 + 8 x 64).  A
-// stage is one bulk K step or one half of the keeper step (stages S and S + 1, consumed together; their activation fragments are
-// 1 KiB whatever AF is).  The activation region is the 8 fragments' first KiB at 1 KiB strides, then (E2M3) their 512-byte tails in
-// the order 0 4 1 5 2 6 3 7.  Every wave requests PPW pieces of a bulk stage -- the first KiB of fragments w and w + 4 of either
-// operand with 16 bytes per lane, (E2M3) the tails of activation fragments w and w + 4 as ONE 16-byte piece (lanes 0 .. 31 / 32 .. 63:
-// they are neighbours in the tail order), a quarter of the scale bytes with 4 -- and PPW8 = 5 of a keeper stage; the waits count stages.
-// E2M1: 17 KiB per stage, 51 KiB per workgroup, 3 workgroups per CU.  E2M3: 21 KiB, 63 KiB, 2 workgroups per CU (three would need
-// 189 KiB of the CU's 160; a 2-stage ring would fit three but cannot keep a stage in flight while one is read).
-constexpr int MXT_NS = 3, MXT_FRAG = 1024, MXT_A = 8 * MXT_FRAG;
-template <class AF>
+// A ring slot: 8 weight fragments, 8 activation fragments, their scale bytes (8 x 64 + 8 x 64).  A stage is one bulk K step or one half of
+// the keeper step (stages S and S + 1, consumed together; their fragments are 1 KiB whatever the bulk formats are).  Either operand's
+// region is the 8 fragments' first KiB (heads) at 1 KiB strides, then (E2M3) their 512-byte tails in the order 0 4 1 5 2 6 3 7; the
+// activation's region follows the weight's (WA), the scale bytes follow both (SC).  Every wave requests PPW pieces of a bulk stage --
+// per operand the heads of fragments w and w + 4 with 16 bytes per lane and (E2M3) the tails of fragments w and w + 4 as ONE 16-byte
+// piece (lanes 0 .. 31 / 32 .. 63: they are neighbours in the tail order), then a quarter of the scale bytes with 4 -- and PPW8 = 5
+// of a keeper stage; the waits count stages.  Stage / ring / workgroups per CU (160 KiB) by activation x weight format:
+//   E2M1 x E2M1  17 KiB  51 KiB  3        E2M1 x E2M3  21 KiB  63 KiB  2
+//   E2M3 x E2M1  21 KiB  63 KiB  2        E2M3 x E2M3  25 KiB  75 KiB  2   (static LDS beyond 64 KiB: the runtime launches it, 4.30)
+// (three workgroups of 21 KiB stages would need 189 KiB; a 2-stage ring would fit more but cannot keep a stage in flight while one
+// is read).
+constexpr int MXT_NS = 3, MXT_FRAG = 1024;
+template <class AF, class WF = MxE2M1>
 struct MxRing {
-  static constexpr int SC = MXT_A + 8 * MxAct<AF>::FRAG, STAGE = SC + 1024, LDS = MXT_NS * STAGE;
-  static constexpr int PPW = MxAct<AF>::TAIL ? 6 : 5, PPW8 = 5;
+  static constexpr int WA = 8 * MxAct<WF>::FRAG, SC = WA + 8 * MxAct<AF>::FRAG, STAGE = SC + 1024, LDS = MXT_NS * STAGE;
+  static constexpr int PPW = 5 + (MxAct<AF>::TAIL ? 1 : 0) + (MxAct<WF>::TAIL ? 1 : 0), PPW8 = 5;
 };
 
 __device__ __forceinline__ v8i_t mx_frag4(const char *p) {
@@ -103,8 +107,8 @@ __device__ __forceinline__ v8i_t mx_frag8(const char *p0, const char *p1) {
   const v4i f = *reinterpret_cast<const v4i *>(p0), g = *reinterpret_cast<const v4i *>(p1);
   return v8i_t{f.x, f.y, f.z, f.w, g.x, g.y, g.z, g.w};
 }
-// a lane's registers of an activation fragment (LDS or memory): its 16 bytes of the head (at head + 16 l) and, E2M3, its 8 of the tail
-// (at tail + 8 l)
+// a lane's registers of a bulk fragment of either operand (LDS or memory): its 16 bytes of the head (at head + 16 l) and, E2M3, its 8
+// of the tail (at tail + 8 l)
 template <class AF>
 __device__ __forceinline__ v8i_t mx_frag_act(const char *head_l, const char *tail_l) {
   if constexpr (std::is_same_v<AF, MxE2M3>) {
@@ -118,13 +122,15 @@ __device__ __forceinline__ v8i_t mx_frag_act(const char *head_l, const char *tai
 
 // The tile's sums: weight fragments wt0 .. wt0 + 7 times activation fragments at0 .. at0 + 7, 4 waves of 64 x 64 (wave w: features
 // 64 (w & 1) .., tokens 64 (w >> 1) ..).  acc[i][j], lane l: token l % 16 of the wave's activation fragment i, features 4 (l / 16) .. + 3
-// of its weight fragment j.  Every element is one chain: K steps 0 .. S - 1 in order, then the keeper.  `lds`: MxRing<AF>::LDS bytes,
-// 16-aligned.  AF: the format of the activation's bulk codes (the weight's are E2M1).
-template <class AF>
+// of its weight fragment j.  Every element is one chain: K steps 0 .. S - 1 in order, then the keeper.  `lds`: MxRing<AF, WF>::LDS bytes,
+// 16-aligned.  AF / WF: the formats of the activation's and the weight's bulk codes.
+template <class AF, class WF = MxE2M1>
 __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const MxOperand &pw, int S, int wt0, int at0, char *lds, v4f (&acc)[4][4]) {
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int T = S + 1;
-  constexpr int AFRAG = MxAct<AF>::FRAG, MXT_SC = MxRing<AF>::SC, MXT_STAGE = MxRing<AF>::STAGE, PPW = MxRing<AF>::PPW, PPW8 = MxRing<AF>::PPW8;
+  using Ring = MxRing<AF, WF>;
+  constexpr int AFRAG = MxAct<AF>::FRAG, WFRAG = MxAct<WF>::FRAG, MXT_A = Ring::WA, MXT_SC = Ring::SC, MXT_STAGE = Ring::STAGE, PPW = Ring::PPW,
+                PPW8 = Ring::PPW8;
   const unsigned lds0 = lds_addr(lds);
   // a tile may hang over the operand's last row tile: the fragments beyond are read from the last one and their results never stored
   const int wf0 = min(wt0 + w, pw.tiles - 1), wf1 = min(wt0 + w + 4, pw.tiles - 1);
@@ -139,8 +145,15 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
     const bool k8 = st >= S;
     const int64_t per = k8 ? 2 : S, at = k8 ? st - S : st;
     const uint8_t *wb = k8 ? pw.q8 : pw.q4, *ab = k8 ? pa.q8 : pa.q4;
-    lds_dma_at<16>(wb + ((int64_t)wf0 * per + at) * MXT_FRAG + l * 16, dst + w * MXT_FRAG);
-    lds_dma_at<16>(wb + ((int64_t)wf1 * per + at) * MXT_FRAG + l * 16, dst + (w + 4) * MXT_FRAG);
+    if (std::is_same_v<WF, MxE2M3> && !k8) {
+      const uint8_t *w0 = wb + ((int64_t)wf0 * per + at) * WFRAG, *w1 = wb + ((int64_t)wf1 * per + at) * WFRAG;
+      lds_dma_at<16>(w0 + l * 16, dst + w * MXT_FRAG);
+      lds_dma_at<16>(w1 + l * 16, dst + (w + 4) * MXT_FRAG);
+      lds_dma_at<16>((l < 32 ? w0 : w1) + MXT_FRAG + (l & 31) * 16, dst + 8 * MXT_FRAG + w * 1024);            // tails 2 w, 2 w + 1
+    } else {
+      lds_dma_at<16>(wb + ((int64_t)wf0 * per + at) * MXT_FRAG + l * 16, dst + w * MXT_FRAG);
+      lds_dma_at<16>(wb + ((int64_t)wf1 * per + at) * MXT_FRAG + l * 16, dst + (w + 4) * MXT_FRAG);
+    }
     if (std::is_same_v<AF, MxE2M3> && !k8) {
       const uint8_t *a0 = ab + ((int64_t)af0 * per + at) * AFRAG, *a1 = ab + ((int64_t)af1 * per + at) * AFRAG;
       lds_dma_at<16>(a0 + l * 16, dst + MXT_A + w * MXT_FRAG);
@@ -178,11 +191,11 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const v8i_t fw = mx_frag4(slot + (wn * 4 + j) * MXT_FRAG + l * 16);
+      const v8i_t fw = mx_frag_act<WF>(slot + (wn * 4 + j) * MXT_FRAG + l * 16, slot + 8 * MXT_FRAG + (2 * j + wn) * 512 + l * 8);
       const int sw = *reinterpret_cast<const uint8_t *>(slot + MXT_SC + (wn * 4 + j) * 64 + l);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fa[i], acc[i][j], FMT_E2M1, MxAct<AF>::FMT, 0, sw, 0, sa[i]);
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fa[i], acc[i][j], MxAct<WF>::FMT, MxAct<AF>::FMT, 0, sw, 0, sa[i]);
     }
   }
   // the keeper: both halves have been requested; MXFP8 fragments are 32 bytes per lane, 16 from either slot
@@ -212,12 +225,14 @@ __device__ __forceinline__ void mx_tile_accumulate(const MxOperand &pa, const Mx
 
 // One K-step share of the decode geometry (M <= 16: a single activation fragment per step, the weight read once): the sums of the NF
 // consecutive weight fragments from ct0 on, over this wave's K steps w, w + WAVES, ... (the keeper counts as step S), weights straight
-// into registers, non-temporal.  The caller sums the waves' tiles in wave order.  AF: the format of the activation's bulk codes; its
-// fragment is 4 or 6 registers per lane, loaded straight from memory.
-template <class AF, int NF, int WAVES>
+// into registers, non-temporal.  The caller sums the waves' tiles in wave order.  AF / WF: the formats of the activation's and the
+// weight's bulk codes; either fragment is 4 or 6 registers per lane, loaded straight from memory (E2M3 weight: one dwordx4 of the head
+// and one dwordx2 of the tail per lane and fragment, both non-temporal: 1.5 x the weight stream).
+template <class AF, int NF, int WAVES, class WF = MxE2M1>
 __device__ __forceinline__ void mx_dec_accumulate(const MxOperand &pa, const MxOperand &pw, int S, int64_t ct0, int w, int l, v4f (&acc)[NF]) {
   const int T = S + 1;
-  const uint8_t *wq = pw.q4 + ct0 * S * 1024 + l * 16, *wsc = pw.sc + ct0 * T * 64 + l;
+  constexpr int WFRAG = MxAct<WF>::FRAG;
+  const uint8_t *wq = pw.q4 + ct0 * S * WFRAG + l * 16, *wsc = pw.sc + ct0 * T * 64 + l;
   const uint8_t *aq = pa.q4 + l * 16, *at = pa.q4 + 1024 + l * 8, *asc = pa.sc + l;
 #pragma unroll
   for (int j = 0; j < NF; ++j) acc[j] = v4f{0.f, 0.f, 0.f, 0.f};
@@ -227,10 +242,13 @@ __device__ __forceinline__ void mx_dec_accumulate(const MxOperand &pa, const MxO
     const int sa = asc[st * 64];
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-      const v4i fw = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(wq + ((int64_t)j * S + st) * 1024));
+      const uint8_t *wf = wq + ((int64_t)j * S + st) * WFRAG;
+      const v4i fw = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(wf));
+      v2u ft = {0u, 0u};
+      if constexpr (std::is_same_v<WF, MxE2M3>) ft = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(wf + 1024 - l * 8));
       const int sw = wsc[(j * T + st) * 64];
-      acc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(v8i_t{fw.x, fw.y, fw.z, fw.w, 0, 0, 0, 0}, fa, acc[j], FMT_E2M1, MxAct<AF>::FMT, 0, sw,
-                                                                0, sa);
+      acc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(v8i_t{fw.x, fw.y, fw.z, fw.w, (int)ft.x, (int)ft.y, 0, 0}, fa, acc[j],
+                                                                MxAct<WF>::FMT, MxAct<AF>::FMT, 0, sw, 0, sa);
     }
   }
   if (w == S % WAVES) {

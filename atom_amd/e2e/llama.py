@@ -623,12 +623,17 @@ class LlamaModel(nn.Module):
         """``config.linear_format``: "int4" (default: ``layer_class``) or "mxfp4" (the dense MX decoder layer of e2e/mx.py, DESIGN.md
         4.28; ``NotImplementedError`` on the subclasses that stack another layer: Mixtral, LoRA).  ``config.activation_format``:
         "mxfp4" (default) or "mxfp6" (W4A6), the format of the MX layer's quantised activations; "mxfp6" needs
-        ``linear_format = "mxfp4"``."""
+        ``linear_format = "mxfp4"``.  ``config.weight_format``: "mxfp4" (default), "mxfp6" (W6A4 / W6A6) or a mapping of
+        the MX layer's weight groups ("qkv", "o_proj", "gate_up", "down_proj"; missing keys are "mxfp4") to one of the two; any
+        "mxfp6" in it needs ``linear_format = "mxfp4"``."""
+        from .mx import weight_formats
         fmt, act = getattr(config, "linear_format", "int4"), getattr(config, "activation_format", "mxfp4")
         if fmt not in ("int4", "mxfp4"):
             raise ValueError(f"config.linear_format must be \"int4\" or \"mxfp4\", got {fmt!r}")
         if act not in ("mxfp4", "mxfp6") or (act == "mxfp6" and fmt != "mxfp4"):
             raise ValueError(f"config.activation_format must be \"mxfp4\" or, with linear_format = \"mxfp4\", \"mxfp6\"; got {act!r} with {fmt!r}")
+        if "mxfp6" in weight_formats(config).values() and fmt != "mxfp4":
+            raise ValueError(f"config.weight_format = {config.weight_format!r} needs linear_format = \"mxfp4\", got {fmt!r}")
         if fmt == "int4":
             return cls.layer_class
         if cls.layer_class is not LlamaDecoderLayer:

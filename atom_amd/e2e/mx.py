@@ -7,20 +7,37 @@ from torch import nn
 from .. import ops
 
 
+WEIGHT_GROUPS = ("qkv", "o_proj", "gate_up", "down_proj")      # the four weight operands of LlamaDecoderLayerMxfp4
+
+
+def weight_formats(config) -> dict:
+    """``config.weight_format`` as {group: "mxfp4" | "mxfp6"} over WEIGHT_GROUPS: a string names all four, a mapping its keys (missing
+    keys are "mxfp4"); anything else is a ``ValueError``."""
+    wf = getattr(config, "weight_format", "mxfp4")
+    if isinstance(wf, str):
+        wf = dict.fromkeys(WEIGHT_GROUPS, wf)
+    if not hasattr(wf, "keys") or any(k not in WEIGHT_GROUPS or wf[k] not in ("mxfp4", "mxfp6") for k in wf.keys()):
+        raise ValueError(f"config.weight_format must be \"mxfp4\", \"mxfp6\" or a mapping of {WEIGHT_GROUPS} to one of them, got {wf!r}")
+    return {g: wf.get(g, "mxfp4") for g in WEIGHT_GROUPS}
+
+
 class LinearMxfp4(nn.Module):
     """``forward(x_fp16, reorder_index)`` = quantise the reordered activation to MX, then the MXFP4 GEMM against the MX weight.
-    ``act_format``: "mxfp4" (W4A4) or "mxfp6" (W4A6: E2M3 activations, same weight)."""
+    ``act_format``: "mxfp4" (W4A4) or "mxfp6" (W4A6: E2M3 activations, same weight).  ``weight_format``: "mxfp4" or "mxfp6" (E2M3
+    bulk codes, W6A4 / W6A6, DESIGN.md 4.30: ``weight_fp4`` then holds [R, S, 96, 16])."""
 
-    def __init__(self, in_features, out_features, act_format="mxfp4"):
+    def __init__(self, in_features, out_features, act_format="mxfp4", weight_format="mxfp4"):
         super().__init__()
         if act_format not in ("mxfp4", "mxfp6"):
             raise ValueError(f"act_format must be \"mxfp4\" or \"mxfp6\", got {act_format!r}")
-        self.act_format = act_format
+        if weight_format not in ("mxfp4", "mxfp6"):
+            raise ValueError(f"weight_format must be \"mxfp4\" or \"mxfp6\", got {weight_format!r}")
+        self.act_format, self.weight_format = act_format, weight_format
         if in_features % 128 or in_features < 256 or out_features % 64 or out_features < 64:
             raise ValueError("LinearMxfp4: in_features a multiple of 128 (>= 256), out_features a multiple of 64")
         self.in_features, self.out_features = in_features, out_features
         r, s = out_features // 16, in_features // 128 - 1
-        self.weight_fp4 = nn.Parameter(torch.empty(r, s, 64, 16, dtype=torch.uint8), requires_grad=False)
+        self.weight_fp4 = nn.Parameter(torch.empty(r, s, 96 if weight_format == "mxfp6" else 64, 16, dtype=torch.uint8), requires_grad=False)
         self.weight_scale = nn.Parameter(torch.empty(r, s + 1, 64, dtype=torch.uint8), requires_grad=False)
         self.weight_fp8 = nn.Parameter(torch.empty(r, 2, 64, 16, dtype=torch.uint8), requires_grad=False)
 
@@ -29,7 +46,7 @@ class LinearMxfp4(nn.Module):
         """Fill the parameters from a (column-reordered) fp16 weight [out, in]."""
         if tuple(weight.shape) != (self.out_features, self.in_features):
             raise ValueError(f"weight must be [{self.out_features}, {self.in_features}], got {tuple(weight.shape)}")
-        w = ops.quant_weight_mx(weight.contiguous())
+        w = ops.quant_weight_mx(weight.contiguous(), self.weight_format)
         self.weight_fp4.data, self.weight_scale.data, self.weight_fp8.data = w.q4, w.sc, w.q8
         return self
 
@@ -72,10 +89,11 @@ class LlamaAttentionMxfp4(nn.Module):
         if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads:
             raise ValueError(f"num_key_value_heads {self.num_kv_heads} does not divide num_attention_heads {self.num_heads}")
         self.kv_dim = self.num_kv_heads * self.head_dim
-        self.q_proj = LinearMxfp4(self.hidden_size, self.hidden_size)
-        self.k_proj = LinearMxfp4(self.hidden_size, self.kv_dim)
-        self.v_proj = LinearMxfp4(self.hidden_size, self.kv_dim)
-        self.o_proj = LinearMxfp4(self.hidden_size, self.hidden_size)
+        wf = weight_formats(config)
+        self.q_proj = LinearMxfp4(self.hidden_size, self.hidden_size, weight_format=wf["qkv"])
+        self.k_proj = LinearMxfp4(self.hidden_size, self.kv_dim, weight_format=wf["qkv"])
+        self.v_proj = LinearMxfp4(self.hidden_size, self.kv_dim, weight_format=wf["qkv"])
+        self.o_proj = LinearMxfp4(self.hidden_size, self.hidden_size, weight_format=wf["o_proj"])
         self.reorder_index = nn.Parameter(torch.randperm(self.hidden_size).to(torch.int16), requires_grad=False)
         self.rope_theta, self.rope_scale, inv_freq, attention_factor = rope_init(config, self.head_dim)
         self.attn_scale = float(attention_factor) ** 2
@@ -137,15 +155,16 @@ class LlamaMLPMxfp4(nn.Module):
         self.act_format = getattr(config, "activation_format", "mxfp4")
         if self.intermediate_size % 128 or self.intermediate_size < 256:
             raise ValueError(f"the MXFP4 MLP needs intermediate_size a multiple of 128 (>= 256), got {self.intermediate_size}")
-        self.gate_proj = LinearMxfp4(self.hidden_size, self.intermediate_size)
-        self.up_proj = LinearMxfp4(self.hidden_size, self.intermediate_size)
-        self.down_proj = LinearMxfp4(self.intermediate_size, self.hidden_size)
+        wf = weight_formats(config)
+        self.gate_proj = LinearMxfp4(self.hidden_size, self.intermediate_size, weight_format=wf["gate_up"])
+        self.up_proj = LinearMxfp4(self.hidden_size, self.intermediate_size, weight_format=wf["gate_up"])
+        self.down_proj = LinearMxfp4(self.intermediate_size, self.hidden_size, weight_format=wf["down_proj"])
 
     def gate_up_mx(self) -> ops.MxOperand:
         mods = [self.gate_proj, self.up_proj]
         key = _mx_key(mods)
         if getattr(self, "_gu", None) is None or self._gu[0] != key:
-            self._gu = (key, ops.fuse_gate_up_mx(self.gate_proj.weight_mx(), self.up_proj.weight_mx()))
+            self._gu = (key, ops.fuse_gate_up_mx(self.gate_proj.weight_mx(), self.up_proj.weight_mx(), self.gate_proj.weight_format))
         return self._gu[1]
 
     def forward(self, x_mx, residual):
@@ -158,7 +177,9 @@ class LlamaDecoderLayerMxfp4(nn.Module):
     add_rmsnorm_quant_mx (the residual add of the attention block; the stream is updated in place) -> gate_up_silu_quant_mx ->
     gemm_mxfp4(add=residual).  No host work: a decode step captures.  ``hidden_states`` is overwritten with the post-attention stream.
     ``config.activation_format = "mxfp6"`` makes the four quantising launches (both norms, o_proj's reorder quantiser, the fused
-    gate/up output) write MXFP6 activations; every GEMM then runs W4A6."""
+    gate/up output) write MXFP6 activations; every GEMM then runs W4A6.  ``config.weight_format`` ("mxfp4", "mxfp6"
+    or a mapping over ``WEIGHT_GROUPS``) gives the four weight operands E2M3 bulk codes, all or some; the launches are
+    the same, the ops read each format off its operand."""
 
     def __init__(self, config, layer_idx: int, fusion=None):
         super().__init__()

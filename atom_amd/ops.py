@@ -1839,7 +1839,7 @@ MxOperand = collections.namedtuple("MxOperand", "q4 sc q8 rows k")
 MxOperand.__doc__ = """An MXFP4 operand in the kernels' MFMA-fragment order (include/atom_hip.h, "MXFP4 W4A4"): q4 u8 [R, S, 64, 16] E2M1
 codes, sc u8 [R, S + 1, 64] E8M0 scale bytes, q8 u8 [R, 2, 64, 16] E4M3 keeper codes; R = ceil(rows / 16), S = k / 128 - 1.
 An MXFP6 activation ("MXFP6 activations, W4A6") is the same tuple with q4 u8 [R, S, 96, 16] E2M3 codes (per fragment 64 lanes x 16 bytes,
-then 64 lanes x 8): the shape tells the format."""
+then 64 lanes x 8): the shape tells the format.  An MXFP6 weight ("MXFP6 weights, W6A4 / W6A6") has that same form."""
 
 _MX_ACT_FORMATS = ("mxfp4", "mxfp6")
 
@@ -1884,13 +1884,16 @@ def reorder_quant_mx(x: torch.Tensor, reorder_index: torch.Tensor = None, act_fo
     return o
 
 
-def quant_weight_mx(weight: torch.Tensor) -> MxOperand:
-    """NEW: quantise an already column-reordered fp16 weight [N, K] to the MX weight operand (same arithmetic as ``reorder_quant_mx``)."""
+def quant_weight_mx(weight: torch.Tensor, weight_format: str = "mxfp4") -> MxOperand:
+    """NEW: quantise an already column-reordered fp16 weight [N, K] to the MX weight operand (same arithmetic as ``reorder_quant_mx``).
+    ``weight_format="mxfp6"``: E2M3 bulk codes (W6A4 / W6A6), the native layout of an MXFP6 activation."""
+    fp6 = _mx_format_arg(weight_format, "weight_format")
     _require_cuda_half(weight, "weight")
     n, k = weight.shape
-    o = _mx_alloc(n, k, weight.device)
-    st = L.lib().atom_quant_weight_mx_f16(weight.data_ptr(), n, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(weight.device))
-    L.check(st, "atom_quant_weight_mx_f16")
+    o = _mx_alloc(n, k, weight.device, fp6)
+    name = "atom_quant_weight_mx6_f16" if fp6 else "atom_quant_weight_mx_f16"
+    st = getattr(L.lib(), name)(weight.data_ptr(), n, k, o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr(), L.current_stream(weight.device))
+    L.check(st, name)
     return o
 
 
@@ -1902,8 +1905,8 @@ def gemm_mxfp4_route(m: int, n: int, k: int) -> str:
 def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand, add: torch.Tensor = None) -> torch.Tensor:
     """NEW: out fp16 [M, N] = a_mx @ w_mx^T on v_mfma_scale_f32_16x16x128_f8f6f4 with the operands' own block scales (FP32
     accumulation, the keeper as one more K step).  ``add`` (fp16 [M, N]): out = half(sum + float(add)) in the same store -- the
-    residual stream of o_proj / down_proj without an elementwise launch.  One launch, no workspace: capturable.  ``a_mx`` may be an
-    MXFP6 activation (W4A6: the format is read off the operand); the weight is always MXFP4."""
+    residual stream of o_proj / down_proj without an elementwise launch.  One launch, no workspace: capturable.  Either operand may
+    be MXFP6 (W4A6, W6A4, W6A6: the formats are read off the operands)."""
     if not (a_mx.q4.is_cuda and w_mx.q4.is_cuda):
         raise L.AtomHipError("MX operands must live on the GPU: the MXFP4 GEMM has no CPU fallback")
     if a_mx.k != w_mx.k:
@@ -1911,15 +1914,16 @@ def gemm_mxfp4(a_mx: MxOperand, w_mx: MxOperand, add: torch.Tensor = None) -> to
     m, n, k = a_mx.rows, w_mx.rows, a_mx.k
     if not (_mx_native(a_mx) and _mx_native(w_mx)):
         raise ValueError("not a native MX operand (see ops.mx_from_plain)")
-    if _mx_is_fp6(w_mx):
-        raise ValueError("the weight operand must be MXFP4: only activations may be MXFP6")
     out = torch.empty((m, n), dtype=torch.float16, device=a_mx.q4.device)
     ptrs = (a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), w_mx.q4.data_ptr(), w_mx.sc.data_ptr(), w_mx.q8.data_ptr())
     if add is not None:
         _require_cuda_half(add, "add")
         if tuple(add.shape) != (m, n) or not add.is_contiguous():
             raise ValueError(f"add must be a contiguous fp16 [{m}, {n}], got {tuple(add.shape)}")
-    if _mx_is_fp6(a_mx):
+    if _mx_is_fp6(w_mx):
+        st = L.lib().atom_gemm_mx_f16(*ptrs, L.ptr(add), out.data_ptr(), m, n, k, 6 if _mx_is_fp6(a_mx) else 4, 6, L.current_stream(out.device))
+        L.check(st, "atom_gemm_mx_f16")
+    elif _mx_is_fp6(a_mx):
         st = L.lib().atom_gemm_mxfp4_a6_f16(*ptrs, L.ptr(add), out.data_ptr(), m, n, k, L.current_stream(out.device))
         L.check(st, "atom_gemm_mxfp4_a6_f16")
     elif add is None:
@@ -1954,13 +1958,15 @@ def silu_mul_quant_mx(gate: torch.Tensor, up: torch.Tensor) -> MxOperand:
     return o
 
 
-def fuse_gate_up_mx(gate_mx: MxOperand, up_mx: MxOperand) -> MxOperand:
+def fuse_gate_up_mx(gate_mx: MxOperand, up_mx: MxOperand, weight_format: str = "mxfp4") -> MxOperand:
     """NEW: the weight operand of ``gate_up_silu_quant_mx``: gate_proj and up_proj (native MX weight operands [F, K]) interleaved in
     pairs of 16-row fragments, [g0 g1 u0 u1 g2 g3 u2 u3 ...] -- four consecutive fragments hold gate and up of the same 32 output
-    channels, one MX block of the output.  Indexing on the row-tile dimension alone (any device)."""
+    channels, one MX block of the output.  Indexing on the row-tile dimension alone (any device).  MXFP6 weights are fused only with
+    ``weight_format="mxfp6"`` said aloud: an MXFP6 weight has the shape of an MXFP6 activation, which is no operand of this op."""
+    fp6 = _mx_format_arg(weight_format, "weight_format")
     if ((gate_mx.rows, gate_mx.k) != (up_mx.rows, up_mx.k) or gate_mx.rows % 32 or not (_mx_native(gate_mx) and _mx_native(up_mx))
-            or _mx_is_fp6(gate_mx) or _mx_is_fp6(up_mx)):
-        raise ValueError("gate and up: native MXFP4 weight operands of one shape, rows a multiple of 32")
+            or _mx_is_fp6(gate_mx) != fp6 or _mx_is_fp6(up_mx) != fp6):
+        raise ValueError(f"gate and up: native {'MXFP6' if fp6 else 'MXFP4'} weight operands of one shape, rows a multiple of 32")
     pairs = gate_mx.rows // 32
 
     def mix(g, u):
@@ -1976,20 +1982,23 @@ def gate_up_silu_quant_mx_route(m: int, f: int, k: int) -> str:
 def gate_up_silu_quant_mx(a_mx: MxOperand, gu_mx: MxOperand, out_format: str = "mxfp4") -> MxOperand:
     """NEW: gate_proj + up_proj + SiLU x up + MX quantiser in ONE launch: ``a_mx`` [M, K] times the fused weight of
     ``fuse_gate_up_mx`` (2 F rows) -> the MX activation operand [M, F] of silu(gate) * up that down_proj reads, taken from the FP32
-    sums (no fp16 gate / up in memory).  Capturable.  ``a_mx`` may be MXFP4 or MXFP6 (read off the operand); ``out_format`` picks the
-    format written."""
+    sums (no fp16 gate / up in memory).  Capturable.  ``a_mx`` and ``gu_mx`` may be MXFP4 or MXFP6 (read off the operands);
+    ``out_format`` picks the format written."""
     out6 = _mx_format_arg(out_format, "out_format")
     if not (a_mx.q4.is_cuda and gu_mx.q4.is_cuda):
         raise L.AtomHipError("MX operands must live on the GPU: the fused gate/up launch has no CPU fallback")
-    if a_mx.k != gu_mx.k or gu_mx.rows % 2 or not (_mx_native(a_mx) and _mx_native(gu_mx)) or _mx_is_fp6(gu_mx):
-        raise ValueError("a_mx [M, K] and the fused MXFP4 gate/up operand [2 F, K] of ops.fuse_gate_up_mx, both native")
+    if a_mx.k != gu_mx.k or gu_mx.rows % 2 or not (_mx_native(a_mx) and _mx_native(gu_mx)):
+        raise ValueError("a_mx [M, K] and the fused gate/up operand [2 F, K] of ops.fuse_gate_up_mx, both native")
     m, f, k = a_mx.rows, gu_mx.rows // 2, a_mx.k
     if L.lib().atom_gemm_mxfp4_silu_mul_quant_route(m, f, k) == 0:
         raise ValueError(f"gate_up_silu_quant_mx: M = {m}, F = {f}, K = {k} is not a shape of the kernel (F a multiple of 128, >= 256)")
     o = _mx_alloc(m, f, a_mx.q4.device, out6)
     ptrs = (a_mx.q4.data_ptr(), a_mx.sc.data_ptr(), a_mx.q8.data_ptr(), gu_mx.q4.data_ptr(), gu_mx.sc.data_ptr(), gu_mx.q8.data_ptr(),
             o.q4.data_ptr(), o.sc.data_ptr(), o.q8.data_ptr())
-    if _mx_is_fp6(a_mx) or out6:
+    if _mx_is_fp6(gu_mx):
+        st = L.lib().atom_gemm_mx_silu_mul_quant(*ptrs, m, f, k, 6 if _mx_is_fp6(a_mx) else 4, 6, 6 if out6 else 4, L.current_stream(a_mx.q4.device))
+        L.check(st, "atom_gemm_mx_silu_mul_quant")
+    elif _mx_is_fp6(a_mx) or out6:
         st = L.lib().atom_gemm_mxfp4_a6_silu_mul_quant(*ptrs, m, f, k, 6 if _mx_is_fp6(a_mx) else 4, 6 if out6 else 4,
                                                        L.current_stream(a_mx.q4.device))
         L.check(st, "atom_gemm_mxfp4_a6_silu_mul_quant")

@@ -1304,6 +1304,26 @@ int atom_gemm_mxfp4_a6_silu_mul_quant(const void *a_q, const void *a_sc, const v
                                       void *stream);
 
 /*
+ * MXFP6 weights, W6A4 / W6A6: the WEIGHT operand with its first K - 128 reordered channels as E2M3 codes, by the
+ * block rule, the plain layout and the native layout of the MXFP6 activation above (the instruction reads an E2M3 first operand in
+ * the same lane and bit order as a second one): wq u8 [N/16][S][96][16], sc and q8 unchanged.  E3M2 is not built.
+ * atom_quant_weight_mx6_f16: atom_quant_weight_mx_f16 writing this operand: same values and errors; any N >= 1 (rows beyond N in
+ *   the last tile are zero blocks, as in an activation operand), the GEMM entries below still ask for N a multiple of 64.
+ * atom_gemm_mx_f16: the GEMM for every pair of bulk formats: act_bits / w_bits are 4 (E2M1) or 6 (E2M3), any other value is
+ *   ATOM_ERR_INVALID_ARG; add_f16 is null or the residual fp16 [M, N] (may be out_f16).  Same routes (atom_gemm_mxfp4_route),
+ *   accumulation chains (K steps in order, then the keeper), shapes, alignment checks and errors as atom_gemm_mxfp4_f16; (4, 4) and
+ *   (6, 4) launch the kernels of atom_gemm_mxfp4_f16 / _add_f16 and atom_gemm_mxfp4_a6_f16.
+ * atom_gemm_mx_silu_mul_quant: atom_gemm_mxfp4_a6_silu_mul_quant with the format of the fused weight (w_bits; 6: two MXFP6 weights
+ *   interleaved in pairs of fragments as the MXFP4 ones are, [F/8][S][96][16]).  Same routes (atom_gemm_mxfp4_silu_mul_quant_route),
+ *   sums, SiLU expression, shapes and errors; w_bits = 4 is that entry itself.
+ */
+int atom_quant_weight_mx6_f16(const void *w_f16, int64_t N, int64_t K, void *q6, void *sc, void *q8, void *stream);
+int atom_gemm_mx_f16(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, const void *add_f16,
+                     void *out_f16, int64_t M, int64_t N, int64_t K, int act_bits, int w_bits, void *stream);
+int atom_gemm_mx_silu_mul_quant(const void *a_q, const void *a_sc, const void *a_q8, const void *w_q, const void *w_sc, const void *w_q8, void *out_q,
+                                void *out_sc, void *out_q8, int64_t M, int64_t F, int64_t K, int act_bits, int w_bits, int out_bits, void *stream);
+
+/*
  * Sparse mixture of experts on MXFP4 (csrc/moe_mxfp4.hip): the routed GEMM of the block above on MX operands, between
  * the same router (atom_moe_route_topk) and the same combine (atom_moe_combine_f16), and the SiLU x up quantiser that feeds its down
  * projection.

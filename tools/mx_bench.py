@@ -3,6 +3,7 @@
   python tools/mx_bench.py [--reps 5] [--iters 50]
   python tools/mx_bench.py --mlp       the fused gate/up SiLU-quantising launch against gemm_mxfp4 x 2 + silu_mul_quant_mx
   python tools/mx_bench.py --act mxfp6 MXFP6 activations (W4A6) against the MXFP4 ones: GEMM, fused gate/up, quantiser
+  python tools/mx_bench.py --weight mxfp6   MXFP6 weights against the MXFP4 ones under either activation: GEMM, fused gate/up
 
 Every figure is the median over --reps repetitions of the mean time of --iters replays of a captured graph holding one launch (hot:
 operands stay in L2 / MALL where they fit), the two sides of a comparison alternating inside one repetition; the spread printed beside
@@ -102,16 +103,40 @@ def act6(args, dev):
     row("quantiser a6", 2048, lambda: ops.reorder_quant_mx(x, idx), lambda: ops.reorder_quant_mx(x, idx, act_format="mxfp6"), K=4096)
 
 
+def weight6(args, dev):
+    """MXFP6 weights against MXFP4 ones on the same data, per activation format: W6A4 against W4A4, W6A6 against W4A6 (the MXFP4-weight
+    graph twice: its own spread)"""
+    def row(what, M, f4, f6, **kw):
+        (t4, s4), (t6, s6), (t4b, _) = time_graphs([graph_of(f4), graph_of(f6), graph_of(f4)], args.reps, args.iters)
+        print(json.dumps({"what": what, "M": M, **kw, "w4_us": round(t4, 2), "w4_spread_us": round(s4, 2), "w4_again_us": round(t4b, 2),
+                          "w6_us": round(t6, 2), "w6_spread_us": round(s6, 2), "ratio": round(t6 / t4, 3)}))
+    N = K = 4096
+    for M in (4096, 256, 16, 1):
+        x, w = operands(M, N, K, dev)
+        wu = operands(M + 1, N, K, dev)[1]
+        w4, w6 = ops.quant_weight_mx(w), ops.quant_weight_mx(w, weight_format="mxfp6")
+        gu4 = ops.fuse_gate_up_mx(w4, ops.quant_weight_mx(wu))
+        gu6 = ops.fuse_gate_up_mx(w6, ops.quant_weight_mx(wu, weight_format="mxfp6"), weight_format="mxfp6")
+        for act in ("mxfp4", "mxfp6"):
+            a = ops.reorder_quant_mx(x, act_format=act)
+            row("gemm w6", M, lambda: ops.gemm_mxfp4(a, w4), lambda: ops.gemm_mxfp4(a, w6), act=act, N=N, K=K, route=ops.gemm_mxfp4_route(M, N, K))
+            row("gate/up w6", M, lambda: ops.gate_up_silu_quant_mx(a, gu4, out_format=act), lambda: ops.gate_up_silu_quant_mx(a, gu6, out_format=act),
+                act=act, F=N, K=K)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--mlp", action="store_true")
     ap.add_argument("--act", choices=["mxfp4", "mxfp6"], default="mxfp4")
+    ap.add_argument("--weight", choices=["mxfp4", "mxfp6"], default="mxfp4")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mx_bench needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
+    if args.weight == "mxfp6":
+        return weight6(args, dev)
     if args.act == "mxfp6":
         return act6(args, dev)
     if args.mlp:
